@@ -13,11 +13,18 @@ N ranks as child processes (before it makes any GPU call itself) and relays rank
 weak scaling (one full-size batch per rank); `strong_scaling` = BASELINE.json configs[3], ONE 2-bit dump
 split N ways as memb_amd.sharding.shard_range does (the reference's own split, src/reader.cpp:65-79).
 
+A plain run sets up (build, the one model, the reader), warms up, times the K steps and prints the record; with
+`--dump-outputs DIR` it also writes what the last timed step computed (dump_outputs). Everything else the benchmark
+measures or checks runs with `--full` only: parity of the timed output with the CPU checker, the CPU baseline, every
+BASELINE.json configuration, the strong-scaling leg (N > 1), the live rocprofv3 counter passes behind
+roofline.traffic and the burst timing of kernels below 0.2 ms.
+
 Rank 0 writes ONE line to stdout: a compact JSON object, the record. It stays below 8 KB
 (tests/test_bench_contract.py; the driver's record keeps the last 8 081 characters of stdout): the required keys,
-`roofline`, `cpu_baseline` and one terse entry per BASELINE.json configuration. Everything measured, verbose, goes
-to stderr (`detail: {...}`) and to gpurun_out/bench_detail.json. Ceilings, word search and host-API legs live in
-tools/perf/bench_extras.py (`--extras` runs them into the detail).
+`roofline`, `cpu_baseline` and (--full) one terse entry per BASELINE.json configuration. Everything measured, verbose,
+goes to stderr (`detail: {...}`) and to the file MEMB_BENCH_DETAIL names (default: bench_detail.json in the
+repository's output folder). Ceilings, word search and host-API legs live in tools/perf/bench_extras.py (`--extras`
+runs them into the detail).
 """
 import argparse
 import ctypes
@@ -39,6 +46,7 @@ FASTTEXT_WORDS = 1999995
 MISSING = 0xFFFFFFFF
 FILL_LAUNCHES = 40
 LINE_LIMIT = 8000               # the driver's record keeps the last 8 081 characters of stdout
+DUMP_BYTES = 48 << 20           # --dump-outputs: larger outputs are written as a fixed, seeded sample of their rows
 
 WORKLOADS = {
     # name: (words, bits, batch) ; batch None = every key (full dump)
@@ -71,7 +79,14 @@ def parse_args():
     parser.add_argument('--small', action='store_true', help='shrink every model to 50 000 words (plumbing rehearsal)')
     parser.add_argument('--host-writer', action='store_true', help='write the synthetic models with the host writer (same bytes)')
     parser.add_argument('--dry-launch', action='store_true', help='--gpus N: print the launch command and what the parent saw; start nothing')
-    return parser.parse_args()
+    parser.add_argument('--full', action='store_true',
+                        help='also everything beyond the headline: parity with the CPU checker, the CPU baseline, every BASELINE.json '
+                             'configuration, the strong-scaling leg (N > 1), live counter passes, burst timing of short kernels')
+    parser.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed to DIR/*.npy (float32, float64)')
+    args = parser.parse_args()
+    if not args.full:   # a plain run: set-up, warmup, the timed steps, the record
+        args.no_cpu_baseline = args.no_configs = args.no_live_traffic = True
+    return args
 
 
 # --------------------------------------------------------------------------------------------
@@ -103,6 +118,22 @@ def sampled_parity(path, rows_host, got_rows, sample=20000, seed=5):
     expected = oracle.OracleReader(path, os.cpu_count() or 1).rows_embedding(np.ascontiguousarray(rows_host[picks]))
     same = np.array_equal(np.ascontiguousarray(got_rows(picks)).view(np.uint32), expected.view(np.uint32))
     return 'bit-exact ({} sampled rows)'.format(len(picks)) if same else 'MISMATCH'
+
+
+def dump_outputs(directory, out, torch, np):
+    """--dump-outputs: the (n, dim) float32 result of the last timed step, as a caller of that path receives it. An output
+    above DUMP_BYTES is written as the same seeded sample of its rows in every run; embeddings_rows.npy says which."""
+    count, dim = out.shape
+    keep = max(1, DUMP_BYTES // (4 * dim))
+    if count <= keep:
+        picks = np.arange(count)
+        got = out.cpu().numpy()
+    else:
+        picks = np.sort(np.random.default_rng(2024).choice(count, size=keep, replace=False))
+        got = out[torch.from_numpy(picks).cuda()].cpu().numpy()
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, 'embeddings.npy'), np.ascontiguousarray(got, dtype=np.float32))
+    np.save(os.path.join(directory, 'embeddings_rows.npy'), picks.astype(np.float64))
 
 
 def batch_rows(count, batch, np, seed=11):
@@ -549,6 +580,8 @@ def main():
         slowest = torch.tensor([elapsed], dtype=torch.float64, device='cuda')
         dist.all_reduce(slowest, op=dist.ReduceOp.MAX)
         elapsed = float(slowest.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rotation[(turn[0] - 1) % len(rotation)][1] if rotation else out, torch, np)
     in_order = [starts[i].elapsed_time(stops[i]) for i in range(args.steps)]
     kernel_ms = sorted(in_order)
     if special is None:
@@ -556,7 +589,7 @@ def main():
     kernel_avg_ms = sum(kernel_ms) / len(kernel_ms)
     kernel_min_ms, kernel_median_ms = kernel_ms[0], kernel_ms[len(kernel_ms) // 2]
     kernel_timing = 'HIP event pair around every launch of the timed region: average'
-    if kernel_avg_ms < 0.2:
+    if kernel_avg_ms < 0.2 and args.full:
         averages = timer.bursts(step, args.steps)
         kernel_avg_ms, kernel_min_ms, kernel_median_ms = sum(averages) / len(averages), averages[0], averages[len(averages) // 2]
         kernel_timing = '5 bursts of {} back-to-back launches after the timed region, one HIP event pair per burst: average per launch'.format(args.steps)
@@ -584,14 +617,14 @@ def main():
     baseline = None
     parity = 'skipped'
     cpu_legs = not args.no_cpu_baseline and world_size == 1
-    if special is None and rotation is not None:
+    if special is None and rotation is not None and not args.no_cpu_baseline:
         reader.rows_embedding_device(rows, out=out)   # (the configured batch is the one that is checked)
         torch.cuda.synchronize()
     if cpu_legs:
         baseline, expected = cpu_baseline(path, rows_host, dim)
         parity = 'bit-exact' if np.array_equal(out.cpu().numpy().view(np.uint32), expected.view(np.uint32)) else 'MISMATCH'
         del expected
-    elif special is not None:
+    elif special is not None and args.full:
         parity = special['parity']()
     elif not args.no_cpu_baseline:
         parity = sampled_parity(path, rows_host, lambda picks: out[torch.from_numpy(picks).cuda()].cpu().numpy())

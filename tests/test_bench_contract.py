@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import REPO
@@ -121,7 +122,7 @@ def test_eight_rank_plumbing_on_the_cpu(native, tmp_path):
     the script itself, gloo rendezvous, host stand-ins for everything that would touch a device
     (MEMB_BENCH_REHEARSAL=cpu: bench.install_host_stand_ins). What it pins is the plumbing -- every rank reports,
     the strong-scaling split covers the vocabulary once, the line keeps its contract -- not a single number."""
-    line = run_bench(['--gpus', '8', '--small', '--steps', '2', '--warmup', '1'], tmp_path,
+    line = run_bench(['--gpus', '8', '--small', '--steps', '2', '--warmup', '1', '--full'], tmp_path,
                      MEMB_BENCH_REHEARSAL='cpu', OMP_NUM_THREADS='1')
     for key in CONTRACT_KEYS:
         assert key in line, key
@@ -144,6 +145,42 @@ def test_eight_rank_plumbing_on_the_cpu(native, tmp_path):
                             tmp_path, MEMB_BENCH_REHEARSAL='cpu', OMP_NUM_THREADS='1')
     assert strong_main['scaling'] == 'strong' and strong_main['ranks_seen'] == 8
     assert sum(entry['batch'] for entry in strong_main['per_rank']) == 50000
+
+
+def check_plain_run_and_dump(tmp_path, **extra_env):
+    """A plain run (no --full) of the 100 000-row workload on the 50 000-word model: the record with its contract keys,
+    exactly --steps timed steps, ONE model written, nothing of --full; --dump-outputs holds what the LAST timed step wrote
+    (four batches round-robin: 1 warmup + 3 steps end on the fourth), bit for bit the CPU checker's rows."""
+    import glob
+
+    import oracle
+    sys.path.insert(0, REPO)
+    import bench
+    tmp_path.mkdir(exist_ok=True)
+    dump = tmp_path / 'outputs'
+    line = run_bench(['--small', '--workload', 'glove840b-300d-4bit-100k', '--steps', '3', '--warmup', '1',
+                      '--dump-outputs', str(dump)], tmp_path, **extra_env)
+    for key in CONTRACT_KEYS:
+        assert key in line, key
+    assert line['steps'] == 3 and line['warmup'] == 1 and line['ms_per_step'] > 0 and line['value'] > 0
+    assert abs(line['value'] - 100000 / (line['ms_per_step'] * 1e-3)) < 1e-3 * line['value']
+    assert len(line['_detail']['roofline']['kernel_ms_in_launch_order']) == 3
+    assert line['cpu_baseline'] is None and line.get('configs') is None and line['parity_vs_cpu_checker'] == 'skipped'
+    models = glob.glob(str(tmp_path / 'models' / '*.bin'))
+    assert len(models) == 1, models
+    embeddings, rows = np.load(dump / 'embeddings.npy'), np.load(dump / 'embeddings_rows.npy')
+    assert embeddings.dtype == np.float32 and rows.dtype == np.float64
+    assert embeddings.shape == (len(rows), 300) and len(rows) == bench.DUMP_BYTES // 1200 < 100000
+    assert np.all(np.diff(rows) > 0) and rows[-1] < 100000
+    last_batch = bench.batch_rows(50000, 100000, np, seed=14)
+    expected = oracle.OracleReader(models[0]).rows_embedding(np.ascontiguousarray(last_batch[rows.astype(np.int64)]))
+    assert np.array_equal(embeddings.view(np.uint32), expected.view(np.uint32))
+    return embeddings
+
+
+def test_plain_run_and_its_outputs_on_the_cpu(native, tmp_path):
+    """The plain path's plumbing with host stand-ins for the device (MEMB_BENCH_REHEARSAL=cpu, one rank)."""
+    check_plain_run_and_dump(tmp_path, MEMB_BENCH_REHEARSAL='cpu', OMP_NUM_THREADS='1')
 
 
 def test_the_process_group_never_carries_data(native):
@@ -206,7 +243,7 @@ def test_gpus_are_counted_from_the_kfd_topology(tmp_path):
 
 @gpu
 def test_single_gpu_line_and_configuration_array(native, tmp_path):
-    line = run_bench(['--small', '--steps', '3', '--warmup', '1', '--extras'], tmp_path)
+    line = run_bench(['--small', '--steps', '3', '--warmup', '1', '--extras', '--full'], tmp_path)
     for key in CONTRACT_KEYS:
         assert key in line, key
     assert line['n_gpus'] == 1 and line['steps'] == 3 and line['scaling'] == 'weak' and line['vs_baseline'] is None
@@ -246,8 +283,16 @@ def test_single_gpu_line_and_configuration_array(native, tmp_path):
 
 
 @gpu
+def test_plain_run_and_its_outputs(native, tmp_path):
+    # twice, each run writing its model afresh: the same arguments give the same inputs, so the same outputs
+    first = check_plain_run_and_dump(tmp_path / 'first')
+    second = check_plain_run_and_dump(tmp_path / 'second')
+    assert np.array_equal(first.view(np.uint32), second.view(np.uint32))
+
+
+@gpu
 def test_two_ranks_started_without_a_launcher(native, tmp_path):
-    line = run_bench(['--gpus', '2', '--small', '--steps', '2', '--warmup', '1'], tmp_path, MEMB_BENCH_REHEARSAL='1')
+    line = run_bench(['--gpus', '2', '--small', '--steps', '2', '--warmup', '1', '--full'], tmp_path, MEMB_BENCH_REHEARSAL='1')
     assert line['n_gpus'] == 2 and line['ranks_seen'] == 2 and len(line['per_rank']) == 2
     assert line['launcher']['parent_mapped_hip_runtime'] is False and line['launcher']['parent_imported_torch'] is False
     assert line['parity_vs_cpu_checker'].startswith('bit-exact')
@@ -270,7 +315,7 @@ def test_two_ranks_started_without_a_launcher(native, tmp_path):
 def test_four_rank_rehearsal(native, tmp_path):
     # as many ranks as a one-GPU box allows next to the test process (at most 6 processes may use the card);
     # the 8-way split itself is covered on the CPU: tests/test_sharding_gloo.py, tests/test_gpu_full_size.py
-    line = run_bench(['--gpus', '4', '--small', '--steps', '2', '--warmup', '1', '--no-cpu-baseline'], tmp_path,
+    line = run_bench(['--gpus', '4', '--small', '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--full'], tmp_path,
                      MEMB_BENCH_REHEARSAL='1')
     assert line['n_gpus'] == 4 and line['ranks_seen'] == 4
     strong = line['strong_scaling']

@@ -366,6 +366,6 @@ def run(bench, reader, path, rows_host, out, timer, library, torch, np, kernel_a
 if __name__ == '__main__':
     import sys
     sys.path.insert(0, REPO)
-    sys.argv = [sys.argv[0], '--extras', '--no-configs', '--no-live-traffic'] + sys.argv[1:]
+    sys.argv = [sys.argv[0], '--extras', '--full', '--no-configs', '--no-live-traffic'] + sys.argv[1:]
     import bench
     bench.main()

@@ -1,11 +1,11 @@
 #!/bin/bash
-# The default bench.py as the driver runs it (the record on stdout), then once more with --extras (ceilings, word search, host API into the detail).
+# bench.py --full (the record on stdout), then once more with --extras (ceilings, word search, host API into the detail).
 set -o pipefail
 out=gpurun_out/r6_final_${1:-a}
 mkdir -p $out
 export MEMB_SYNTH_DEVICE=0
 start=$(date +%s)
-timeout -k 10 400 python bench.py > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
 echo "default run: $(( $(date +%s) - start )) s, record $(wc -c < $out/bench.json) bytes"
 cp gpurun_out/bench_detail.json $out/bench_detail.json
 timeout -k 10 500 python bench.py --extras --no-configs > $out/extras.json 2> $out/extras.err || { tail -20 $out/extras.err; exit 1; }

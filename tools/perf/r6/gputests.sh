@@ -1,12 +1,12 @@
 #!/bin/bash
-# The whole -m gpu suite in one process, then the default bench.py (the record on stdout, the detail on stderr).
+# The whole -m gpu suite in one process, then bench.py --full (the record on stdout, the detail on stderr).
 set -o pipefail
 out=gpurun_out/r6_gputests
 mkdir -p $out
 export MEMB_SYNTH_DEVICE=0
 timeout -k 10 900 python -m pytest tests -x -q -m gpu --capture=sys > $out/pytest.txt 2>&1 || { tail -40 $out/pytest.txt; exit 1; }
 tail -3 $out/pytest.txt
-timeout -k 10 400 python bench.py > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
 wc -c $out/bench.json
 python - <<'P'
 import json
