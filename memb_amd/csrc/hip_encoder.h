@@ -373,14 +373,9 @@ int encoder_pack_checked(
     if (code == MEMB_HIP_OK) {
         params.streamOffsets = deviceOffsets;
         params.packed = encoder->packed;
-        hipError_t status = hipFuncSetAttribute(
-            reinterpret_cast<const void*>(&pack_streams), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (status == hipSuccess) {
-            hipLaunchKernelGGL(
-                pack_streams, dim3(blocks), dim3(threads), 4 * (256 + waves * static_cast<uint32_t>(imageDwords)), encoder->stream, params);
-            status = hipGetLastError();
-        }
-        code = check(status, "pack_streams launch");
+        code = check(
+            launchKernel(&pack_streams, dim3(blocks), dim3(threads), 4 * (256 + waves * static_cast<uint32_t>(imageDwords)), encoder->stream, params),
+            "pack_streams launch");
     }
     if (code == MEMB_HIP_OK) {
         code = check(hipStreamSynchronize(encoder->stream), "pack_streams");

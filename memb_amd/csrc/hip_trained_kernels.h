@@ -28,10 +28,12 @@ struct TrainedParams {
                                     // row's address needs no lookup, its offsets arrive with its stream: a random
                                     // word costs two line requests (index entry + straddling stream: 3.2)
     uint32_t loadPieces;            // pieces copied to LDS per word (recordPieces, or the whole slot: slotDwords / 4)
-    uint16_t* segmentIndexOut;      // OUT_INDEX: index being built, [nRows][indexLanes - 1]
+    union {
+        uint16_t* segmentIndexOut;  // OUT_INDEX: index being built, [nRows][indexLanes - 1]
                                     // (both hold 32-bit entries when indexWide: rows longer than 65535 bits)
-                                    // Lookup modes of decode_trained: null, or where the launch leaves what it SAW of the
+        uint32_t* orderOut;         // lookup modes of decode_trained: null, or where the launch leaves what it SAW of the
                                     // batch's order (one uint32_t in pinned host memory, noteBatchOrder below)
+    };
     const uint32_t* table;          // 8-byte entries, see TableEntry
     const float* codebook;          // 256 centroids, or 256 centroid pairs (FAST)
     unsigned long long nRows;
@@ -667,7 +669,6 @@ __device__ __forceinline__ TrainedParams batchOfTile(const TrainedParams& p, con
 // may both write it (a plain store of 0 or 1).
 __device__ __forceinline__ void noteBatchOrder(const TrainedParams& p, uint32_t lane)
 {
-    uint32_t* seen = reinterpret_cast<uint32_t*>(p.segmentIndexOut);
     uint32_t consecutive = 1;
     if (p.rows && p.n >= 2) {
         const unsigned long long at = (p.n - 2) / (WAVE - 1) * lane;   // <= n - 2
@@ -675,7 +676,7 @@ __device__ __forceinline__ void noteBatchOrder(const TrainedParams& p, uint32_t 
     }
     const uint32_t pairs = __popcll(__ballot(consecutive != 0));
     if (lane == 0) {
-        __hip_atomic_store(seen, pairs >= 48 ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(p.orderOut, pairs >= 48 ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 
@@ -710,7 +711,7 @@ __device__ __forceinline__ void decodeTilesOfBlock(const TrainedParams& p, const
     // sign with a cruder ordering).
     const WaveLds mem = setUpLds<MODE>(p, lds);
 #ifndef MEMB_HIP_NO_ORDER_PROBE   // (two builds side by side: tools/perf/r6/probe_cost.sh)
-    if (!BATCHES && MODE != OUT_INDEX && blockIdx.x == 0 && threadIdx.x < WAVE && p.segmentIndexOut) {   // (one wavefront of the grid)
+    if (!BATCHES && MODE != OUT_INDEX && blockIdx.x == 0 && threadIdx.x < WAVE && p.orderOut) {   // (one wavefront of the grid)
         noteBatchOrder(p, lane);
     }
 #endif

@@ -50,6 +50,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 namespace {
@@ -172,7 +173,7 @@ struct memb_hip_ctx {
     uint32_t fineLanes = 0;
     uint32_t fineSymbols = 0;
     uint32_t recordPieces = 0;           // non-zero: row records (TrainedParams::recordPieces); `streams` is that array
-    char unionKernel[96] = {0};            // what the last union launch with this context as its first model ran
+    const char* unionKernel = "";        // what the last union launch with this context as its first model ran (kernelTable)
     uint32_t lanesPerWord = 1;           // G: lanes that share one word
     uint32_t segmentSymbols = 0;         // S: symbols per lane, multiple of 4
     std::vector<uint32_t> streamBytes;   // per row, host side (reporting only)
@@ -289,6 +290,29 @@ uint32_t trainedLdsBytes(const memb_hip_ctx* ctx, uint32_t waves, uint32_t words
     return 4u * (ctx->tableDwords + codebookDwords(ctx) + waves * perWave);
 }
 
+// How a kernel writes rows of dim floats to out + row * ld + colOff: in 16-byte pieces where every row starts 16-byte
+// aligned, as one dense run of pieces where the rows lie back to back, else one float at a time.
+int outputMode(uint32_t dim, size_t ld, size_t colOff, const void* out)
+{
+    if (dim % 4 != 0 || ld % 4 != 0 || colOff % 4 != 0 || reinterpret_cast<uintptr_t>(out) % 16 != 0) {
+        return OUT_SCALAR;
+    }
+    return ld == dim && colOff == 0 ? OUT_FLAT : OUT_VEC4;
+}
+
+// Wavefronts a CU holds in blocks of `waves` with ldsBytes of LDS each (0: the block does not fit). LDS is handed out in
+// 1 KiB steps of a 160 KiB pool; at most 32 waves per CU, fewer when the kernel's registers say so (registerWaves: 512
+// per lane and SIMD, MI355X_MICROARCH.md "Register files").
+uint32_t residentWaves(uint32_t ldsLimit, uint32_t waves, uint32_t ldsBytes, uint32_t registerWaves)
+{
+    if (ldsBytes > ldsLimit) {
+        return 0;
+    }
+    const uint32_t blocksPerCu = std::min<uint32_t>(
+        ldsLimit / ((ldsBytes + 1023) / 1024 * 1024), std::max<uint32_t>(1, std::min<uint32_t>(32, registerWaves) / waves));
+    return blocksPerCu * waves;
+}
+
 // Wavefronts per block: the PREFERRED size (planTrained: eight for batches of more than 16 R tiles, else four), unless
 // another size lets a CU hold at least a quarter more resident wavefronts (LDS is handed out per block: the 8-bit model's
 // 33 KiB of tables leave 12 wavefronts per CU in blocks of four and 16 in blocks of eight, which is worth 10-17 %; the
@@ -304,14 +328,7 @@ TrainedGeometry chooseGeometry(
     const uint32_t forcedWaves = ctx->switches.waves;   // (1 .. 16; anything but 1, 2, 4, 8: measurements)
     auto residentWith = [&](uint32_t waves, uint32_t* ldsBytes) -> uint32_t {
         *ldsBytes = trainedLdsBytes(ctx, waves, wordsPerWave, true);
-        if (*ldsBytes > ctx->ldsLimit) {
-            return 0;
-        }
-        // LDS is handed out in 1 KiB steps of a 160 KiB pool; at most 32 waves per CU, fewer when the kernel's
-        // registers say so (512 per lane and SIMD, MI355X_MICROARCH.md "Register files")
-        const uint32_t blocksPerCu = std::min<uint32_t>(
-            ctx->ldsLimit / ((*ldsBytes + 1023) / 1024 * 1024), std::max<uint32_t>(1, std::min<uint32_t>(32, registerWavesPerCu) / waves));
-        return blocksPerCu * waves;
+        return residentWaves(ctx->ldsLimit, waves, *ldsBytes, registerWavesPerCu);
     };
     uint32_t preferredLds = 0;
     const uint32_t wanted = forcedWaves ? forcedWaves : preferred;
@@ -335,213 +352,209 @@ TrainedGeometry chooseGeometry(
         best.ldsBytes = preferredLds;
         best.resident = preferredResident;
     }
-    const bool vec = (ctx->dim % 4 == 0) && (ld % 4 == 0) && (colOff % 4 == 0) &&
-        (reinterpret_cast<uintptr_t>(out) % 16 == 0);
-    if (!vec) {
-        best.mode = OUT_SCALAR;
-    } else if (ld == ctx->dim && colOff == 0) {
-        best.mode = OUT_FLAT;
-    } else {
-        best.mode = OUT_VEC4;
-    }
+    best.mode = outputMode(ctx->dim, ld, colOff, out);
     return best;
 }
 
-template <bool HAS_SUB, int MODE, bool FAST>
-hipError_t launchTrainedVariant(const TrainedParams& params, uint32_t blocks, uint32_t threads, uint32_t ldsBytes, hipStream_t stream)
+// One instance of a kernel template: the function and its name as in the symbol, e.g. decode_trained<false, 2, true>
+// (what info() reports as `kernel` and `union_kernel`).
+template <typename... A>
+struct KernelInstance {
+    void (*fn)(A...) = nullptr;
+    std::string name;
+};
+
+std::string templateArgument(bool value)
 {
-    static thread_local int configuredDevice = -1;
-    int device = 0;
-    (void)hipGetDevice(&device);
-    if (configuredDevice != device) {
-        hipError_t status = hipFuncSetAttribute(
-            reinterpret_cast<const void*>(&decode_trained<HAS_SUB, MODE, FAST>),
-            hipFuncAttributeMaxDynamicSharedMemorySize,
-            160 * 1024);
-        if (status != hipSuccess) {
-            return status;
+    return value ? "true" : "false";
+}
+
+std::string templateArgument(int value)
+{
+    return std::to_string(value);
+}
+
+template <typename... T>
+std::string instanceName(const char* family, T... arguments)
+{
+    std::string name = family;
+    const char* separator = "<";
+    ((name += separator + templateArgument(arguments), separator = ", "), ...);
+    return name + ">";
+}
+
+// The kernel table: every instance of the five decode kernel templates, indexed by its template arguments, empty where
+// no instance exists (tests/test_isa.py counts them). Key forms <HAS_SUB, FAST>: <false, true> nibble keys (a one-level
+// table), <false, false> and <true, false> byte keys with a one- or a two-level table.
+struct KernelTable {
+    KernelInstance<TrainedParams> trained[2][5][2];              // decode_trained<HAS_SUB, MODE, FAST>
+    KernelInstance<TrainedParams> persistent[2][5][2];           // decode_records_persistent<HAS_SUB, MODE, FAST>: not OUT_INDEX
+    KernelInstance<TrainedParams, BatchList> batches[2][3][2];   // decode_trained_batches<HAS_SUB, MODE, FAST>: OUT_SCALAR .. OUT_FLAT
+    KernelInstance<UnionParams> unions[2][2][5][2];              // decode_trained_union<HAS_SUB, FAST, COUNT, AVERAGE>: COUNT 2 .. 4
+    KernelInstance<UnionParams> split[2][2][2][2];               // decode_union_split<HAS_SUB, FAST, AVERAGE, COMPACT>: COMPACT
+                                                                 // with nibble keys only
+
+    KernelTable()
+    {
+        addKeyForm<false, true>();
+        addKeyForm<false, false>();
+        addKeyForm<true, false>();
+    }
+
+private:
+    template <bool HAS_SUB, bool FAST>
+    void addKeyForm()
+    {
+        addMode<HAS_SUB, FAST, OUT_SCALAR>();
+        addMode<HAS_SUB, FAST, OUT_VEC4>();
+        addMode<HAS_SUB, FAST, OUT_FLAT>();
+        addMode<HAS_SUB, FAST, OUT_INDEX>();
+        addMode<HAS_SUB, FAST, OUT_KEYS>();
+        addUnion<HAS_SUB, FAST, 2, false>();
+        addUnion<HAS_SUB, FAST, 2, true>();
+        addUnion<HAS_SUB, FAST, 3, false>();
+        addUnion<HAS_SUB, FAST, 3, true>();
+        addUnion<HAS_SUB, FAST, 4, false>();
+        addUnion<HAS_SUB, FAST, 4, true>();
+    }
+
+    template <bool HAS_SUB, bool FAST, int MODE>
+    void addMode()
+    {
+        trained[HAS_SUB][MODE][FAST] = {&decode_trained<HAS_SUB, MODE, FAST>, instanceName("decode_trained", HAS_SUB, MODE, FAST)};
+        if constexpr (MODE != OUT_INDEX) {
+            persistent[HAS_SUB][MODE][FAST] = {
+                &decode_records_persistent<HAS_SUB, MODE, FAST>, instanceName("decode_records_persistent", HAS_SUB, MODE, FAST)};
         }
-        configuredDevice = device;
-    }
-    hipLaunchKernelGGL(
-        (decode_trained<HAS_SUB, MODE, FAST>), dim3(blocks), dim3(threads), ldsBytes, stream, params);
-    return hipGetLastError();
-}
-
-template <bool HAS_SUB, int MODE, bool FAST>
-hipError_t launchBatchesVariant(
-    const TrainedParams& params, const BatchList& list, uint32_t blocks, uint32_t threads, uint32_t ldsBytes, hipStream_t stream)
-{
-    static thread_local int configuredDevice = -1;
-    int device = 0;
-    (void)hipGetDevice(&device);
-    if (configuredDevice != device) {
-        hipError_t status = hipFuncSetAttribute(
-            reinterpret_cast<const void*>(&decode_trained_batches<HAS_SUB, MODE, FAST>),
-            hipFuncAttributeMaxDynamicSharedMemorySize,
-            160 * 1024);
-        if (status != hipSuccess) {
-            return status;
+        if constexpr (MODE <= OUT_FLAT) {
+            batches[HAS_SUB][MODE][FAST] = {
+                &decode_trained_batches<HAS_SUB, MODE, FAST>, instanceName("decode_trained_batches", HAS_SUB, MODE, FAST)};
         }
-        configuredDevice = device;
     }
-    hipLaunchKernelGGL(
-        (decode_trained_batches<HAS_SUB, MODE, FAST>), dim3(blocks), dim3(threads), ldsBytes, stream, params, list);
-    return hipGetLastError();
-}
 
-template <int MODE>
-hipError_t launchBatchesMode(
-    const memb_hip_ctx* ctx, const TrainedParams& params, const BatchList& list, uint32_t blocks, uint32_t threads,
-    uint32_t ldsBytes, hipStream_t stream)
+    template <bool HAS_SUB, bool FAST, int COUNT, bool AVERAGE>
+    void addUnion()
+    {
+        unions[HAS_SUB][FAST][COUNT][AVERAGE] = {
+            &decode_trained_union<HAS_SUB, FAST, COUNT, AVERAGE>, instanceName("decode_trained_union", HAS_SUB, FAST, COUNT, AVERAGE)};
+        if constexpr (COUNT == 2) {
+            split[HAS_SUB][FAST][AVERAGE][false] = {
+                &decode_union_split<HAS_SUB, FAST, AVERAGE, false>, instanceName("decode_union_split", HAS_SUB, FAST, AVERAGE, false)};
+        }
+        if constexpr (COUNT == 2 && FAST) {
+            split[HAS_SUB][FAST][AVERAGE][true] = {
+                &decode_union_split<HAS_SUB, FAST, AVERAGE, true>, instanceName("decode_union_split", HAS_SUB, FAST, AVERAGE, true)};
+        }
+    }
+};
+
+const KernelTable& kernelTable()
 {
-    if (ctx->fast) {
-        return launchBatchesVariant<false, MODE, true>(params, list, blocks, threads, ldsBytes, stream);
-    }
-    return ctx->byteTable.hasSubTables ? launchBatchesVariant<true, MODE, false>(params, list, blocks, threads, ldsBytes, stream)
-                                       : launchBatchesVariant<false, MODE, false>(params, list, blocks, threads, ldsBytes, stream);
+    static const KernelTable table;
+    return table;
 }
 
-typedef void (*TrainedKernel)(TrainedParams);
-
-// decode_records_persistent as instantiated for a context and an output mode.
-template <int MODE>
-TrainedKernel recordsKernelOfMode(const memb_hip_ctx* ctx)
+// HAS_SUB of a model's lookup kernels: byte keys decode through the 4-byte PACKED table (the index pass reads the 8-byte
+// one: buildSegmentIndex), nibble keys have a one-level table.
+bool lookupHasSub(const memb_hip_ctx* ctx)
 {
-    if (ctx->fast) {
-        return &decode_records_persistent<false, MODE, true>;
-    }
-    return ctx->byteTable.hasSubTables ? &decode_records_persistent<true, MODE, false>
-                                       : &decode_records_persistent<false, MODE, false>;
+    return !ctx->fast && ctx->byteTable.hasSubTables;
 }
 
-TrainedKernel recordsKernel(const memb_hip_ctx* ctx, int mode)
+// decode_trained (persistent: decode_records_persistent) for a model's lookups in this output mode
+const KernelInstance<TrainedParams>& lookupKernel(const memb_hip_ctx* ctx, bool persistent, int mode)
 {
-    switch (mode) {
-        case OUT_FLAT:
-            return recordsKernelOfMode<OUT_FLAT>(ctx);
-        case OUT_VEC4:
-            return recordsKernelOfMode<OUT_VEC4>(ctx);
-        case OUT_KEYS:
-            return recordsKernelOfMode<OUT_KEYS>(ctx);
-        default:
-            return recordsKernelOfMode<OUT_SCALAR>(ctx);
-    }
+    return (persistent ? kernelTable().persistent : kernelTable().trained)[lookupHasSub(ctx)][mode][ctx->fast];
 }
 
-// What the runtime knows about a kernel on a device: registers (-> wavefronts a CU can hold) and, per
-// (block size, LDS), the resident blocks per CU. Looked up once.
+// What the runtime knows about a kernel on the current device, looked up once per (kernel, device) -- which is also when
+// the kernel's dynamic-LDS limit is raised to the 160 KiB of a CU: its registers (-> wavefronts a CU can hold) and, for
+// blocks of `threads` (non-zero) with ldsBytes of LDS, how many such blocks a CU holds.
 struct KernelFacts {
     int numRegs = 0;
     uint32_t registerWavesPerCu = 32;
-    bool ldsRaised = false;
-    std::vector<std::pair<std::pair<uint32_t, uint32_t>, int>> blocksPerCu;   // (threads, ldsBytes) -> blocks
+    int blocksPerCu = 0;
 };
 
-std::mutex g_kernelFactsMutex;
-std::vector<std::pair<std::pair<const void*, int>, KernelFacts>> g_kernelFacts;   // (kernel, device) ->
-
-// (caller holds g_kernelFactsMutex)
-hipError_t kernelFactsLocked(const void* kernel, KernelFacts** out)
+hipError_t kernelFacts(const void* kernel, KernelFacts* out, uint32_t threads = 0, uint32_t ldsBytes = 0)
 {
+    struct Known {
+        const void* kernel;
+        int device;
+        KernelFacts facts;
+        std::vector<std::pair<std::pair<uint32_t, uint32_t>, int>> blocksPerCu;   // (threads, ldsBytes) -> blocks
+    };
+    static std::mutex mutex;
+    static std::vector<Known> known;
     int device = 0;
     (void)hipGetDevice(&device);
-    for (auto& entry : g_kernelFacts) {
-        if (entry.first.first == kernel && entry.first.second == device) {
-            *out = &entry.second;
-            return hipSuccess;
-        }
-    }
-    KernelFacts facts;
-    hipFuncAttributes attributes;
-    hipError_t status = hipFuncGetAttributes(&attributes, kernel);
-    if (status != hipSuccess) {
-        return status;
-    }
-    facts.numRegs = attributes.numRegs;
-    // allocation granule 8 registers, 512 per lane per SIMD, 4 SIMDs, at most 8 wavefronts each
-    const int allocated = std::max(8, (attributes.numRegs + 7) / 8 * 8);
-    facts.registerWavesPerCu = 4u * static_cast<uint32_t>(std::min(8, 512 / allocated));
-    status = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (status != hipSuccess) {
-        return status;
-    }
-    facts.ldsRaised = true;
-    g_kernelFacts.push_back({{kernel, device}, facts});
-    *out = &g_kernelFacts.back().second;
-    return hipSuccess;
-}
-
-hipError_t registerWavesPerCu(TrainedKernel kernel, uint32_t* waves, int* numRegs)
-{
-    std::lock_guard<std::mutex> lock(g_kernelFactsMutex);
-    KernelFacts* facts = nullptr;
-    hipError_t status = kernelFactsLocked(reinterpret_cast<const void*>(kernel), &facts);
-    if (status == hipSuccess) {
-        *waves = facts->registerWavesPerCu;
-        *numRegs = facts->numRegs;
-    }
-    return status;
-}
-
-// launch(blocks) enqueues `kernel` (threads per block, ldsBytes of dynamic LDS) with that many blocks.
-template <typename Launch>
-hipError_t launchPersistentGeneric(
-    const memb_hip_ctx* ctx, const void* kernel, Launch launch, uint32_t tileBlocks, uint32_t threads, uint32_t ldsBytes,
-    uint32_t tilesPerWave = 0)
-{
-    int blocksPerCu = 0;
-    {
-        std::lock_guard<std::mutex> lock(g_kernelFactsMutex);
-        KernelFacts* facts = nullptr;
-        hipError_t status = kernelFactsLocked(kernel, &facts);
+    std::lock_guard<std::mutex> lock(mutex);
+    auto entry = std::find_if(known.begin(), known.end(), [&](const Known& k) { return k.kernel == kernel && k.device == device; });
+    if (entry == known.end()) {
+        hipFuncAttributes attributes;
+        hipError_t status = hipFuncGetAttributes(&attributes, kernel);
         if (status != hipSuccess) {
             return status;
         }
-        for (const auto& known : facts->blocksPerCu) {
-            if (known.first.first == threads && known.first.second == ldsBytes) {
-                blocksPerCu = known.second;
+        KernelFacts facts;
+        facts.numRegs = attributes.numRegs;
+        // allocation granule 8 registers, 512 per lane per SIMD, 4 SIMDs, at most 8 wavefronts each
+        const int allocated = std::max(8, (attributes.numRegs + 7) / 8 * 8);
+        facts.registerWavesPerCu = 4u * static_cast<uint32_t>(std::min(8, 512 / allocated));
+        status = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (status != hipSuccess) {
+            return status;
+        }
+        entry = known.insert(known.end(), Known{kernel, device, facts, {}});
+    }
+    *out = entry->facts;
+    if (threads) {
+        for (const auto& blocks : entry->blocksPerCu) {
+            if (blocks.first.first == threads && blocks.first.second == ldsBytes) {
+                out->blocksPerCu = blocks.second;
             }
         }
-        if (!blocksPerCu) {
-            status = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocksPerCu, kernel, static_cast<int>(threads), ldsBytes);
+        if (!out->blocksPerCu) {
+            hipError_t status = hipOccupancyMaxActiveBlocksPerMultiprocessor(&out->blocksPerCu, kernel, static_cast<int>(threads), ldsBytes);
             if (status != hipSuccess) {
                 return status;
             }
-            blocksPerCu = std::max(blocksPerCu, 1);
-            facts->blocksPerCu.push_back({{threads, ldsBytes}, blocksPerCu});
+            out->blocksPerCu = std::max(out->blocksPerCu, 1);
+            entry->blocksPerCu.push_back({{threads, ldsBytes}, out->blocksPerCu});
         }
     }
-    // as many blocks as are resident at once; each wavefront strides over the tiles. (Round 5, batch 11: a grid cut down so
-    // that every wavefront gets the SAME number of tiles -- 12 500 tiles as 4 167 wavefronts x 3 instead of 5 120 wavefronts
-    // of which 44 % run a third round -- is slower: 100 000 uncached rows +10 % (4-bit), +15 % (6-bit, 2-bit). More wavefronts
-    // in flight beat an even last round.)
-    const uint32_t resident = static_cast<uint32_t>(blocksPerCu) * ctx->cuCount;
-    launch(std::min(tileBlocks, resident));
-    return hipGetLastError();
+    return hipSuccess;
 }
 
-hipError_t launchPersistent(
-    const memb_hip_ctx* ctx, TrainedKernel kernel, const TrainedParams& params, uint32_t tileBlocks, uint32_t threads,
-    uint32_t ldsBytes, hipStream_t stream)
+template <typename... A>
+hipError_t kernelFacts(void (*kernel)(A...), KernelFacts* out, uint32_t threads = 0, uint32_t ldsBytes = 0)
 {
-    return launchPersistentGeneric(
-        ctx, reinterpret_cast<const void*>(kernel), [&](uint32_t blocks) {
-            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), ldsBytes, stream, params);
-        }, tileBlocks, threads, ldsBytes);
+    return kernelFacts(reinterpret_cast<const void*>(kernel), out, threads, ldsBytes);
 }
 
-template <int MODE>
-hipError_t launchTrainedMode(
-    const memb_hip_ctx* ctx, const TrainedParams& params, uint32_t blocks, uint32_t threads, uint32_t ldsBytes, hipStream_t stream)
+// Enqueues kernel<<<grid, block, ldsBytes, stream>>>(args...) -- every kernel with dynamic LDS is launched here. The first
+// launch of a kernel on a device in a thread goes through kernelFacts, which raises its LDS limit; after that the check is
+// one lookup in this thread's own table, no lock: the latency of a single word is on this path.
+template <typename... A>
+hipError_t launchKernel(void (*kernel)(A...), dim3 grid, dim3 block, uint32_t ldsBytes, hipStream_t stream, A... args)
 {
-    if (ctx->fast) {
-        return launchTrainedVariant<false, MODE, true>(params, blocks, threads, ldsBytes, stream);
+    static thread_local std::unordered_map<void (*)(A...), int> configuredDevice;
+    if (!kernel) {
+        return hipErrorInvalidDeviceFunction;
     }
-    // (the index pass reads the 8-byte table, every other byte-key kernel the packed one)
-    const bool hasSub = MODE == OUT_INDEX ? ctx->hostTable.hasSubTables : ctx->byteTable.hasSubTables;
-    return hasSub ? launchTrainedVariant<true, MODE, false>(params, blocks, threads, ldsBytes, stream)
-                  : launchTrainedVariant<false, MODE, false>(params, blocks, threads, ldsBytes, stream);
+    int device = 0;
+    (void)hipGetDevice(&device);
+    int& configured = configuredDevice.try_emplace(kernel, -1).first->second;
+    if (configured != device) {
+        KernelFacts facts;
+        hipError_t status = kernelFacts(kernel, &facts);
+        if (status != hipSuccess) {
+            return status;
+        }
+        configured = device;
+    }
+    hipLaunchKernelGGL(kernel, grid, block, ldsBytes, stream, args...);
+    return hipGetLastError();
 }
 
 TrainedParams baseTrainedParams(const memb_hip_ctx* ctx)
@@ -646,7 +659,7 @@ struct TrainedPlan {
     bool fine = false;                   // decode_trained with the finer index (small batches)
     bool persistent = false;             // decode_records_persistent (else decode_trained)
     TrainedGeometry geometry{};
-    TrainedKernel kernel = nullptr;      // persistent only
+    const KernelInstance<TrainedParams>* kernel = nullptr;   // the instance that runs (lookupKernel)
     uint32_t registerWavesPerCu = 32;    // persistent only: what the kernel's registers allow
     int numRegs = 0;
 };
@@ -745,14 +758,17 @@ int planTrained(
     if (keysOut) {
         plan->geometry.mode = OUT_KEYS;
     }
+    plan->kernel = &lookupKernel(ctx, plan->persistent, plan->geometry.mode);
     if (plan->persistent && plan->geometry.waves) {
         // again with what the kernel's registers allow (a block size whose LDS would hold more wavefronts than
         // the registers admit is no better than a smaller one)
-        plan->kernel = recordsKernel(ctx, plan->geometry.mode);
-        hipError_t status = registerWavesPerCu(plan->kernel, &plan->registerWavesPerCu, &plan->numRegs);
+        KernelFacts facts;
+        hipError_t status = kernelFacts(plan->kernel->fn, &facts);
         if (status != hipSuccess) {
             return fail(MEMB_HIP_ERR_DEVICE, std::string("hipFuncGetAttributes: ") + hipGetErrorString(status));
         }
+        plan->registerWavesPerCu = facts.registerWavesPerCu;
+        plan->numRegs = facts.numRegs;
         const int mode = plan->geometry.mode;
         plan->geometry = chooseGeometry(ctx, wordsPerWave, ld, colOff, out, plan->registerWavesPerCu);
         plan->geometry.mode = mode;
@@ -778,7 +794,6 @@ int launchTrained(
     const uint32_t wordsPerWave = WAVE / (plan.fine ? ctx->fineLanes : ctx->lanesPerWord);
     const bool persistent = plan.persistent;
     TrainedGeometry geometry = plan.geometry;
-    TrainedKernel kernel = plan.kernel;
     if (!geometry.waves) {
         return fail(MEMB_HIP_ERR_INVALID, "decode tables and bitstream slots do not fit into LDS");
     }
@@ -797,33 +812,29 @@ int launchTrained(
     const uint32_t threads = geometry.waves * WAVE;
     hipError_t status;
     if (persistent) {
-        const uint32_t blocks = static_cast<uint32_t>((tiles + geometry.waves - 1) / geometry.waves);
-        status = launchPersistent(ctx, kernel, params, blocks, threads, geometry.ldsBytes, stream);
+        // as many blocks as are resident at once; each wavefront strides over the tiles. (Round 5, batch 11: a grid cut down so
+        // that every wavefront gets the SAME number of tiles -- 12 500 tiles as 4 167 wavefronts x 3 instead of 5 120 wavefronts
+        // of which 44 % run a third round -- is slower: 100 000 uncached rows +10 % (4-bit), +15 % (6-bit, 2-bit). More wavefronts
+        // in flight beat an even last round.)
+        const uint32_t tileBlocks = static_cast<uint32_t>((tiles + geometry.waves - 1) / geometry.waves);
+        KernelFacts facts;
+        status = kernelFacts(plan.kernel->fn, &facts, threads, geometry.ldsBytes);
+        if (status == hipSuccess) {
+            const uint32_t resident = static_cast<uint32_t>(facts.blocksPerCu) * ctx->cuCount;
+            status = launchKernel(plan.kernel->fn, dim3(std::min(tileBlocks, resident)), dim3(threads), geometry.ldsBytes, stream, params);
+        }
     } else {
         params.tilesPerWave = oneTileSteps(ctx, tiles, 4u * (params.tableDwords + params.codebookDwords), false);
         // very large batches leave word of their order for the next one (device-resident row ids only: the host-buffer
         // entry points stage slices of the caller's batch)
         const uint64_t R = uint64_t(ctx->cuCount) * PIPELINE_WAVES_PER_CU;
         if (tiles > 16 * R && !keysOut && rows && ctx->orderSeenDevice) {
-            params.segmentIndexOut = reinterpret_cast<uint16_t*>(ctx->orderSeenDevice);
+            params.orderOut = ctx->orderSeenDevice;
         }
         const size_t perBlock = size_t(geometry.waves) * params.tilesPerWave;
         const uint32_t blocks = static_cast<uint32_t>((tiles + perBlock - 1) / perBlock);
         const uint32_t ldsBytes = std::min<uint32_t>(geometry.ldsBytes + ctx->switches.ldsPad, 160 * 1024);   // (ldsPad: measurement builds)
-        switch (geometry.mode) {
-            case OUT_FLAT:
-                status = launchTrainedMode<OUT_FLAT>(ctx, params, blocks, threads, ldsBytes, stream);
-                break;
-            case OUT_VEC4:
-                status = launchTrainedMode<OUT_VEC4>(ctx, params, blocks, threads, ldsBytes, stream);
-                break;
-            case OUT_KEYS:
-                status = launchTrainedMode<OUT_KEYS>(ctx, params, blocks, threads, ldsBytes, stream);
-                break;
-            default:
-                status = launchTrainedMode<OUT_SCALAR>(ctx, params, blocks, threads, ldsBytes, stream);
-                break;
-        }
+        status = launchKernel(plan.kernel->fn, dim3(blocks), dim3(threads), ldsBytes, stream, params);
     }
     if (status != hipSuccess) {
         return fail(MEMB_HIP_ERR_DEVICE, std::string("decode_trained launch: ") + hipGetErrorString(status));
@@ -841,11 +852,8 @@ int launchTrainedBatches(memb_hip_ctx* ctx, const memb_hip_batch* batches, size_
     for (size_t k = 0; k < count; ++k) {
         const memb_hip_batch& batch = batches[k];
         words += batch.n;
-        const bool vec = (ctx->dim % 4 == 0) && (batch.ld % 4 == 0) && (batch.col_off % 4 == 0) &&
-            (reinterpret_cast<uintptr_t>(batch.out) % 16 == 0);
-        const int batchMode = !vec ? OUT_SCALAR : (batch.ld == ctx->dim && batch.col_off == 0) ? OUT_FLAT : OUT_VEC4;
         // one output mode for the launch: the most general one any batch needs (OUT_SCALAR < OUT_VEC4 < OUT_FLAT)
-        mode = std::min(mode, batchMode);
+        mode = std::min(mode, outputMode(ctx->dim, batch.ld, batch.col_off, batch.out));
     }
     // (the finer index as for one batch of as many words: a serving loop's handful of small lookups is a small batch)
     TrainedPlan plan;
@@ -883,49 +891,13 @@ int launchTrainedBatches(memb_hip_ctx* ctx, const memb_hip_batch* batches, size_
     if (blocks >= 0x7FFFFFFFull) {
         return fail(MEMB_HIP_ERR_INVALID, "batches too large for one launch");
     }
-    const uint32_t threads = geometry.waves * WAVE;
-    hipError_t status;
-    switch (mode) {
-        case OUT_FLAT:
-            status = launchBatchesMode<OUT_FLAT>(ctx, params, list, static_cast<uint32_t>(blocks), threads, geometry.ldsBytes, stream);
-            break;
-        case OUT_VEC4:
-            status = launchBatchesMode<OUT_VEC4>(ctx, params, list, static_cast<uint32_t>(blocks), threads, geometry.ldsBytes, stream);
-            break;
-        default:
-            status = launchBatchesMode<OUT_SCALAR>(ctx, params, list, static_cast<uint32_t>(blocks), threads, geometry.ldsBytes, stream);
-            break;
-    }
+    const hipError_t status = launchKernel(
+        kernelTable().batches[lookupHasSub(ctx)][mode][ctx->fast].fn, dim3(static_cast<uint32_t>(blocks)), dim3(geometry.waves * WAVE),
+        geometry.ldsBytes, stream, params, list);
     if (status != hipSuccess) {
         return fail(MEMB_HIP_ERR_DEVICE, std::string("decode_trained_batches launch: ") + hipGetErrorString(status));
     }
     return MEMB_HIP_OK;
-}
-
-typedef void (*UnionKernel)(UnionParams);
-
-template <bool HAS_SUB, bool FAST, bool AVERAGE>
-UnionKernel unionKernelOf(size_t count)
-{
-    switch (count) {
-        case 2:
-            return &decode_trained_union<HAS_SUB, FAST, 2, AVERAGE>;
-        case 3:
-            return &decode_trained_union<HAS_SUB, FAST, 3, AVERAGE>;
-        default:
-            return &decode_trained_union<HAS_SUB, FAST, 4, AVERAGE>;
-    }
-}
-
-UnionKernel unionKernel(bool hasSub, bool fast, bool average, size_t count)
-{
-    if (fast) {
-        return average ? unionKernelOf<false, true, true>(count) : unionKernelOf<false, true, false>(count);
-    }
-    if (hasSub) {
-        return average ? unionKernelOf<true, false, true>(count) : unionKernelOf<true, false, false>(count);
-    }
-    return average ? unionKernelOf<false, false, true>(count) : unionKernelOf<false, false, false>(count);
 }
 
 // See memb_hip_decode_rows_union_device. MEMB_HIP_UNSUPPORTED when the models cannot share the kernel.
@@ -1021,9 +993,12 @@ int launchTrainedUnion(
     };
 
     // waves per block: most resident wavefronts per CU -- by LDS and by the kernel's registers --, blocks of
-    // four on ties (as chooseGeometry)
-    auto chooseWaves = [&](uint32_t sharedDwords, uint32_t perWaveDwords, uint32_t registerWaves, uint32_t* waves, uint32_t* ldsBytes) {
-        double bestResident = -1;
+    // four on ties (as chooseGeometry); 0 when no block size fits
+    auto chooseWaves = [&](const KernelInstance<UnionParams>& kernel, uint32_t sharedDwords, uint32_t perWaveDwords,
+                           uint32_t* waves, uint32_t* ldsBytes) -> hipError_t {
+        KernelFacts facts;
+        const hipError_t status = kernelFacts(kernel.fn, &facts);
+        uint32_t bestResident = 0;
         *waves = 0;
         // (a forced block size -- option waves_per_block, 1 .. 16 -- is the only candidate, as in chooseGeometry)
         const uint32_t forced = first->switches.waves;
@@ -1032,23 +1007,17 @@ int launchTrainedUnion(
                 continue;
             }
             const uint32_t bytes = 4u * (sharedDwords + candidate * perWaveDwords);
-            if (bytes > first->ldsLimit) {
-                continue;
-            }
-            const uint32_t blocksPerCu = std::min<uint32_t>(
-                first->ldsLimit / ((bytes + 1023) / 1024 * 1024), std::max<uint32_t>(1, std::min<uint32_t>(32, registerWaves) / candidate));
-            if (double(blocksPerCu) * candidate > bestResident) {
-                bestResident = double(blocksPerCu) * candidate;
+            const uint32_t resident = residentWaves(first->ldsLimit, candidate, bytes, facts.registerWavesPerCu);
+            if (resident > bestResident) {
+                bestResident = resident;
                 *waves = candidate;
                 *ldsBytes = bytes;
             }
         }
+        return status;
     };
     uint32_t waves = 0;
     uint32_t ldsBytes = 0;
-    UnionKernel kernel = nullptr;
-    uint32_t registerWaves = 32;
-    int numRegs = 0;
 
     // decode_union_split: two models staged as row records -- the wavefront's word slots are divided
     // between the models, a tile is half as many words, LDS per wavefront as in the single-model kernel.
@@ -1090,15 +1059,11 @@ int launchTrainedUnion(
         sp.keyTileOffsetDwords[0] = roundUp4(wordsPerWave * ctxs[larger]->slotDwords);
         sp.keyTileOffsetDwords[1] = sp.keyTileOffsetDwords[0] + half * sp.model[0].keyRowBytes / 4;
         sp.perWaveDwords = sp.keyTileOffsetDwords[0] + roundUp4(sp.model[0].keyTileDwords);
-        kernel = compact ? (average ? &decode_union_split<false, true, true, true> : &decode_union_split<false, true, false, true>)
-            : allFast ? (average ? &decode_union_split<false, true, true> : &decode_union_split<false, true, false>)
-            : packedSub ? (average ? &decode_union_split<true, false, true> : &decode_union_split<true, false, false>)
-                        : (average ? &decode_union_split<false, false, true> : &decode_union_split<false, false, false>);
-        hipError_t status = registerWavesPerCu(reinterpret_cast<TrainedKernel>(kernel), &registerWaves, &numRegs);
+        const KernelInstance<UnionParams>& kernel = kernelTable().split[packedSub][allFast][average][compact];
+        hipError_t status = chooseWaves(kernel, shared, sp.perWaveDwords, &waves, &ldsBytes);
         if (status != hipSuccess) {
             return fail(MEMB_HIP_ERR_DEVICE, std::string("hipFuncGetAttributes: ") + hipGetErrorString(status));
         }
-        chooseWaves(shared, sp.perWaveDwords, registerWaves, &waves, &ldsBytes);
         if (waves && (n + half - 1) / half / waves >= 0x7FFFFFFFull) {
             waves = 0;   // (more blocks than a grid holds: the forms below have tiles twice as large)
         }
@@ -1106,52 +1071,31 @@ int launchTrainedUnion(
             const size_t splitTiles = (n + half - 1) / half;
             sp.model[2].tilesPerWave = oneTileSteps(first, splitTiles, 4u * shared, true);
             const size_t perBlock = size_t(waves) * sp.model[2].tilesPerWave;
-            {
-                std::lock_guard<std::mutex> lock(g_kernelFactsMutex);   // (raises the kernel's LDS limit on first use)
-                KernelFacts* facts = nullptr;
-                status = kernelFactsLocked(reinterpret_cast<const void*>(kernel), &facts);
-            }
-            if (status == hipSuccess) {
-                hipLaunchKernelGGL(kernel, dim3(static_cast<uint32_t>((splitTiles + perBlock - 1) / perBlock)), dim3(waves * WAVE), ldsBytes, stream, sp);
-                status = hipGetLastError();
-            }
+            status = launchKernel(
+                kernel.fn, dim3(static_cast<uint32_t>((splitTiles + perBlock - 1) / perBlock)), dim3(waves * WAVE), ldsBytes, stream, sp);
             if (status != hipSuccess) {
                 return fail(MEMB_HIP_ERR_DEVICE, std::string("decode_union_split launch: ") + hipGetErrorString(status));
             }
-            std::snprintf(ctxs[0]->unionKernel, sizeof(ctxs[0]->unionKernel), "decode_union_split<%s, %s, %s, %s>",
-                          packedSub ? "true" : "false", allFast ? "true" : "false", average ? "true" : "false", compact ? "true" : "false");
+            ctxs[0]->unionKernel = kernel.name.c_str();
             return MEMB_HIP_OK;
         }
         // (does not fit: the forms below lay their areas out afresh)
-        registerWaves = 32;
     }
     // decode_trained_union, one tile per wavefront: three or four models, pairs without row records
     layOut();
-    kernel = unionKernel(hasSub, allFast, average, count);
-    hipError_t status = registerWavesPerCu(reinterpret_cast<TrainedKernel>(kernel), &registerWaves, &numRegs);
+    const KernelInstance<UnionParams>& kernel = kernelTable().unions[hasSub && !allFast][allFast][count][average];
+    hipError_t status = chooseWaves(kernel, sharedDwords, params.perWaveDwords, &waves, &ldsBytes);
     if (status != hipSuccess) {
         return fail(MEMB_HIP_ERR_DEVICE, std::string("hipFuncGetAttributes: ") + hipGetErrorString(status));
     }
-    chooseWaves(sharedDwords, params.perWaveDwords, registerWaves, &waves, &ldsBytes);
     if (!waves) {
         return fail(MEMB_HIP_UNSUPPORTED, "union kernel: tables and bitstream slots of the models do not fit into LDS together");
     }
-    const uint32_t threads = waves * WAVE;
-    const uint32_t tileBlocks = static_cast<uint32_t>((tiles + waves - 1) / waves);
-    {
-        std::lock_guard<std::mutex> lock(g_kernelFactsMutex);   // (raises the kernel's LDS limit on first use)
-        KernelFacts* facts = nullptr;
-        status = kernelFactsLocked(reinterpret_cast<const void*>(kernel), &facts);
-    }
-    if (status == hipSuccess) {
-        hipLaunchKernelGGL(kernel, dim3(tileBlocks), dim3(threads), ldsBytes, stream, params);
-        status = hipGetLastError();
-    }
+    status = launchKernel(kernel.fn, dim3(static_cast<uint32_t>((tiles + waves - 1) / waves)), dim3(waves * WAVE), ldsBytes, stream, params);
     if (status != hipSuccess) {
         return fail(MEMB_HIP_ERR_DEVICE, std::string("decode_trained_union launch: ") + hipGetErrorString(status));
     }
-    std::snprintf(ctxs[0]->unionKernel, sizeof(ctxs[0]->unionKernel), "decode_trained_union<%s, %s, %zu, %s>",
-                  hasSub ? "true" : "false", allFast ? "true" : "false", count, average ? "true" : "false");
+    ctxs[0]->unionKernel = kernel.name.c_str();
     return MEMB_HIP_OK;
 }
 
@@ -1194,7 +1138,9 @@ int buildSegmentIndex(memb_hip_ctx* ctx, uint32_t lanes, uint32_t symbols, uint1
     params.wordsPerWave = wordsPerWave;
     const size_t tiles = (ctx->nRows + wordsPerWave - 1) / wordsPerWave;
     const uint32_t blocks = static_cast<uint32_t>((tiles + waves - 1) / waves);
-    hipError_t status = launchTrainedMode<OUT_INDEX>(ctx, params, blocks, waves * WAVE, ldsBytes, ctx->stream);
+    // (the index pass reads the 8-byte table)
+    const KernelInstance<TrainedParams>& kernel = kernelTable().trained[ctx->hostTable.hasSubTables && !ctx->fast][OUT_INDEX][ctx->fast];
+    hipError_t status = launchKernel(kernel.fn, dim3(blocks), dim3(waves * WAVE), ldsBytes, ctx->stream, params);
     if (status == hipSuccess) {
         status = hipStreamSynchronize(ctx->stream);
     }
@@ -1225,8 +1171,7 @@ struct UniformTilePlan {
 UniformTilePlan planUniform(const memb_hip_ctx* ctx, size_t ld, size_t colOff, const float* out)
 {
     UniformTilePlan plan;
-    const bool vec = (ctx->dim % 4 == 0) && (ld % 4 == 0) && (colOff % 4 == 0) &&
-        (reinterpret_cast<uintptr_t>(out) % 16 == 0);
+    const bool vec = outputMode(ctx->dim, ld, colOff, out) != OUT_SCALAR;
     plan.tileWords = std::max<uint32_t>(1, std::min<uint32_t>(WAVE, (9600 + ctx->dim * 4 - 1) / (ctx->dim * 4)));
     plan.waves = 4;
     while (plan.waves > 1 && uint64_t(plan.waves) * plan.tileWords * ctx->regionPieces * 16 > ctx->ldsLimit) {
@@ -1255,8 +1200,7 @@ int launchUniform(
     params.dim = ctx->dim;
     params.wordsPerBlock = rowwiseWordsPerBlock(ctx->dim);
     params.levels = ctx->levels;
-    const bool vec = (ctx->dim % 4 == 0) && (ld % 4 == 0) && (colOff % 4 == 0) &&
-        (reinterpret_cast<uintptr_t>(out) % 16 == 0);
+    const bool vec = outputMode(ctx->dim, ld, colOff, out) != OUT_SCALAR;
     const UniformTilePlan tilePlan = planUniform(ctx, ld, colOff, out);
     const uint32_t tileWords = tilePlan.tileWords;
     const uint32_t waves = tilePlan.waves;
@@ -1267,17 +1211,9 @@ int launchUniform(
         const uint32_t ldsBytes = waves * tileWords * ctx->regionPieces * 16;
         const uint64_t tiles = (n + tileWords - 1) / tileWords;
         const bool flat = ld == ctx->dim && colOff == 0;
-        void (*kernel)(UniformParams) = flat ? &dequant_uniform_tile<true> : &dequant_uniform_tile<false>;
-        hipError_t status;
-        {
-            std::lock_guard<std::mutex> lock(g_kernelFactsMutex);   // (raises the kernel's LDS limit on first use)
-            KernelFacts* facts = nullptr;
-            status = kernelFactsLocked(reinterpret_cast<const void*>(kernel), &facts);
-        }
-        if (status == hipSuccess) {
-            hipLaunchKernelGGL(kernel, dim3(static_cast<uint32_t>((tiles + waves - 1) / waves)), dim3(waves * WAVE), ldsBytes, stream, params);
-            status = hipGetLastError();
-        }
+        const hipError_t status = launchKernel(
+            flat ? &dequant_uniform_tile<true> : &dequant_uniform_tile<false>, dim3(static_cast<uint32_t>((tiles + waves - 1) / waves)),
+            dim3(waves * WAVE), ldsBytes, stream, params);
         if (status != hipSuccess) {
             return fail(MEMB_HIP_ERR_DEVICE, std::string("dequant_uniform_tile launch: ") + hipGetErrorString(status));
         }
@@ -1313,8 +1249,7 @@ int launchFull(
     params.nRows = ctx->nRows;
     params.dim = ctx->dim;
     params.wordsPerBlock = rowwiseWordsPerBlock(ctx->dim);
-    const bool vec = (ctx->dim % 4 == 0) && (ld % 4 == 0) && (colOff % 4 == 0) &&
-        (reinterpret_cast<uintptr_t>(out) % 16 == 0);
+    const bool vec = outputMode(ctx->dim, ld, colOff, out) != OUT_SCALAR;
     const uint32_t blocks = static_cast<uint32_t>((n + params.wordsPerBlock - 1) / params.wordsPerBlock);
     if (vec) {
         params.pieceMagic = magicFor(ctx->dim / 4, uint64_t(params.wordsPerBlock) * (ctx->dim / 4));
@@ -2253,12 +2188,8 @@ int fillInfo(const memb_hip_ctx* ctx, memb_hip_ctx_info* info, uint64_t batchWor
         info->lds_bytes_per_block = geometry.ldsBytes;
         info->row_layout = ctx->recordPieces ? 2u : (ctx->rowMeta ? 1u : 0u);
         info->row_bytes = ctx->recordPieces * 16;
-        // template arguments as in the symbol: <two-level table, output mode (2 = dense rows), nibble keys, ...>
-        std::snprintf(
-            info->kernel, sizeof(info->kernel), "%s<%s, %d, %s>",
-            plan.persistent ? "decode_records_persistent" : "decode_trained",
-            (ctx->fast ? ctx->hostTable : ctx->byteTable).hasSubTables ? "true" : "false", static_cast<int>(OUT_FLAT),
-            ctx->fast ? "true" : "false");
+        // (the instance of dense fp32 rows, output mode 2)
+        std::snprintf(info->kernel, sizeof(info->kernel), "%s", lookupKernel(ctx, plan.persistent, OUT_FLAT).name.c_str());
         if (!plan.persistent) {
             const uint32_t wordsPerWave = WAVE / info->lanes_per_word;
             const uint64_t words = batchWords ? batchWords : uint64_t(1) << 30;
