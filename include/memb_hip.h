@@ -117,8 +117,12 @@ typedef struct memb_hip_full_desc {
  * (memb_hip_decode_batches_device); memb_hip_ctx_info is back on its ABI-3 offsets -- two reserved dwords follow
  * tiles_per_wavefront, where ABI 3 had the rest of its large_batch_* fields -- and grew at the END only (word_index_*);
  * memb_hip_ctx_get_info refuses the struct_size of the ABI-4 declaration, whose union_kernel sat 8 bytes lower.
+ * Round 6, still under 5: the options "pipeline_tiles" and "union_compact" were removed (memb_hip_ctx_set_option refuses
+ * them), and so were the environment switches MEMB_HIP_PERSISTENT, _UNION_FUSED, _HOST_EXPAND, _FINE_LANES,
+ * _TILES_PER_WAVE, _UNION_SPLIT and _UNION_COMPACT; MEMB_HIP_ROWS_IN_RANDOM_ORDER changed meaning.
+ * 6 = memb_hip_resolve_packed_device_bounded (device-resident words checked against the extent of their byte buffer).
  */
-#define MEMB_HIP_ABI_VERSION 5
+#define MEMB_HIP_ABI_VERSION 6
 int memb_hip_abi_version(void);
 
 /*
@@ -336,7 +340,8 @@ int memb_hip_ctx_stage_words(
  *             job_words: lookups of finished jobs overlap the filling of later ones). Enqueued on `stream`, returns
  *             without waiting. The rows never visit the host: hand rows_dev to memb_hip_decode_rows_device.
  * The pinned buffers must stay untouched until the lookups that read them have run (begin waits for them; destroy too).
- * Not thread-safe: one batch in the making per object.
+ * Not thread-safe: one batch in the making per object. (In the Python package a memb_amd.Reader or ReadersUnion may be
+ * shared between threads -- no two calls in flight ever share a batch -- but a memb_amd._memb.WordBatch may not.)
  */
 typedef struct memb_hip_words memb_hip_words;
 typedef struct memb_hip_words_plan {
@@ -376,9 +381,16 @@ int memb_hip_decode_words(memb_hip_ctx* ctx, const memb_hip_words* batch, float*
 /*
  * The same lookup for callers whose words are on the device already: word i = bytes_dev[offsets_dev[i] ..
  * offsets_dev[i + 1]) (n + 1 offsets, ascending; no NUL inside a word).
+ *   _bounded   bytes_dev holds bytes_len bytes: a word whose offsets run backwards or reach past bytes_len is
+ *              MEMB_HIP_MISSING_ROW, and its bytes are not read; every other word keeps its answer (ABI 6).
+ *   unbounded  the extent of bytes_dev is not known: offsets are taken at their word, and offsets that leave the
+ *              buffer are read wherever they point. Kept for existing callers; prefer _bounded.
  */
 int memb_hip_resolve_packed_device(
     memb_hip_ctx* ctx, const uint8_t* bytes_dev, const uint32_t* offsets_dev, size_t n, uint32_t* rows_dev, void* stream);
+int memb_hip_resolve_packed_device_bounded(
+    memb_hip_ctx* ctx, const uint8_t* bytes_dev, size_t bytes_len, const uint32_t* offsets_dev, size_t n, uint32_t* rows_dev,
+    void* stream);
 
 /* Wait for the context's own stream (used by memb_hip_decode_rows). */
 int memb_hip_sync(memb_hip_ctx* ctx);

@@ -86,6 +86,45 @@ struct WordPointers {
     const char* const* data() const { return pointers.data(); }
 };
 
+// Every binding that fills or looks up through a WordBatch holds its claim for the whole call: a batch shared by two calls
+// in flight (one's begin would reset, even free, what the other's threads and lookups still use) is a RuntimeError.
+// Taken while the GIL is held and never waited for.
+struct BatchClaim {
+    memb::WordBatch& batch;
+
+    explicit BatchClaim(memb::WordBatch& claimed): batch(claimed)
+    {
+        if (!batch.tryClaim()) {
+            throw std::runtime_error("word batch is in use by another call");
+        }
+    }
+    ~BatchClaim() { batch.releaseClaim(); }
+    BatchClaim(const BatchClaim&) = delete;
+    BatchClaim& operator=(const BatchClaim&) = delete;
+};
+
+// packed_to_rows_device / _packed_fill_seconds: one buffer of bytes and n + 1 uint32 offsets, as plain memory
+struct PackedWords {
+    const uint8_t* data;
+    size_t dataBytes;
+    const uint32_t* offsets;
+    size_t count;
+};
+
+PackedWords packedWords(const py::buffer_info& blob, const py::array& offsets)
+{
+    if (blob.ndim != 1 || blob.itemsize != 1 || (blob.size > 1 && blob.strides[0] != 1)) {
+        throw py::type_error("bytes must be a contiguous one-dimensional buffer of bytes");
+    }
+    if (!py::isinstance<py::array_t<uint32_t>>(offsets) || offsets.ndim() != 1 || offsets.shape(0) < 1 ||
+        !(offsets.flags() & py::array::c_style)) {
+        throw py::type_error("offsets must be a contiguous numpy.uint32 array of n + 1 entries");
+    }
+    return PackedWords{
+        static_cast<const uint8_t*>(blob.ptr), static_cast<size_t>(blob.size), static_cast<const uint32_t*>(offsets.data()),
+        static_cast<size_t>(offsets.shape(0)) - 1};
+}
+
 // A list of str into a word batch on the device (memb::WordBatch, include/memb_hip.h: memb_hip_words_plan) -- the part
 // of a device word search that is host work, and at 2.2 M words the longest part of a lookup, so every word is touched
 // ONCE: pooled threads read the str objects and write their UTF-8 bytes (up to the first NUL, where the reference's
@@ -240,22 +279,33 @@ struct WordFiller {
         }
     }
 
+    // expected: the number of words the caller has room for (rows it writes); a list whose size differs from it when the
+    // words are read is refused. SIZE_MAX: any size.
     template <typename OnChunk>
-    static size_t fill(memb::WordBatch& batch, const py::handle& words, OnChunk onChunk)
+    static size_t fill(memb::WordBatch& batch, const py::handle& words, OnChunk onChunk, size_t expected = SIZE_MAX)
     {
         py::object fast = py::reinterpret_steal<py::object>(PySequence_Fast(words.ptr(), "expected a list of str"));
         if (!fast) {
             throw py::error_already_set();
         }
-        const size_t count = static_cast<size_t>(PySequence_Fast_GET_SIZE(fast.ptr()));
-        PyObject** items = PySequence_Fast_ITEMS(fast.ptr());
         size_t bytesPerWord = 0;
         for (int attempt = 0; attempt < 48; ++attempt) {
+            size_t count = static_cast<size_t>(PySequence_Fast_GET_SIZE(fast.ptr()));
             memb_hip_words_plan plan;
             {
                 py::gil_scoped_release release;   // (begin waits for the lookups that still read the previous batch)
                 plan = batch.begin(count, bytesPerWord);
             }
+            // Other Python threads ran while the GIL was released: a list may have been resized meanwhile (its item array
+            // moved, its size changed). Read both again; a batch begun for another size starts over.
+            const size_t now = static_cast<size_t>(PySequence_Fast_GET_SIZE(fast.ptr()));
+            if (expected != SIZE_MAX && now != expected) {
+                throw std::runtime_error("the list of words changed size during the call");
+            }
+            if (now != count) {
+                continue;
+            }
+            PyObject** items = PySequence_Fast_ITEMS(fast.ptr());
             std::vector<int> state(plan.jobs, FILLED);
             std::vector<uint64_t> needed(plan.jobs, 0);
             if (count == 0) {
@@ -603,6 +653,7 @@ PYBIND11_MODULE(_memb, m) {
         .def(
             "pack",
             [](memb::WordBatch& batch, const py::sequence& wordList) {
+                BatchClaim claim(batch);
                 return WordFiller::fill(batch, wordList, [](size_t, size_t) {});
             },
             py::arg("words"),
@@ -701,6 +752,7 @@ PYBIND11_MODULE(_memb, m) {
         .def(
             "resolve_batch_to_device",
             [](memb::Reader& reader, memb::WordBatch& batch, uintptr_t rows, uintptr_t stream) {
+                BatchClaim claim(batch);
                 py::gil_scoped_release release;   // (may stage the keys on first use)
                 reader.resolveRowsToDevice(batch, reinterpret_cast<uint32_t*>(rows), reinterpret_cast<void*>(stream));
             },
@@ -711,16 +763,18 @@ PYBIND11_MODULE(_memb, m) {
         .def(
             "words_to_rows_device",
             [](memb::Reader& reader, memb::WordBatch& batch, const py::sequence& wordList, uintptr_t rows, uintptr_t stream) {
-                // fill + lookup under one hold of the GIL (the batch object is not shared between two calls in flight);
-                // the lookups of finished runs of jobs are enqueued while the pool fills the next. Staging the keys (first
-                // call only: tens of MB to HBM, the hash table built, a synchronize) runs with the GIL released.
+                // fill + lookup under the batch's claim (no second call shares the batch meanwhile); the lookups of finished
+                // runs of jobs are enqueued while the pool fills the next. Staging the keys (first call only: tens of MB to
+                // HBM, the hash table built, a synchronize) runs with the GIL released.
+                BatchClaim claim(batch);
+                const size_t count = static_cast<size_t>(py::len(wordList));   // (the rows at rows_ptr)
                 {
                     py::gil_scoped_release release;
                     reader.stageWords();
                 }
                 return WordFiller::fill(batch, wordList, [&](size_t firstWord, size_t words) {
                     reader.resolveRangeToDevice(batch, firstWord, words, reinterpret_cast<uint32_t*>(rows), reinterpret_cast<void*>(stream));
-                });
+                }, count);
             },
             py::arg("batch"),
             py::arg("words"),
@@ -731,20 +785,11 @@ PYBIND11_MODULE(_memb, m) {
             "packed_to_rows_device",
             [](memb::Reader& reader, memb::WordBatch& batch, const py::buffer& bytes, const py::array& offsets, uintptr_t rows, uintptr_t stream) {
                 const py::buffer_info blob = bytes.request();
-                if (blob.ndim != 1 || blob.itemsize != 1 || (blob.size > 1 && blob.strides[0] != 1)) {
-                    throw py::type_error("bytes must be a contiguous one-dimensional buffer of bytes");
-                }
-                if (!py::isinstance<py::array_t<uint32_t>>(offsets) || offsets.ndim() != 1 || offsets.shape(0) < 1 ||
-                    !(offsets.flags() & py::array::c_style)) {
-                    throw py::type_error("offsets must be a contiguous numpy.uint32 array of n + 1 entries");
-                }
-                const size_t count = static_cast<size_t>(offsets.shape(0)) - 1;
-                const uint32_t* starts = static_cast<const uint32_t*>(offsets.data());
-                const uint8_t* data = static_cast<const uint8_t*>(blob.ptr);
-                const size_t dataBytes = static_cast<size_t>(blob.size);
+                const PackedWords packed = packedWords(blob, offsets);
+                BatchClaim claim(batch);
                 py::gil_scoped_release release;   // (plain memory from here on: the views above keep it alive)
                 reader.stageWords();
-                return PackedFiller::fill(batch, data, dataBytes, starts, count, [&](size_t firstWord, size_t words) {
+                return PackedFiller::fill(batch, packed.data, packed.dataBytes, packed.offsets, packed.count, [&](size_t firstWord, size_t words) {
                     reader.resolveRangeToDevice(batch, firstWord, words, reinterpret_cast<uint32_t*>(rows), reinterpret_cast<void*>(stream));
                 });
             },
@@ -756,21 +801,23 @@ PYBIND11_MODULE(_memb, m) {
             "words packed as one buffer of UTF-8 bytes + n + 1 ascending uint32 offsets -> row ids in device memory")
         .def(
             "packed_device_to_rows_device",
-            [](memb::Reader& reader, uintptr_t bytes, uintptr_t offsets, size_t count, uintptr_t rows, uintptr_t stream) {
+            [](memb::Reader& reader, uintptr_t bytes, size_t bytesLen, uintptr_t offsets, size_t count, uintptr_t rows, uintptr_t stream) {
                 py::gil_scoped_release release;
                 reader.stageWords();
-                if (memb_hip_resolve_packed_device(
-                        reader.deviceContext(), reinterpret_cast<const uint8_t*>(bytes), reinterpret_cast<const uint32_t*>(offsets), count,
-                        reinterpret_cast<uint32_t*>(rows), reinterpret_cast<void*>(stream)) != MEMB_HIP_OK) {
+                if (memb_hip_resolve_packed_device_bounded(
+                        reader.deviceContext(), reinterpret_cast<const uint8_t*>(bytes), bytesLen, reinterpret_cast<const uint32_t*>(offsets),
+                        count, reinterpret_cast<uint32_t*>(rows), reinterpret_cast<void*>(stream)) != MEMB_HIP_OK) {
                     throw std::runtime_error(std::string("HIP word search failed: ") + memb_hip_last_error());
                 }
             },
             py::arg("bytes_ptr"),
+            py::arg("bytes_len"),
             py::arg("offsets_ptr"),
             py::arg("n"),
             py::arg("rows_ptr"),
             py::arg("stream") = 0,
-            "the same for bytes and offsets that are in device memory already (memb_hip_resolve_packed_device)")
+            "the same for bytes (bytes_len of them) and offsets that are in device memory already: a word whose offsets run "
+            "backwards or reach past bytes_len is not in the model (memb_hip_resolve_packed_device_bounded)")
         .def(
             "batch_embedding_into",
             [](memb::Reader& reader,
@@ -946,6 +993,8 @@ PYBIND11_MODULE(_memb, m) {
             if (readers.size() != rows.size()) {
                 throw std::runtime_error("One row-id array per reader is needed");
             }
+            BatchClaim claim(batch);
+            const size_t count = static_cast<size_t>(py::len(wordList));   // (the rows at every rows_ptrs entry)
             std::vector<const memb::Reader*> models;
             std::vector<uint32_t*> targets;
             for (size_t i = 0; i < readers.size(); ++i) {
@@ -959,7 +1008,7 @@ PYBIND11_MODULE(_memb, m) {
             // one launch per finished run of jobs: every word fetched and hashed once, probed in each reader's table
             return WordFiller::fill(batch, wordList, [&](size_t firstWord, size_t words) {
                 memb::Reader::resolveRangeToDevice(models, batch, firstWord, words, targets, reinterpret_cast<void*>(stream));
-            });
+            }, count);
         },
         py::arg("batch"),
         py::arg("words"),
@@ -969,19 +1018,18 @@ PYBIND11_MODULE(_memb, m) {
     // measurement hook (bench.py's word_search block, tools/perf): seconds the calling thread and the pool spend
     // writing a list of str into a word batch's pinned memory -- the host work of a device word search
     m.def("_word_fill_seconds", [](memb::WordBatch& batch, const py::sequence& wordList) {
+        BatchClaim claim(batch);
         const auto start = std::chrono::steady_clock::now();
         WordFiller::fill(batch, wordList, [](size_t, size_t) {});
         return std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
     });
-    m.def("_packed_fill_seconds", [](memb::WordBatch& batch, const py::buffer& bytes, const py::array_t<uint32_t, py::array::c_style>& offsets) {
+    m.def("_packed_fill_seconds", [](memb::WordBatch& batch, const py::buffer& bytes, const py::array& offsets) {
         const py::buffer_info blob = bytes.request();
-        const size_t count = static_cast<size_t>(offsets.shape(0)) - 1;
-        const uint32_t* starts = offsets.data();
-        const uint8_t* data = static_cast<const uint8_t*>(blob.ptr);
-        const size_t dataBytes = static_cast<size_t>(blob.size);
+        const PackedWords packed = packedWords(blob, offsets);
+        BatchClaim claim(batch);
         py::gil_scoped_release release;
         const auto start = std::chrono::steady_clock::now();
-        PackedFiller::fill(batch, data, dataBytes, starts, count, [](size_t, size_t) {});
+        PackedFiller::fill(batch, packed.data, packed.dataBytes, packed.offsets, packed.count, [](size_t, size_t) {});
         return std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
     });
     m.attr("HOST_DEVICE") = static_cast<int>(memb::CompressedStorage::HOST_DEVICE);

@@ -499,16 +499,18 @@ size_t wordBatchCount(const memb_hip_words* batch)
     return batch->committed ? batch->count : 0;
 }
 
+// totalBytes: the extent of the caller's byte buffer -- a word whose offsets run backwards or reach past it is MISSING
+// (memb_hip_resolve_packed_device_bounded). The unbounded entry point passes 0xFFFFFFFF: the offsets are taken at their word.
 int resolve_packed_device_checked(
-    memb_hip_ctx* ctx, const uint8_t* bytes, const uint32_t* offsets, size_t n, uint32_t* rows, hipStream_t stream)
+    memb_hip_ctx* ctx, const uint8_t* bytes, uint64_t totalBytes, const uint32_t* offsets, size_t n, uint32_t* rows,
+    hipStream_t stream)
 {
-    if (!ctx || (n && (!offsets || !rows))) {
+    if (!ctx || (n && (!offsets || !rows || (totalBytes && !bytes)))) {
         return fail(MEMB_HIP_ERR_INVALID, "null argument");
     }
     DeviceScope deviceScope(ctx->device);
     HIP_TRY(deviceScope.status());
-    // (the extent of the caller's byte buffer is not known here: the offsets are taken at their word)
-    return launchResolve(ctx, bytes, 0xFFFFFFFFull, offsets, 0, 0, n, rows, stream);
+    return launchResolve(ctx, bytes, totalBytes, offsets, 0, 0, n, rows, stream);
 }
 
 }  // namespace

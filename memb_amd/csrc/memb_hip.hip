@@ -2721,7 +2721,18 @@ int memb_hip_resolve_range_union_device(
 int memb_hip_resolve_packed_device(
     memb_hip_ctx* ctx, const uint8_t* bytes_dev, const uint32_t* offsets_dev, size_t n, uint32_t* rows_dev, void* stream)
 {
-    return guarded([&] { return resolve_packed_device_checked(ctx, bytes_dev, offsets_dev, n, rows_dev, static_cast<hipStream_t>(stream)); });
+    return guarded([&] {
+        return resolve_packed_device_checked(ctx, bytes_dev, 0xFFFFFFFFull, offsets_dev, n, rows_dev, static_cast<hipStream_t>(stream));
+    });
+}
+
+int memb_hip_resolve_packed_device_bounded(
+    memb_hip_ctx* ctx, const uint8_t* bytes_dev, size_t bytes_len, const uint32_t* offsets_dev, size_t n, uint32_t* rows_dev,
+    void* stream)
+{
+    return guarded([&] {
+        return resolve_packed_device_checked(ctx, bytes_dev, bytes_len, offsets_dev, n, rows_dev, static_cast<hipStream_t>(stream));
+    });
 }
 
 int memb_hip_algorithmic_bytes(const memb_hip_ctx* ctx, const uint32_t* rows, size_t n, uint64_t* bytes)

@@ -51,9 +51,15 @@ public:
     int device() const { return device_; }
     const memb_hip_words* handle() const { return handle_; }
 
+    // Held for the length of one call that fills or looks up through the batch (the Python bindings): the underlying
+    // memb_hip_words takes one caller at a time, so a second call finds the claim taken and fails instead of waiting.
+    bool tryClaim() { return !claimed_.exchange(true, std::memory_order_acquire); }
+    void releaseClaim() { claimed_.store(false, std::memory_order_release); }
+
 private:
     int device_;
     memb_hip_words* handle_ = nullptr;
+    std::atomic<bool> claimed_{false};
 };
 
 class Reader {

@@ -3,6 +3,8 @@ the HIP batch-lookup path. `reader[word]` / `reader[list_of_words]` return numpy
 float32 exactly as the reference does; words the model does not know give zeros.
 Everything below "additions" is new: row ids, strided outputs, results that stay
 on the GPU."""
+import numbers
+import threading
 from abc import ABC, abstractmethod
 
 import numpy as np
@@ -62,6 +64,51 @@ def _current_stream(torch, index):
     return torch.cuda.current_stream(index).cuda_stream
 
 
+class WordBatches:
+    """The word batches (packed query words: pinned + device buffers, kept between calls) of one Reader or ReadersUnion.
+    A call takes a free batch, or a new one when every batch is out, and gives it back when it returns: no batch is ever
+    shared by two calls in flight, and there are never more batches than concurrent callers. The free list is a stack,
+    so a single caller keeps reusing one batch, whose next begin waits for the lookups still reading it."""
+
+    def __init__(self):
+        self._free = []
+        self._lock = threading.Lock()
+        self.last = None   # the batch given back most recently
+
+    def take(self, device):
+        with self._lock:
+            if self._free:
+                return self._free.pop()
+        return _memb.WordBatch(device)
+
+    def give(self, batch):
+        with self._lock:
+            self._free.append(batch)
+            self.last = batch
+
+
+def host_offsets(offsets):
+    '''offsets of resolve_packed_device's host path as a contiguous numpy.uint32 array, never cast silently: any integer
+    array or sequence; a value outside 0 .. 0xFFFFFFFF is a ValueError, anything but integers a TypeError. A
+    C-contiguous uint32 array is passed on as it is.'''
+    if isinstance(offsets, np.ndarray) and offsets.dtype == np.uint32 and offsets.flags.c_contiguous:
+        return offsets
+    array = np.asarray(offsets)
+    if array.dtype.kind not in 'iu' and not isinstance(offsets, np.ndarray):
+        # a sequence that numpy holds as float or object (Python ints beyond int64 among them): judged by its values
+        values = list(offsets)
+        if not all(isinstance(value, numbers.Integral) and not isinstance(value, (bool, np.bool_)) for value in values):
+            raise TypeError('offsets must be integers')
+        if min(values) < 0 or max(values) > 0xFFFFFFFF:
+            raise ValueError('offsets must lie in 0 .. 0xFFFFFFFF')
+        return np.array(values, dtype=np.uint32)
+    if array.dtype.kind not in 'iu':
+        raise TypeError('offsets must be integers, not {}'.format(array.dtype))
+    if array.size and (array.min() < 0 or array.max() > 0xFFFFFFFF):
+        raise ValueError('offsets must lie in 0 .. 0xFFFFFFFF')
+    return np.ascontiguousarray(array, dtype=np.uint32)
+
+
 def tokenizer_word_list(tokenizer):
     """The words of a keras Tokenizer placed at their indices, '' where an index
     has no word (index 0 never has one). With `num_words` set only indices below
@@ -113,7 +160,13 @@ class Reader(BaseReader):
             self._impl = _memb.Reader(name, num_threads, -1 if device is None else int(device), max_direct_decode_bits)
         if host_below is not None:
             self._impl.set_host_below(int(host_below))
-        self._word_batch = None   # packed query words of resolve_rows_device (pinned + device buffers, kept between calls)
+        self._word_batches = WordBatches()   # of resolve_rows_device / resolve_packed_device: one per call in flight
+
+    @property
+    def _word_batch(self):
+        """the word batch a call of this reader gave back most recently (tests and measurement hooks look up its packed
+        words again); None before the first call"""
+        return self._word_batches.last
 
     @property
     def dim(self):
@@ -226,6 +279,7 @@ class Reader(BaseReader):
         looked up by one kernel in a hash table over the model's keys (the same answers as the host search -- the
         reference's lower_bound + strcmp, src/trained_compression.cpp:115-125 -- misses as 0xFFFFFFFF). Returns a
         torch.int32 tensor on this reader's device; nothing waits for the GPU, the row ids never visit the host.
+        May be called from several threads at once (each call packs its words into a batch of its own).
         out : optional contiguous int32 / uint32 tensor of len(words) entries on this reader's device'''
         import torch
         index = self._impl.device()
@@ -237,20 +291,25 @@ class Reader(BaseReader):
         elif (out.device.type != 'cuda' or out.device.index != index or out.dtype not in (torch.int32, torch.uint32)
               or not out.is_contiguous() or out.numel() != n):
             raise TypeError('out must be a contiguous int32/uint32 tensor of len(words) entries on cuda:{}'.format(index))
-        if self._word_batch is None:
-            self._word_batch = _memb.WordBatch(index)
-        self._impl.words_to_rows_device(self._word_batch, words, out.data_ptr(), _current_stream(torch, index))
+        batch = self._word_batches.take(index)
+        try:
+            self._impl.words_to_rows_device(batch, words, out.data_ptr(), _current_stream(torch, index))
+        finally:
+            self._word_batches.give(batch)
         return out
 
     def resolve_packed_device(self, data, offsets, out=None):
         '''resolve_rows_device for words that are packed already (a tokenizer's output): word i is the UTF-8 bytes
         data[offsets[i]:offsets[i + 1]]. No str object is touched -- the walk over a list of 2.2 M str is a cache miss per
         word and the larger half of resolve_rows_device's time.
-        data : bytes-like (bytes, bytearray, memoryview, numpy.uint8) with offsets a numpy.uint32 array of n + 1 ascending
-            entries -- copied once into pinned memory by pooled threads (GIL released), the lookups of finished runs overlap
-            the copy of later ones; or BOTH torch tensors on this reader's device (uint8, int32 / uint32): looked up in place
-            (memb_hip_resolve_packed_device).
-        Returns the torch.int32 row ids on this reader's device (0xFFFFFFFF = not in the model).'''
+        data : bytes-like (bytes, bytearray, memoryview, numpy.uint8) with offsets n + 1 ascending integers (any integer
+            array or sequence; a value outside 0 .. 0xFFFFFFFF is a ValueError, a non-integer dtype a TypeError) -- copied
+            once into pinned memory by pooled threads (GIL released), the lookups of finished runs overlap the copy of later
+            ones; or BOTH torch tensors on this reader's device (uint8, int32 / uint32): looked up in place
+            (memb_hip_resolve_packed_device_bounded: a word whose offsets run backwards or reach past data.numel() is
+            0xFFFFFFFF; int32 offsets are read as uint32).
+        Returns the torch.int32 row ids on this reader's device (0xFFFFFFFF = not in the model).
+        May be called from several threads at once (each call packs its words into a batch of its own).'''
         import torch
         index = self._impl.device()
         if index == _memb.HOST_DEVICE:
@@ -270,17 +329,21 @@ class Reader(BaseReader):
             for tensor, kinds in ((data, (torch.uint8,)), (offsets, (torch.int32, torch.uint32))):
                 if tensor.device.type != 'cuda' or tensor.device.index != index or tensor.dtype not in kinds or not tensor.is_contiguous():
                     raise TypeError('device-resident words: contiguous uint8 bytes and int32 offsets on cuda:{}'.format(index))
-            self._impl.packed_device_to_rows_device(data.data_ptr(), offsets.data_ptr(), n, out.data_ptr(), _current_stream(torch, index))
+            self._impl.packed_device_to_rows_device(
+                data.data_ptr(), data.numel(), offsets.data_ptr(), n, out.data_ptr(), _current_stream(torch, index))
             return out
-        if self._word_batch is None:
-            self._word_batch = _memb.WordBatch(index)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
-        self._impl.packed_to_rows_device(self._word_batch, data, offsets, out.data_ptr(), _current_stream(torch, index))
+        offsets = host_offsets(offsets)
+        batch = self._word_batches.take(index)
+        try:
+            self._impl.packed_to_rows_device(batch, data, offsets, out.data_ptr(), _current_stream(torch, index))
+        finally:
+            self._word_batches.give(batch)
         return out
 
     def batch_embedding_device(self, words):
         '''batch_embedding with the result left on the GPU as a torch.Tensor (DLPack capable). Words are resolved on
-        the GPU as well (resolve_rows_device): the only host work is packing the strings.'''
+        the GPU as well (resolve_rows_device): the only host work is packing the strings. May be called from several
+        threads at once.'''
         return self.rows_embedding_device(self.resolve_rows_device(words))
 
     def rows_embedding_device_many(self, batches):

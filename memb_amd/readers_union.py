@@ -10,7 +10,7 @@ its column block of the result (the C ABI's `ld` / `col_off`), and
 """
 import numpy as np
 
-from .reader import BaseReader, Reader, tokenizer_word_list
+from .reader import BaseReader, Reader, WordBatches, tokenizer_word_list
 
 CONCATENATE = 'concatenate'
 AVERAGE = 'average'
@@ -41,7 +41,7 @@ class ReadersUnion(BaseReader):
         self._readers = list(readers)
         self._mode = mode
         self._widths = widths
-        self._word_batch = None   # packed query words of batch_embedding_device, shared by the readers
+        self._word_batches = WordBatches()   # of batch_embedding_device (one per call in flight), shared by the readers
 
     @property
     def dim(self):
@@ -74,7 +74,8 @@ class ReadersUnion(BaseReader):
         reference API). Concatenation: column blocks of one (n, dim) tensor. Average:
         reader 1 stores, readers 2..R add, the last one also divides by R -- the very
         additions and the one division numpy.mean performs, in its order, so the
-        result has the same bits as batch_embedding. All readers on one device."""
+        result has the same bits as batch_embedding. All readers on one device. May be called from several threads
+        at once."""
         import torch
         readers = self._readers
         if not all(isinstance(reader, Reader) for reader in readers):
@@ -87,10 +88,12 @@ class ReadersUnion(BaseReader):
         # the words are packed and copied ONCE and resolved on the GPU by every reader's own hash table
         # (Reader.resolve_rows_device): the row ids never visit the host
         row_ids = [torch.empty((len(words),), dtype=torch.int32, device=device) for _ in readers]
-        if self._word_batch is None:
-            self._word_batch = _memb.WordBatch(readers[0].device)
-        _memb.union_words_to_rows_device(
-            self._word_batch, words, [reader._impl for reader in readers], [ids.data_ptr() for ids in row_ids], stream)
+        batch = self._word_batches.take(readers[0].device)
+        try:
+            _memb.union_words_to_rows_device(
+                batch, words, [reader._impl for reader in readers], [ids.data_ptr() for ids in row_ids], stream)
+        finally:
+            self._word_batches.give(batch)
         merged = torch.empty((len(words), self.dim), dtype=torch.float32, device=device)
         # one launch that decodes every reader's words of a tile and writes the merged rows once,
         # where the readers can share a kernel

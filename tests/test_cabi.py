@@ -16,7 +16,7 @@ def declared_functions():
     return sorted(set(re.findall(r'\b(memb_hip_[a-z_]+)\s*\(', text)))
 
 
-def test_header_declares_the_expected_entry_points():
+def test_header_declares_exactly_the_expected_entry_points():
     assert declared_functions() == sorted([
         'memb_hip_device_count', 'memb_hip_ctx_create_trained', 'memb_hip_ctx_create_uniform',
         'memb_hip_ctx_create_full', 'memb_hip_ctx_destroy', 'memb_hip_ctx_get_info', 'memb_hip_decode_rows',
@@ -29,6 +29,8 @@ def test_header_declares_the_expected_entry_points():
         'memb_hip_words_begin', 'memb_hip_words_commit', 'memb_hip_words_count', 'memb_hip_resolve_rows_device',
         'memb_hip_resolve_range_device', 'memb_hip_resolve_range_union_device', 'memb_hip_resolve_packed_device',
         'memb_hip_decode_batches_device', 'memb_hip_decode_words',
+        # ABI 6: device-resident words checked against the extent of their byte buffer
+        'memb_hip_resolve_packed_device_bounded',
     ])
 
 
@@ -78,6 +80,16 @@ def test_error_reporting_without_compute(native):
     assert library.memb_hip_words_commit(None) == 1
     assert library.memb_hip_resolve_range_device(None, None, ctypes.c_size_t(0), ctypes.c_size_t(0), None, None) == 1
     assert library.memb_hip_resolve_packed_device(None, None, None, ctypes.c_size_t(0), None, None) == 1
+    bounded = library.memb_hip_resolve_packed_device_bounded
+    bounded.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                        ctypes.c_void_p]
+    assert bounded(None, None, 0, None, 0, None, None) == 1
+    assert b'null' in library.memb_hip_last_error()
+    # (a context is refused before anything else: null offsets, rows or bytes of a non-empty buffer are refused too, with
+    # any context -- a fake one is never dereferenced)
+    fake = ctypes.c_void_p(8)
+    assert bounded(fake, None, 0, None, 5, None, None) == 1
+    assert bounded(fake, None, 16, ctypes.c_void_p(8), 5, ctypes.c_void_p(8), None) == 1
     assert library.memb_hip_decode_batches_device(None, None, ctypes.c_size_t(0), None) == 1
     assert library.memb_hip_decode_words(None, None, None, ctypes.c_size_t(0), ctypes.c_size_t(0)) == 1
     if count.value == 0:

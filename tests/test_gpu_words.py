@@ -685,3 +685,126 @@ def test_words_that_are_packed_already(native, make_model):
         reader.resolve_packed_device(b'abc', np.array([0, 2, 9], dtype=np.uint32))        # past the end of the bytes
     with pytest.raises(TypeError):
         reader.resolve_packed_device(blob, torch.zeros(3, dtype=torch.int32, device='cuda'))   # one on the host, one on the device
+
+
+def _packed(words):
+    encoded = [word.encode('utf-8') for word in words]
+    offsets = np.zeros(len(words) + 1, dtype=np.uint32)
+    np.cumsum([len(e) for e in encoded], out=offsets[1:])
+    return b''.join(encoded), offsets
+
+
+def _bounded_answers(checker, data, offsets):
+    """What resolve_packed_device owes for words data[offsets[i]:offsets[i + 1]], offsets read as uint32: MISSING for a
+    word whose offsets run backwards or reach past the end of `data`, the checker's row of its bytes for every other"""
+    offsets = np.asarray(offsets).astype(np.int64) & 0xFFFFFFFF
+    words = [data[begin:end] if begin <= end <= len(data) else None for begin, end in zip(offsets[:-1], offsets[1:])]
+    rows = iter(checker.resolve_rows([word for word in words if word is not None]))
+    return np.array([MISSING if word is None else next(rows) for word in words], dtype=np.uint32)
+
+
+def test_host_offsets_are_checked_not_cast(native, make_model):
+    """Host offsets of resolve_packed_device: any integer array or sequence whose values fit uint32 gives the answers of
+    uint32 offsets; a value that does not fit is a ValueError and a non-integer dtype a TypeError -- never a cast (which
+    turned int64 [0, 2**32 + 3] into [0, 3] and -1 into 0xFFFFFFFF, and resolved other bytes without a word)."""
+    path, words = make_model(30000, 300, 'trained', 4)
+    reader = native.Reader(path)
+    checker = oracle.OracleReader(path)
+    queries = words[:300] + ['', 'nope', 'naïve-日本語'] + words[300:400]
+    blob, offsets = _packed(queries)
+    expected = checker.resolve_rows(queries)
+    for valid in (offsets, offsets.astype(np.int64), offsets.astype(np.int32), offsets.astype(np.uint64),
+                  offsets.tolist(), tuple(int(v) for v in offsets)):
+        got = reader.resolve_packed_device(blob, valid)
+        assert np.array_equal(got.cpu().numpy().view(np.uint32), expected), type(valid)
+    padded = blob + b'x' * 8
+    for value in (2 ** 32 + 3, 2 ** 32, 2 ** 63, 2 ** 64):
+        with pytest.raises(ValueError):
+            reader.resolve_packed_device(padded, [0, value])
+        if value < 2 ** 63:
+            with pytest.raises(ValueError):
+                reader.resolve_packed_device(padded, np.array([0, value], dtype=np.int64))
+    with pytest.raises(ValueError):
+        reader.resolve_packed_device(padded, np.array([-1, 3], dtype=np.int64))
+    with pytest.raises(ValueError):
+        reader.resolve_packed_device(padded, [0, 2, -1])
+    for bad in (np.array([0.0, 3.0]), [0, 2.5], [0, 3.0], np.array([False, True]), np.array([0, 3], dtype=object)):
+        with pytest.raises(TypeError):
+            reader.resolve_packed_device(padded, bad)
+
+
+def test_device_words_past_the_end_of_their_buffer_are_missing(native, make_model):
+    """Device-resident words are bounded by data.numel(): `data` is a view big[:k] of a larger tensor whose bytes behind
+    k spell a real key. A word whose offsets reach past k -- wholly or in part -- or run backwards is not in the model,
+    and every other word keeps its answer. (Every read stays inside the one allocation: without the bound the hidden
+    key's row comes back, and still nothing is read outside a live buffer.)"""
+    import torch
+    path, words = make_model(30000, 300, 'trained', 4)
+    reader = native.Reader(path)
+    checker = oracle.OracleReader(path)
+    rng = np.random.default_rng(21)
+    queries = [words[i] for i in rng.integers(0, len(words), size=700)] + ['', 'nope']
+    hidden = words[123].encode('utf-8')
+    assert checker.resolve_rows([words[123]])[0] != MISSING
+    blob, offsets = _packed(queries)
+    k = len(blob)
+    big = torch.from_numpy(np.frombuffer(blob + hidden + b'\x00' * 64, dtype=np.uint8).copy()).cuda()
+    data = big[:k]
+    # three words behind the 702: the hidden key (wholly behind the view), one that runs backwards, one across the end
+    offsets = np.concatenate([offsets, [k + len(hidden), k - 1, k + 1]]).astype(np.uint32)
+    expected = _bounded_answers(checker, blob, offsets)
+    assert expected[-3:].tolist() == [MISSING] * 3
+    got = reader.resolve_packed_device(data, torch.from_numpy(offsets.view(np.int32)).cuda())
+    torch.cuda.synchronize()
+    got = got.cpu().numpy().view(np.uint32)
+    assert np.array_equal(got, expected), [(i, int(got[i]), int(expected[i])) for i in np.nonzero(got != expected)[0][:5]]
+
+
+def test_device_offsets_that_wrap_or_run_backwards_are_missing(native, make_model):
+    """int32 offsets with negative entries (read as 2**31 and more) and pairs that run backwards: MISSING for the words
+    they bound, every other word keeps its answer, whichever lane of a wavefront holds the bad word."""
+    import torch
+    path, words = make_model(30000, 300, 'trained', 4)
+    reader = native.Reader(path)
+    checker = oracle.OracleReader(path)
+    rng = np.random.default_rng(22)
+    queries = [words[i] for i in rng.integers(0, len(words), size=900)] + ['', 'nope', 'naïve-日本語']
+    blob, offsets = _packed(queries)
+    poisoned = offsets.astype(np.int64)
+    for entry in (0, 10, 200, 513):
+        poisoned[entry] = -5 - entry                 # spoils words entry - 1 (its end) and entry (its begin)
+    for entry in (70, 640):
+        poisoned[entry] = poisoned[entry + 1] + 2    # word entry runs backwards; word entry - 1 grows over its neighbour
+    poisoned[-1] = 0x7FFFFFFF                        # the last word ends far past the bytes
+    poisoned = poisoned.astype(np.int32)
+    expected = _bounded_answers(checker, blob, poisoned)
+    assert (expected == MISSING).sum() >= 10
+    data = torch.from_numpy(np.frombuffer(blob, dtype=np.uint8).copy()).cuda()
+    got = reader.resolve_packed_device(data, torch.from_numpy(poisoned).cuda())
+    torch.cuda.synchronize()
+    got = got.cpu().numpy().view(np.uint32)
+    assert np.array_equal(got, expected), [(i, int(got[i]), int(expected[i])) for i in np.nonzero(got != expected)[0][:5]]
+    # the reader still answers afterwards
+    again = reader.resolve_packed_device(data, torch.from_numpy(offsets.view(np.int32)).cuda())
+    assert np.array_equal(again.cpu().numpy().view(np.uint32), checker.resolve_rows(queries))
+
+
+def test_packed_fill_hook_checks_its_arguments(native):
+    """_memb._packed_fill_seconds (a measurement hook of the shipped module) makes the argument checks of
+    packed_to_rows_device: no offsets at all, items of more than one byte, or buffers that are not contiguous are refused
+    before anything is read."""
+    from memb_amd import _memb
+    batch = _memb.WordBatch(0)
+    two = np.array([0, 2], dtype=np.uint32)
+    with pytest.raises(TypeError):
+        _memb._packed_fill_seconds(batch, b'', np.zeros(0, dtype=np.uint32))
+    with pytest.raises(TypeError):
+        _memb._packed_fill_seconds(batch, np.zeros(8, dtype=np.uint16), two)
+    with pytest.raises(TypeError):
+        _memb._packed_fill_seconds(batch, np.zeros(16, dtype=np.uint8)[::2], two)
+    with pytest.raises(TypeError):
+        _memb._packed_fill_seconds(batch, b'abcd', np.array([0, 9, 2, 9, 4], dtype=np.uint32)[::2])
+    with pytest.raises(TypeError):
+        _memb._packed_fill_seconds(batch, b'abcd', two.astype(np.int64))
+    assert _memb._packed_fill_seconds(batch, b'abcd', np.array([0, 2, 4], dtype=np.uint32)) >= 0
+    assert batch.size() == 2

@@ -76,6 +76,28 @@ def test_word_search_on_a_larger_vocabulary(native, make_model):
     assert all(rows[i] == order[probes[i]] for i in range(3000))
 
 
+
+def test_packed_word_offsets_are_never_cast_silently(native):
+    """Host offsets of Reader.resolve_packed_device (memb_amd.reader.host_offsets): integer arrays and sequences become
+    uint32 when every value fits; a value outside 0 .. 0xFFFFFFFF is a ValueError and anything but integers a TypeError
+    (a plain cast turned int64 [0, 2**32 + 3] into [0, 3]); a C-contiguous uint32 array is passed on without a copy."""
+    from memb_amd.reader import host_offsets
+    offsets = np.array([0, 3, 5], dtype=np.uint32)
+    assert host_offsets(offsets) is offsets
+    for valid in (np.array([0, 3], dtype=np.int64), [0, 3], (0, 3), np.array([0, 3], dtype=np.int32),
+                  np.array([0, 3], dtype=np.uint64), [np.int64(0), 3], np.array([0, 0xFFFFFFFF], dtype=np.int64)[::1]):
+        converted = host_offsets(valid)
+        assert converted.dtype == np.uint32 and converted.flags.c_contiguous
+        assert converted.tolist() == [int(v) for v in valid]
+    for too_large in ([0, 2 ** 32 + 3], np.array([0, 2 ** 32 + 3]), [0, 2 ** 32], [0, 2 ** 63], [0, 2 ** 64], [-1, 2],
+                      np.array([-1, 2]), np.array([0, 2 ** 63], dtype=np.uint64)):
+        with pytest.raises(ValueError):
+            host_offsets(too_large)
+    for not_integers in (np.array([0.0, 2.0]), [0, 2.5], [0, 2.0], np.array([True, False]), [True, False],
+                         np.array([0, 1], dtype=object), ['0', '1']):
+        with pytest.raises(TypeError):
+            host_offsets(not_integers)
+
 def test_hash_index_lookup_equals_binary_search(native, make_model):
     # batches >= 4096 words go through the lazily built hash index; it must give the binary search's answers
     path, words = make_model(5000, dim=8, storage='trained', bits=4)
