@@ -905,7 +905,27 @@ PYBIND11_MODULE(_memb, m) {
             py::arg("stream") = 0,
             py::arg("accumulate") = false,
             py::arg("divisor") = 0.0f,
-            py::arg("random_order") = false);
+            py::arg("random_order") = false)
+        .def(
+            "rows_to_device_typed",
+            [](memb::Reader& reader, uintptr_t rows, size_t n, uintptr_t out, int outType, size_t ld, size_t colOff,
+               uintptr_t stream)
+            {
+                reader.rowsToDeviceBufferTyped(
+                    reinterpret_cast<const uint32_t*>(rows), n, reinterpret_cast<void*>(out), outType, ld, colOff,
+                    reinterpret_cast<void*>(stream));
+            },
+            py::arg("rows_ptr"),
+            py::arg("n"),
+            py::arg("out_ptr"),
+            py::arg("out_type"),
+            py::arg("ld"),
+            py::arg("col_off") = 0,
+            py::arg("stream") = 0);
+
+    m.attr("OUT_F32") = MEMB_HIP_OUT_F32;
+    m.attr("OUT_BF16") = MEMB_HIP_OUT_BF16;
+    m.attr("OUT_F16") = MEMB_HIP_OUT_F16;
 
     m.def("available_compression_strategies", &memb::availableCompressionStrategies);
 

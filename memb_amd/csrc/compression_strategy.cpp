@@ -137,6 +137,17 @@ void CompressedStorage::decodeRowsDevice(
     }
 }
 
+void CompressedStorage::decodeRowsDeviceTyped(
+    const uint32_t* rows, size_t n, void* out, int outType, size_t ld, size_t colOff, void* stream) const
+{
+    if (onHost()) {
+        throw std::runtime_error("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device");
+    }
+    if (memb_hip_decode_rows_device_typed(deviceContext(), rows, n, out, outType, ld, colOff, stream) != MEMB_HIP_OK) {
+        throwDeviceError("HIP batch lookup failed");
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Word -> row on the device
 // ---------------------------------------------------------------------------

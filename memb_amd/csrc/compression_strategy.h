@@ -17,6 +17,7 @@
 
 #include "wire.h"
 #include "../../include/memb_hip.h"
+#include "../../include/memb_hip_narrow.h"
 
 #include <atomic>
 #include <memory>
@@ -60,6 +61,9 @@ public:
     void decodeRowsDevice(
         const uint32_t* rows, size_t n, float* out, size_t ld, size_t colOff, void* stream,
         bool accumulate = false, float divisor = 0.f, bool randomOrder = false) const;
+    // Same with elements of outType (include/memb_hip_narrow.h: MEMB_HIP_OUT_*); ld and colOff count elements.
+    void decodeRowsDeviceTyped(
+        const uint32_t* rows, size_t n, void* out, int outType, size_t ld, size_t colOff, void* stream) const;
 
     // device == HOST_DEVICE: rows are decoded by extractRowHost on host threads
     static constexpr int HOST_DEVICE = -2;

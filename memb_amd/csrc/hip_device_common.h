@@ -77,3 +77,24 @@ __device__ __forceinline__ float4 epilogue4(float4 value, const float* destinati
     }
     return value;
 }
+
+// Narrow output elements (memb_hip_narrow.hip; OUT = MEMB_HIP_OUT_BF16 or MEMB_HIP_OUT_F16 of include/memb_hip_narrow.h): an
+// fp32 value rounded once to the nearest even value by a plain cast -- v_cvt_pk_bf16_f32 / v_cvt_f16_f32 on gfx950, which
+// under the library's float mode (subnormals kept) give torch's bits for subnormals, infinities and signed zeros and keep
+// a NaN a NaN. (The integer form (u + 0x7FFF + ((u >> 16) & 1)) >> 16 turns some NaNs into zeros or infinities.)
+template <int OUT>
+__device__ __forceinline__ uint32_t narrowBits(float value)
+{
+    if constexpr (OUT == 1) {   // MEMB_HIP_OUT_BF16
+        return __builtin_bit_cast(uint16_t, static_cast<__bf16>(value));
+    } else {                    // MEMB_HIP_OUT_F16
+        return __builtin_bit_cast(uint16_t, static_cast<_Float16>(value));
+    }
+}
+
+// two values, `low` in the lower half: the dword at the lower address of a little-endian pair
+template <int OUT>
+__device__ __forceinline__ uint32_t narrowPair(float low, float high)
+{
+    return narrowBits<OUT>(low) | (narrowBits<OUT>(high) << 16);
+}

@@ -252,6 +252,9 @@ __device__ __forceinline__ void unpackMeta(const TrainedParams& p, const LaneRol
 #ifndef MEMB_HIP_OUTPUT_BURST
 #define MEMB_HIP_OUTPUT_BURST 5   // 16-byte pieces a lane gathers before it stores them back to back (outputTile)
 #endif
+#ifndef MEMB_HIP_NARROW_FLAT_BURST
+#define MEMB_HIP_NARROW_FLAT_BURST 4   // the same for 16-byte pieces of bf16 / fp16 (outputTileNarrow, OUT_FLAT)
+#endif
 
 constexpr int STREAM_REGISTERS = 4;   // 16-byte pieces one lane can hold for a prefetched tile
 
@@ -464,6 +467,102 @@ __device__ __forceinline__ void decodeSegment(
     }
 }
 
+// Symbol tile -> bf16 / fp16 rows (decode_trained_narrow, memb_hip_narrow.hip). The codebook in LDS holds the rounded
+// values already (setUpLds): 256 of 2 bytes for byte keys, 256 pairs of 4 bytes for nibble keys, so an output value is
+// one gather and no conversion. A half-piece h = 4 consecutive values of the tile, linear in the symbol tile as for fp32.
+//   OUT_FLAT   rows back to back (ld = dim, col_off = 0): a lane gathers two half-pieces and stores 8 values with one
+//              16-byte store (the host picks this mode only where every tile starts 16-byte aligned); a tile whose
+//              values end on an odd half-piece ends with one 8-byte store
+//   OUT_VEC4   one half-piece per 8-byte store, row by row (dim, ld, col_off multiples of 4, out 8-byte aligned)
+//   OUT_SCALAR one 2-byte store per value: no store touches a byte outside a row's columns
+template <int MODE, bool FAST, int OUT, int BURST = MODE == OUT_FLAT ? MEMB_HIP_NARROW_FLAT_BURST : MEMB_HIP_OUTPUT_BURST>
+__device__ __forceinline__ void outputTileNarrow(
+    const TrainedParams& p, const uint32_t* codebookLds, const uint32_t* keyTile, unsigned long long tileBase,
+    uint32_t tileWords, uint32_t lane, const LaneRole& role, bool present)
+{
+    const uint16_t* valueLds = reinterpret_cast<const uint16_t*>(codebookLds);
+    uint16_t* out = reinterpret_cast<uint16_t*>(p.out);
+    // nibble keys have no absent key: absent words are looked up in the ballot (outputTile)
+    unsigned long long absent = 0;
+    if (FAST) {
+        absent = __ballot(!present && !role.spare && role.segment == 0 && role.word < tileWords);
+    }
+    const bool checkWords = FAST && absent != 0;
+    const uint32_t halvesPerWord = p.dim / 4;
+    // the four values of half-piece h as two dwords; zeros where the half-piece's word is absent
+    auto gather = [&](uint32_t h) -> uint2 {
+        uint2 v;
+        if (FAST) {
+            const uint32_t k = reinterpret_cast<const uint16_t*>(keyTile)[h];
+            v.x = codebookLds[k & 0xff];
+            v.y = codebookLds[k >> 8];
+        } else {
+            const uint32_t k = keyTile[h];
+            v.x = valueLds[k & 0xff] | (static_cast<uint32_t>(valueLds[(k >> 8) & 0xff]) << 16);
+            v.y = valueLds[(k >> 16) & 0xff] | (static_cast<uint32_t>(valueLds[k >> 24]) << 16);
+        }
+        if (checkWords && ((absent >> (fastDivide(h, p.pieceMagic, halvesPerWord) * p.lanesPerWord)) & 1)) {
+            v = make_uint2(0u, 0u);
+        }
+        return v;
+    };
+
+    if (MODE == OUT_FLAT || MODE == OUT_VEC4) {
+        const uint32_t halves = tileWords * halvesPerWord;
+        uint16_t* tileOut = out + tileBase * p.ld + p.colOff;
+        constexpr uint32_t PER_LANE = MODE == OUT_FLAT ? 2 : 1;   // half-pieces per store
+        const uint32_t pieces = (halves + PER_LANE - 1) / PER_LANE;
+        for (uint32_t q0 = lane; q0 < pieces; q0 += WAVE * BURST) {
+            uint2 v[BURST][PER_LANE];
+#pragma unroll
+            for (int u = 0; u < BURST; ++u) {
+#pragma unroll
+                for (uint32_t s = 0; s < PER_LANE; ++s) {
+                    v[u][s] = gather(min((q0 + WAVE * u) * PER_LANE + s, halves - 1));
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < BURST; ++u) {
+                const uint32_t q = q0 + WAVE * u;
+                if (q >= pieces) {
+                    continue;
+                }
+                if (MODE == OUT_FLAT) {
+                    uint16_t* destination = tileOut + 8 * static_cast<size_t>(q);
+                    if (2 * q + 1 < halves) {
+                        *reinterpret_cast<uint4*>(destination) = make_uint4(v[u][0].x, v[u][0].y, v[u][PER_LANE - 1].x, v[u][PER_LANE - 1].y);
+                    } else {
+                        *reinterpret_cast<uint2*>(destination) = v[u][0];
+                    }
+                } else {
+                    const uint32_t w = fastDivide(q, p.pieceMagic, halvesPerWord);
+                    const uint32_t c = q - w * halvesPerWord;
+                    *reinterpret_cast<uint2*>(tileOut + w * p.ld + 4 * c) = v[u][0];
+                }
+            }
+        }
+    } else {
+        const uint8_t* keyBytes = reinterpret_cast<const uint8_t*>(keyTile);
+        const uint32_t total = tileWords * p.dim;
+        for (uint32_t q = lane; q < total; q += WAVE) {
+            const uint32_t w = q / p.dim;
+            const uint32_t c = q - w * p.dim;
+            uint32_t value;
+            if (FAST) {
+                // a lone nibble n indexes the pair of key byte n: (centroid n, centroid 0)
+                const uint32_t k = keyBytes[w * p.keyRowBytes + (c >> 1)];
+                value = codebookLds[(k >> (4 * (c & 1))) & 15] & 0xFFFFu;
+                if (checkWords && ((absent >> (w * p.lanesPerWord)) & 1)) {
+                    value = 0;
+                }
+            } else {
+                value = valueLds[keyBytes[w * p.keyRowBytes + c]];
+            }
+            out[(tileBase + w) * p.ld + p.colOff + c] = static_cast<uint16_t>(value);
+        }
+    }
+}
+
 // Symbol tile -> fp32 rows: codebook gather and row-contiguous stores.
 template <int MODE, bool FAST, int BURST = MEMB_HIP_OUTPUT_BURST>
 __device__ __forceinline__ void outputTile(
@@ -607,8 +706,9 @@ __device__ __forceinline__ WaveLds waveLds(const TrainedParams& p, uint32_t* lds
     return result;
 }
 
-// Loads table and codebook; ends with a block barrier.
-template <int MODE>
+// Loads table and codebook; ends with a block barrier. A narrow OUT rounds the codebook once on its way into LDS: every
+// output value is a centroid, so that is each output rounded once (p.codebookDwords counts the narrow dwords).
+template <int MODE, int OUT = 0>
 __device__ __forceinline__ WaveLds setUpLds(const TrainedParams& p, uint32_t* lds)
 {
     uint32_t* codebookLds = lds + p.tableDwords;
@@ -616,7 +716,12 @@ __device__ __forceinline__ WaveLds setUpLds(const TrainedParams& p, uint32_t* ld
     for (uint32_t i = threadIdx.x; copy && i < p.tableDwords / 4; i += blockDim.x) {
         reinterpret_cast<uint4*>(lds)[i] = reinterpret_cast<const uint4*>(p.table)[i];
     }
-    if (MODE != OUT_INDEX && MODE != OUT_KEYS) {
+    if constexpr (OUT != 0) {
+        for (uint32_t i = threadIdx.x; copy && i < p.codebookDwords; i += blockDim.x) {
+            const float2 pair = reinterpret_cast<const float2*>(p.codebook)[i];
+            codebookLds[i] = narrowPair<OUT>(pair.x, pair.y);
+        }
+    } else if (MODE != OUT_INDEX && MODE != OUT_KEYS) {
         for (uint32_t i = threadIdx.x; copy && i < p.codebookDwords; i += blockDim.x) {
             codebookLds[i] = reinterpret_cast<const uint32_t*>(p.codebook)[i];
         }
@@ -687,7 +792,9 @@ __device__ __forceinline__ void noteBatchOrder(const TrainedParams& p, uint32_t 
 // and the block copies table and codebook into LDS once for all of them; the row ids of the next tile are loaded while
 // this one is decoded.
 // BATCHES: the tiles are virtual tiles of a BatchList (decode_trained_batches); otherwise `list` is not looked at.
-template <bool HAS_SUB, int MODE, bool FAST, bool BATCHES>
+// OUT: the output element -- 0 = float, else MEMB_HIP_OUT_BF16 / MEMB_HIP_OUT_F16 (decode_trained_narrow: outputTileNarrow,
+// and no order word).
+template <bool HAS_SUB, int MODE, bool FAST, bool BATCHES, int OUT = 0>
 __device__ __forceinline__ void decodeTilesOfBlock(const TrainedParams& p, const BatchList& list, uint32_t* lds)
 {
     // byte keys: 4-byte table entries; the index pass keeps the 8-byte table. (Nibble keys through the 4-byte entries here
@@ -709,9 +816,10 @@ __device__ __forceinline__ void decodeTilesOfBlock(const TrainedParams& p, const
     // without the T loop: 10 000 rows -5 %, dumps +6..+10 %. The BASELINE configurations that run this kernel are dumps:
     // a block that starts its dependent loads a microsecond later is the better citizen there (round 3 had seen the same
     // sign with a cruder ordering).
-    const WaveLds mem = setUpLds<MODE>(p, lds);
+    constexpr bool NARROW = OUT != 0;
+    const WaveLds mem = setUpLds<MODE, OUT>(p, lds);
 #ifndef MEMB_HIP_NO_ORDER_PROBE   // (two builds side by side: tools/perf/r6/probe_cost.sh)
-    if (!BATCHES && MODE != OUT_INDEX && blockIdx.x == 0 && threadIdx.x < WAVE && p.orderOut) {   // (one wavefront of the grid)
+    if (!BATCHES && !NARROW && MODE != OUT_INDEX && blockIdx.x == 0 && threadIdx.x < WAVE && p.orderOut) {   // (one wavefront of the grid)
         noteBatchOrder(p, lane);
     }
 #endif
@@ -770,7 +878,11 @@ __device__ __forceinline__ void decodeTilesOfBlock(const TrainedParams& p, const
         if (MODE != OUT_INDEX) {
             waveLdsFence();
             if (!(measureFlags(q) & 2)) {
-                outputTile<MODE, FAST>(q, mem.codebook, mem.keyTile, tileBase, tileWords, lane, role, meta.row < q.nRows);
+                if constexpr (NARROW) {
+                    outputTileNarrow<MODE, FAST, OUT>(q, mem.codebook, mem.keyTile, tileBase, tileWords, lane, role, meta.row < q.nRows);
+                } else {
+                    outputTile<MODE, FAST>(q, mem.codebook, mem.keyTile, tileBase, tileWords, lane, role, meta.row < q.nRows);
+                }
             }
         }
         waveLdsFence();   // (the next tile's streams and symbols go where this one's were)
@@ -1393,6 +1505,7 @@ __global__ MEMB_SGPR_BUDGET void decode_union_split(UnionParams u)
     }
 }
 
+#ifndef MEMB_HIP_LOOKUP_KERNELS_ONLY   // (memb_hip_narrow.hip: the staging kernels live in memb_hip.hip alone)
 // Staging: streamStarts + segmentIndex -> rowMeta records (see TrainedParams::rowMeta). One thread per row.
 // With recordPieces != 0 the record goes to piece row * recordPieces of `rowMeta` (= the row-record
 // array) and its first dword holds the row's stream length in bytes instead of a start.
@@ -1453,3 +1566,4 @@ __global__ void repack_streams(
         streams[static_cast<unsigned long long>(first) + piece] = make_uint4(dwords[0], dwords[1], dwords[2], dwords[3]);
     }
 }
+#endif

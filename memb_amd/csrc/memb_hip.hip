@@ -35,7 +35,9 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/memb_hip.h"
+#include "../../include/memb_hip_narrow.h"
 #include "codec.h"
+#include "hip_narrow.h"
 #include "wire.h"
 #include "worker_pool.h"
 
@@ -280,14 +282,16 @@ uint32_t packedTableDwords(const memb_hip_ctx* ctx)
     return roundUp4(static_cast<uint32_t>(ctx->byteTable.entries.size()));
 }
 
-// withKeys: a lookup kernel (symbol tiles; byte-key models then use the PACKED layout); without: the index pass
-uint32_t trainedLdsBytes(const memb_hip_ctx* ctx, uint32_t waves, uint32_t wordsPerWave, bool withKeys)
+// withKeys: a lookup kernel (symbol tiles; byte-key models then use the PACKED layout); without: the index pass.
+// outBytes: bytes of an output element, whose codebook the lookup kernel holds in LDS (2: decode_trained_narrow)
+uint32_t trainedLdsBytes(const memb_hip_ctx* ctx, uint32_t waves, uint32_t wordsPerWave, bool withKeys, uint32_t outBytes = 4)
 {
     uint32_t perWave = wordsPerWave * ctx->slotDwords + (withKeys ? keyTileDwords(ctx, wordsPerWave) : 0);
+    const uint32_t codebook = codebookDwords(ctx) * outBytes / 4;
     if (withKeys && !ctx->fast) {
-        return 4u * (packedTableDwords(ctx) + codebookDwords(ctx) + waves * perWave);
+        return 4u * (packedTableDwords(ctx) + codebook + waves * perWave);
     }
-    return 4u * (ctx->tableDwords + codebookDwords(ctx) + waves * perWave);
+    return 4u * (ctx->tableDwords + codebook + waves * perWave);
 }
 
 // How a kernel writes rows of dim floats to out + row * ld + colOff: in 16-byte pieces where every row starts 16-byte
@@ -322,12 +326,12 @@ uint32_t residentWaves(uint32_t ldsLimit, uint32_t waves, uint32_t ldsBytes, uin
 // unknown): a block size whose LDS would allow more resident wavefronts than the registers do gains nothing by it.
 TrainedGeometry chooseGeometry(
     const memb_hip_ctx* ctx, uint32_t wordsPerWave, size_t ld, size_t colOff, const float* out,
-    uint32_t registerWavesPerCu = ONE_TILE_WAVES_PER_CU, uint32_t preferred = 4)
+    uint32_t registerWavesPerCu = ONE_TILE_WAVES_PER_CU, uint32_t preferred = 4, uint32_t outBytes = 4)
 {
     TrainedGeometry best{};
     const uint32_t forcedWaves = ctx->switches.waves;   // (1 .. 16; anything but 1, 2, 4, 8: measurements)
     auto residentWith = [&](uint32_t waves, uint32_t* ldsBytes) -> uint32_t {
-        *ldsBytes = trainedLdsBytes(ctx, waves, wordsPerWave, true);
+        *ldsBytes = trainedLdsBytes(ctx, waves, wordsPerWave, true, outBytes);
         return residentWaves(ctx->ldsLimit, waves, *ldsBytes, registerWavesPerCu);
     };
     uint32_t preferredLds = 0;
@@ -629,7 +633,7 @@ bool lookupParamsConsistent(const memb_hip_ctx* ctx, const TrainedParams& params
         params.keyRowBytes * (ctx->fast ? 2u : 1u) >= params.dim &&
         uint64_t(params.keyTileDwords) * 4 >= uint64_t(wordsPerWave) * params.keyRowBytes &&
         (params.lanesPerWord == 1 || params.segmentIndex != nullptr) &&
-        geometry.ldsBytes == trainedLdsBytes(ctx, geometry.waves, wordsPerWave, true) &&
+        geometry.ldsBytes == trainedLdsBytes(ctx, geometry.waves, wordsPerWave, true, 4 * params.codebookDwords / codebookDwords(ctx)) &&
         (ctx->fast || (params.table != nullptr && params.tableDwords >= (1u << params.rootBits))) &&
         geometry.ldsBytes <= ctx->ldsLimit;
 }
@@ -692,10 +696,11 @@ bool rowsUnordered(const memb_hip_ctx* ctx, bool callerSaysRandom)
 // -1.1 %, Student-t -2.5 %; the same batches SHUFFLED +3.4 %, -1.3 %, +3.6 %, +3.5 %, +2.9 %; 1 M random rows +2.0 %, -1.5 %,
 // +2.5 %, +2.7 %, +2.1 %: the rule takes the dump's side for every key format and says what it costs the other order
 // (HISTORY.md, "(r5) 5.0", has the table; DESIGN.md section 5.0 the rule as it stands). The 8-bit model runs blocks of eight at every size: chooseGeometry.
-// force: -1 = by the rule, 0 = one tile per wavefront, 1 = decode_records_persistent where the layout allows
+// force: -1 = by the rule, 0 = one tile per wavefront, 1 = decode_records_persistent where the layout allows.
+// outBytes: of the output element (2: decode_trained_narrow, whose codebook takes half the LDS)
 int planTrained(
     const memb_hip_ctx* ctx, size_t n, size_t ld, size_t colOff, const float* out, bool keysOut, TrainedPlan* plan, int force = -1,
-    bool mayBeFine = true, bool randomOrder = false)
+    bool mayBeFine = true, bool randomOrder = false, uint32_t outBytes = 4)
 {
     uint32_t wordsPerWave = WAVE / ctx->lanesPerWord;
     const uint64_t tiles = (n + wordsPerWave - 1) / wordsPerWave;
@@ -719,12 +724,14 @@ int planTrained(
     if (mayBeFine && ctx->fineIndex && ctx->switches.fineLanes == 0 && ctx->switches.persistent != 2 && force != 1) {
         const uint32_t fineWords = WAVE / ctx->fineLanes;
         const uint64_t fineTiles = (n + fineWords - 1) / fineWords;
-        const uint64_t fineRound = uint64_t(ctx->cuCount) * chooseGeometry(ctx, fineWords, ld, colOff, out).resident;
+        const uint64_t fineRound =
+            uint64_t(ctx->cuCount) * chooseGeometry(ctx, fineWords, ld, colOff, out, ONE_TILE_WAVES_PER_CU, 4, outBytes).resident;
         fineByRule = fineTiles <= fineRound;
     }
     plan->fine = mayBeFine && ctx->fineIndex && force != 1 && (ctx->switches.fineLanes == 2 || fineByRule);
     // (models whose tables leave a CU fewer than 1.5 R wavefronts -- the 8-bit one -- keep the edge at 2 R: not measured there)
-    const uint64_t usualRound = uint64_t(ctx->cuCount) * chooseGeometry(ctx, wordsPerWave, ld, colOff, out).resident;
+    const uint64_t usualRound =
+        uint64_t(ctx->cuCount) * chooseGeometry(ctx, wordsPerWave, ld, colOff, out, ONE_TILE_WAVES_PER_CU, 4, outBytes).resident;
     const uint64_t pipelineFrom = 2 * usualRound >= 3 * R ? std::min<uint64_t>(2 * R, usualRound) : 2 * R;
     if (plan->fine) {
         wordsPerWave = WAVE / ctx->fineLanes;
@@ -749,12 +756,12 @@ int planTrained(
     // (Batch 7, the 8-bit Student-t model, 21 resident in blocks of seven against 24: seven -2.0 % shuffled, +1.2 % key order.)
     uint32_t unorderedWaves = ctx->recordPieces >= 10 ? 7u : 4u;
     if (unorderedWaves == 7 && !ctx->switches.waves &&
-        chooseGeometry(ctx, wordsPerWave, ld, colOff, out, ONE_TILE_WAVES_PER_CU, 7).resident <=
-            chooseGeometry(ctx, wordsPerWave, ld, colOff, out, ONE_TILE_WAVES_PER_CU, 8).resident) {
+        chooseGeometry(ctx, wordsPerWave, ld, colOff, out, ONE_TILE_WAVES_PER_CU, 7, outBytes).resident <=
+            chooseGeometry(ctx, wordsPerWave, ld, colOff, out, ONE_TILE_WAVES_PER_CU, 8, outBytes).resident) {
         unorderedWaves = 8;
     }
     const uint32_t preferred = !plan->persistent && tiles > 16 * R ? (randomOrder ? unorderedWaves : 8u) : 4u;
-    plan->geometry = chooseGeometry(ctx, wordsPerWave, ld, colOff, out, ONE_TILE_WAVES_PER_CU, preferred);
+    plan->geometry = chooseGeometry(ctx, wordsPerWave, ld, colOff, out, ONE_TILE_WAVES_PER_CU, preferred, outBytes);
     if (keysOut) {
         plan->geometry.mode = OUT_KEYS;
     }
@@ -775,7 +782,7 @@ int planTrained(
     }
     if (plan->fine && !plan->geometry.waves) {   // (cannot happen: fewer words per wavefront need less LDS)
         plan->fine = false;
-        return planTrained(ctx, n, ld, colOff, out, keysOut, plan, force, false, randomOrder);
+        return planTrained(ctx, n, ld, colOff, out, keysOut, plan, force, false, randomOrder, outBytes);
     }
     return MEMB_HIP_OK;
 }
@@ -1260,6 +1267,140 @@ int launchFull(
     hipError_t status = hipGetLastError();
     if (status != hipSuccess) {
         return fail(MEMB_HIP_ERR_DEVICE, std::string("gather_full launch: ") + hipGetErrorString(status));
+    }
+    return MEMB_HIP_OK;
+}
+
+// ---- bf16 / fp16 rows (memb_hip_decode_rows_device_typed; the kernels: memb_hip_narrow.hip) ----
+
+// How decode_trained_narrow writes rows of dim 2-byte values to out + row * ld + colOff (ld, colOff in elements):
+// OUT_FLAT = 16-byte stores of 8 values over a tile's rows back to back, where every tile starts 16-byte aligned (dim a
+// multiple of 8, or an even number of words per tile); OUT_VEC4 = 8-byte stores of 4 values, row by row; else one value
+// per store.
+int narrowOutputMode(uint32_t dim, size_t ld, size_t colOff, const void* out, uint32_t wordsPerWave)
+{
+    if (dim % 4 != 0 || ld % 4 != 0 || colOff % 4 != 0 || reinterpret_cast<uintptr_t>(out) % 8 != 0) {
+        return OUT_SCALAR;
+    }
+    const bool dense = ld == dim && colOff == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
+    return dense && (dim % 8 == 0 || wordsPerWave % 2 == 0) ? OUT_FLAT : OUT_VEC4;
+}
+
+// launchKernel for a kernel known by its address (the narrow kernels live in another translation unit): `params` is the
+// kernel's one argument.
+hipError_t launchKernelAt(const void* kernel, dim3 grid, dim3 block, uint32_t ldsBytes, hipStream_t stream, void* params)
+{
+    static thread_local std::unordered_map<const void*, int> configuredDevice;
+    if (!kernel) {
+        return hipErrorInvalidDeviceFunction;
+    }
+    int device = 0;
+    (void)hipGetDevice(&device);
+    int& configured = configuredDevice.try_emplace(kernel, -1).first->second;
+    if (configured != device) {
+        KernelFacts facts;
+        hipError_t status = kernelFacts(kernel, &facts);
+        if (status != hipSuccess) {
+            return status;
+        }
+        configured = device;
+    }
+    void* arguments[] = {params};
+    hipError_t status = hipLaunchKernel(kernel, grid, block, arguments, ldsBytes, stream);
+    return status != hipSuccess ? status : hipGetLastError();
+}
+
+// decode_trained_narrow: planned like decode_trained (planTrained), with half the codebook in LDS. Its instances keep
+// decode_trained's registers -- seven wavefronts per SIMD, ONE_TILE_WAVES_PER_CU (tests/test_narrow_isa.py) -- and it runs
+// at every batch size: no narrow decode_records_persistent. The batch-order word is read for the
+// block size, never written: a bf16 batch does not change what the next fp32 one picks.
+int launchNarrowTrained(
+    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, void* out, int outType, size_t ld, size_t colOff, hipStream_t stream)
+{
+    TrainedPlan plan;
+    const int planned = planTrained(ctx, n, ld, colOff, nullptr, false, &plan, 0, true, rowsUnordered(ctx, false), 2);
+    if (planned != MEMB_HIP_OK) {
+        return planned;
+    }
+    const TrainedGeometry geometry = plan.geometry;
+    if (!geometry.waves) {
+        return fail(MEMB_HIP_ERR_INVALID, "decode tables and bitstream slots do not fit into LDS");
+    }
+    TrainedParams params = lookupParams(ctx, plan.fine);
+    params.codebookDwords = codebookDwords(ctx) / 2;
+    params.rows = rows;
+    params.out = static_cast<float*>(out);   // (2-byte elements: outputTileNarrow)
+    params.n = n;
+    params.ld = ld;
+    params.colOff = colOff;
+    if (!lookupParamsConsistent(ctx, params, geometry) || ld < colOff + params.dim) {
+        return fail(MEMB_HIP_ERR_INVALID, "internal error: inconsistent decode geometry");
+    }
+    const uint32_t wordsPerWave = params.wordsPerWave;
+    const int mode = narrowOutputMode(ctx->dim, ld, colOff, out, wordsPerWave);
+    const void* kernel = memb_narrow::trainedKernel(lookupHasSub(ctx), mode, ctx->fast, outType);
+    const size_t tiles = (n + wordsPerWave - 1) / wordsPerWave;
+    params.tilesPerWave = oneTileSteps(ctx, tiles, 4u * (params.tableDwords + params.codebookDwords), false);
+    const size_t perBlock = size_t(geometry.waves) * params.tilesPerWave;
+    const uint32_t blocks = static_cast<uint32_t>((tiles + perBlock - 1) / perBlock);
+    const uint32_t ldsBytes = std::min<uint32_t>(geometry.ldsBytes + ctx->switches.ldsPad, 160 * 1024);
+    const hipError_t status = launchKernelAt(kernel, dim3(blocks), dim3(geometry.waves * WAVE), ldsBytes, stream, &params);
+    if (status != hipSuccess) {
+        return fail(MEMB_HIP_ERR_DEVICE, std::string("decode_trained_narrow launch: ") + hipGetErrorString(status));
+    }
+    return MEMB_HIP_OK;
+}
+
+// dequant_uniform_narrow / gather_full_narrow: the block kernels' geometry (launchUniform, launchFull), four values per
+// 8-byte store where rows allow it.
+int launchNarrowRowwise(
+    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, void* out, int outType, size_t ld, size_t colOff, hipStream_t stream)
+{
+    const bool vec = ctx->dim % 4 == 0 && ld % 4 == 0 && colOff % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0;
+    const uint32_t wordsPerBlock = rowwiseWordsPerBlock(ctx->dim);
+    const uint32_t pieceMagic = vec ? magicFor(ctx->dim / 4, uint64_t(wordsPerBlock) * (ctx->dim / 4)) : 0u;
+    const uint32_t blocks = static_cast<uint32_t>((n + wordsPerBlock - 1) / wordsPerBlock);
+    UniformParams uniform{};
+    FullParams full{};
+    const void* kernel;
+    void* params;
+    if (ctx->storage == memb::wire::Storage_Uniform) {
+        uniform.rows = rows;
+        uniform.out = static_cast<float*>(out);
+        uniform.n = n;
+        uniform.ld = ld;
+        uniform.colOff = colOff;
+        uniform.records = ctx->uniformRecords;
+        uniform.regionPieces = ctx->regionPieces;
+        uniform.nRows = ctx->nRows;
+        uniform.dim = ctx->dim;
+        uniform.wordsPerBlock = wordsPerBlock;
+        uniform.pieceMagic = pieceMagic;
+        uniform.levels = ctx->levels;
+        kernel = memb_narrow::uniformKernel(vec, outType);
+        params = &uniform;
+    } else {
+        full.rows = rows;
+        full.out = static_cast<float*>(out);
+        full.n = n;
+        full.ld = ld;
+        full.colOff = colOff;
+        full.values = ctx->fullValues;
+        full.nRows = ctx->nRows;
+        full.dim = ctx->dim;
+        full.wordsPerBlock = wordsPerBlock;
+        full.pieceMagic = pieceMagic;
+        kernel = memb_narrow::fullKernel(vec, outType);
+        params = &full;
+    }
+    void* arguments[] = {params};
+    hipError_t status = kernel ? hipLaunchKernel(kernel, dim3(blocks), dim3(ROWWISE_THREADS), arguments, 0, stream)
+                               : hipErrorInvalidDeviceFunction;
+    if (status == hipSuccess) {
+        status = hipGetLastError();
+    }
+    if (status != hipSuccess) {
+        return fail(MEMB_HIP_ERR_DEVICE, std::string("narrow row-wise launch: ") + hipGetErrorString(status));
     }
     return MEMB_HIP_OK;
 }
@@ -2246,6 +2387,45 @@ int decode_rows_device_ex_checked(
     return launch(ctx, rows, n, out, ld, col_off, static_cast<hipStream_t>(stream), epilogue);
 }
 
+int decode_rows_device_typed_checked(
+    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, void* out, int outType, size_t ld, size_t col_off, void* stream)
+{
+    if (outType != MEMB_HIP_OUT_F32 && outType != MEMB_HIP_OUT_BF16 && outType != MEMB_HIP_OUT_F16) {
+        return fail(MEMB_HIP_ERR_INVALID, "unknown out_type " + std::to_string(outType));
+    }
+    if (!ctx || (n && (!rows || !out))) {
+        return fail(MEMB_HIP_ERR_INVALID, "null argument");
+    }
+    const size_t elementBytes = outType == MEMB_HIP_OUT_F32 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(out) % elementBytes != 0) {
+        return fail(MEMB_HIP_ERR_INVALID, "out must be aligned to its element (" + std::to_string(elementBytes) + " bytes)");
+    }
+    if (col_off > ld || ld - col_off < ctx->dim) {
+        return fail(MEMB_HIP_ERR_INVALID, "ld must be at least col_off + dim");
+    }
+    if (outType == MEMB_HIP_OUT_F32) {
+        return decode_rows_device_checked(ctx, rows, n, static_cast<float*>(out), ld, col_off, stream);
+    }
+    if (n == 0) {
+        return MEMB_HIP_OK;
+    }
+    if (n > (size_t(1) << 37)) {
+        return fail(MEMB_HIP_ERR_INVALID, "batch too large");
+    }
+    DeviceScope deviceScope(ctx->device);
+    HIP_TRY(deviceScope.status());
+    const hipStream_t hipStream = static_cast<hipStream_t>(stream);
+    switch (ctx->storage) {
+        case memb::wire::Storage_Trained:
+            return launchNarrowTrained(ctx, rows, n, out, outType, ld, col_off, hipStream);
+        case memb::wire::Storage_Uniform:
+        case memb::wire::Storage_Full:
+            return launchNarrowRowwise(ctx, rows, n, out, outType, ld, col_off, hipStream);
+        default:
+            return fail(MEMB_HIP_ERR_INVALID, "context has no storage");
+    }
+}
+
 int decode_batches_device_checked(memb_hip_ctx* ctx, const memb_hip_batch* batches, size_t count, void* stream)
 {
     if (!ctx || (count && !batches)) {
@@ -2628,6 +2808,12 @@ int memb_hip_decode_rows_device(memb_hip_ctx* ctx, const uint32_t* rows, size_t 
 int memb_hip_decode_rows_device_ex(memb_hip_ctx* ctx, const uint32_t* rows, size_t n, float* out, size_t ld, size_t col_off, void* stream, uint32_t flags, float divisor)
 {
     return guarded([&] { return decode_rows_device_ex_checked(ctx, rows, n, out, ld, col_off, stream, flags, divisor); });
+}
+
+int memb_hip_decode_rows_device_typed(
+    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, void* out, int out_type, size_t ld, size_t col_off, void* stream)
+{
+    return guarded([&] { return decode_rows_device_typed_checked(ctx, rows, n, out, out_type, ld, col_off, stream); });
 }
 
 int memb_hip_decode_batches_device(memb_hip_ctx* ctx, const memb_hip_batch* batches, size_t count, void* stream)

@@ -450,6 +450,12 @@ void Reader::rowsToDeviceBuffer(
     compressedStorage_->decodeRowsDevice(rows, n, buffer, ld, colOff, stream, accumulate, divisor, randomOrder);
 }
 
+void Reader::rowsToDeviceBufferTyped(
+    const uint32_t* rows, size_t n, void* buffer, int outType, size_t ld, size_t colOff, void* stream) const
+{
+    compressedStorage_->decodeRowsDeviceTyped(rows, n, buffer, outType, ld, colOff, stream);
+}
+
 std::vector<float> Reader::wordEmbedding(const std::string& word) const
 {
     std::vector<float> result(dim());

@@ -111,6 +111,9 @@ public:
     void rowsToDeviceBuffer(
         const uint32_t* rows, size_t n, float* buffer, size_t ld, size_t colOff, void* stream,
         bool accumulate = false, float divisor = 0.f, bool randomOrder = false) const;
+    // Device rows of bf16 / fp16 / fp32 (include/memb_hip_narrow.h); ld and colOff count elements of outType.
+    void rowsToDeviceBufferTyped(
+        const uint32_t* rows, size_t n, void* buffer, int outType, size_t ld, size_t colOff, void* stream) const;
 
     // Several device-buffer lookups in one kernel launch (include/memb_hip.h: memb_hip_decode_batches_device).
     void batchesToDeviceBuffers(const memb_hip_batch* batches, size_t count, void* stream) const;

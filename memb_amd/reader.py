@@ -237,33 +237,50 @@ class Reader(BaseReader):
         '''Write the batch into columns [col_off, col_off + dim) of a wider float32 matrix'''
         self._impl.batch_embedding_into(words, out, col_off)
 
-    def rows_embedding_device(self, rows, out=None, col_off=0, accumulate=False, divisor=0.0, order=None):
+    def rows_embedding_device(self, rows, out=None, col_off=0, accumulate=False, divisor=0.0, order=None, dtype=None):
         '''Lookup that never leaves the GPU.
         Parameters
         ----------
         rows : torch.Tensor (int32 view of the uint32 row ids, on this reader's device)
-        out : torch.Tensor float32 (n, >= col_off + dim) on the same device, optional
-        accumulate : add the rows to what `out` holds instead of overwriting it
-        divisor : if non-zero, divide the (accumulated) rows by it
+        out : torch.Tensor of `dtype`, (n, >= col_off + dim) on the same device, optional
+        accumulate : add the rows to what `out` holds instead of overwriting it (float32 only)
+        divisor : if non-zero, divide the (accumulated) rows by it (float32 only)
         order : None, or 'random' -- a hint that the rows come in no particular order (token ids, shuffled keys): batches
             of more than 524 000 rows then keep blocks of four wavefronts, 3 % faster for such rows (key-order dumps like
             the default of eight). Never changes a result.
+        dtype : torch.float32, torch.bfloat16 or torch.float16; default out.dtype, else float32. bf16 / fp16 rows are the
+            float32 rows rounded once to nearest even (the bits of .to(dtype)), decoded straight into that type: no float32
+            temporary, no second kernel.
         '''
         # (a small batch is seven microseconds of which the kernel is three: every attribute is fetched once)
         import torch
         device = rows.device
         if device.type != 'cuda' or rows.dtype not in (torch.int32, torch.uint32) or not rows.is_contiguous():
             raise TypeError('rows must be a contiguous int32/uint32 tensor on the GPU')
+        if dtype is None:
+            dtype = torch.float32 if out is None else out.dtype
+        elif out is not None and out.dtype != dtype:
+            raise TypeError('out is {} but dtype is {}'.format(out.dtype, dtype))
+        if dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise TypeError('out must be a float32, bfloat16 or float16 (n, width) tensor with unit column stride')
+        narrow = dtype != torch.float32
+        if narrow and (accumulate or divisor):
+            raise ValueError('accumulate and divisor need float32 rows: a {} sum would be rounded after every reader'.format(dtype))
         n = rows.numel()
         if out is None:
-            out = torch.empty((n, col_off + self.dim), dtype=torch.float32, device=device)
-        if out.dtype != torch.float32 or out.dim() != 2 or out.stride(1) != 1 or out.shape[0] != n:
-            raise TypeError('out must be a float32 (n, width) tensor with unit column stride')
+            out = torch.empty((n, col_off + self.dim), dtype=dtype, device=device)
+        if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] != n:
+            raise TypeError('out must be a {} (n, width) tensor with unit column stride'.format(dtype))
         # the kernel runs on this reader's device with these pointers: both tensors must live there
         index = device.index
         if index != self._impl.device() or out.device != device:
             raise ValueError('rows and out must be on cuda:{} (the device this reader is staged on), got {} and {}'.format(
                 self.device, device, out.device))
+        if narrow:
+            self._impl.rows_to_device_typed(
+                rows.data_ptr(), n, out.data_ptr(), _memb.OUT_BF16 if dtype == torch.bfloat16 else _memb.OUT_F16,
+                out.stride(0), col_off, _current_stream(torch, index))
+            return out
         self._impl.rows_to_device(
             rows.data_ptr(), n, out.data_ptr(), out.stride(0), col_off, _current_stream(torch, index), accumulate, float(divisor),
             order == 'random')
@@ -340,11 +357,11 @@ class Reader(BaseReader):
             self._word_batches.give(batch)
         return out
 
-    def batch_embedding_device(self, words):
+    def batch_embedding_device(self, words, dtype=None):
         '''batch_embedding with the result left on the GPU as a torch.Tensor (DLPack capable). Words are resolved on
         the GPU as well (resolve_rows_device): the only host work is packing the strings. May be called from several
-        threads at once.'''
-        return self.rows_embedding_device(self.resolve_rows_device(words))
+        threads at once. dtype: torch.float32 (default), torch.bfloat16 or torch.float16 (rows_embedding_device).'''
+        return self.rows_embedding_device(self.resolve_rows_device(words), dtype=dtype)
 
     def rows_embedding_device_many(self, batches):
         '''Several lookups in ONE kernel launch (memb_hip_decode_batches_device): `batches` is a sequence of
@@ -374,11 +391,11 @@ class Reader(BaseReader):
         self._impl.batches_to_device(descriptors, _current_stream(torch, index))
         return outs
 
-    def tokenizer_embedding_device(self, tokenizer):
+    def tokenizer_embedding_device(self, tokenizer, dtype=None):
         '''tokenizer_embedding with the weights left on the GPU: a torch.Tensor that
         torch.nn.Embedding.from_pretrained (or any DLPack consumer) takes as is, so the
-        embedding matrix of a model never crosses PCIe'''
-        return self.batch_embedding_device(tokenizer_word_list(tokenizer))
+        embedding matrix of a model never crosses PCIe. dtype: as batch_embedding_device'''
+        return self.batch_embedding_device(tokenizer_word_list(tokenizer), dtype=dtype)
 
     def info(self, batch_words=0):
         '''Facts about the device context (stages the model on first call). The kernel and its launch geometry

@@ -16,6 +16,7 @@ import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip.hip')
+NARROW_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_narrow.hip')
 # the flags of build_native.build_hip_library
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt',
          '-Wno-unused-value', '-Wno-align-mismatch', '-Wno-pass-failed', '-Wno-unused-command-line-argument']
@@ -28,18 +29,19 @@ def _tool(name):
     raise RuntimeError(name + ' not found')
 
 
-def device_assembly(extra_flags=()):
+def device_assembly(extra_flags=(), source=SOURCE):
     with tempfile.TemporaryDirectory() as scratch:
         target = os.path.join(scratch, 'memb_hip.s')
-        subprocess.run([_tool('hipcc'), *FLAGS, *extra_flags, '--cuda-device-only', '-S', '-o', target, SOURCE],
+        subprocess.run([_tool('hipcc'), *FLAGS, *extra_flags, '--cuda-device-only', '-S', '-o', target, source],
                        check=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
         with open(target) as f:
             return f.read()
 
 
-def kernel_table(extra_flags=()):
-    """{demangled kernel name: facts} for every kernel of libmemb_hip.so"""
-    text = device_assembly(extra_flags)
+def kernel_table(extra_flags=(), source=SOURCE):
+    """{demangled kernel name: facts} for every kernel of one translation unit of libmemb_hip.so (default memb_hip.hip;
+    NARROW_SOURCE: the bf16 / fp16 kernels)"""
+    text = device_assembly(extra_flags, source)
     names = re.findall(r'^\s*\.amdhsa_kernel (\S+)$', text, flags=re.M)
     demangled = subprocess.run([_tool('c++filt')], input='\n'.join(names), stdout=subprocess.PIPE, text=True,
                                check=True).stdout.split('\n')
