@@ -251,12 +251,11 @@ def test_device_entry_point_can_be_captured_into_a_graph(native, make_model):
         assert bits_equal(out.cpu().numpy(), expected)
 
 
-def test_arbitrary_prefix_codes_through_the_c_abi(native):
-    # Storages the reference's writer cannot produce (its k-means prunes rare clusters, which bounds
-    # the code lengths): random complete prefix codes with up to 255 symbols and code lengths up to
-    # 16 bits -- the format's maximum, PrefixCode::code is a uint16 (reference src/prefix_code.h:10-13)
-    # -- handed to the C ABI as a crafted description, for several first-level table widths and
-    # batch sizes on both sides of the small-batch threshold. Expected rows: the symbols themselves.
+def prefix_code_contexts(native):
+    """The models of test_arbitrary_prefix_codes_through_the_c_abi, one C-ABI context per (storage, first-level width):
+    yields (library, context, label, dim, n_rows, expected, rng, longest) -- `expected` the (n_rows, dim) fp32 rows (the
+    centroids of the symbols drawn), `longest` the longest code of any storage so far -- and destroys the context when
+    the caller comes back for the next one."""
     import ctypes
     from test_oracle_vs_reference import random_code
     library = ctypes.CDLL(native.HIP_LIBRARY_PATH)
@@ -303,17 +302,29 @@ def test_arbitrary_prefix_codes_through_the_c_abi(native):
             context = ctypes.c_void_p()
             assert library.memb_hip_ctx_create_trained(ctypes.byref(context), 0, ctypes.byref(desc)) == 0, \
                 library.memb_hip_last_error()
-            for count in (n_rows, min(n_rows, 100)):
-                ids = rng.permutation(n_rows)[:count].astype(np.uint32)
-                ids[::7] = 0xFFFFFFFF
-                out = np.full((count, dim), 5.0, dtype=np.float32)
-                code = library.memb_hip_decode_rows(
-                    context, ids.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(count),
-                    out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(dim), ctypes.c_size_t(0))
-                assert code == 0, library.memb_hip_last_error()
-                want = np.where((ids == 0xFFFFFFFF)[:, None], np.float32(0), expected[np.minimum(ids, n_rows - 1)])
-                assert bits_equal(out, want), (trial, symbols, dim, max_direct_bits, count, max(lengths))
+            yield library, context, (trial, symbols, dim, max_direct_bits, max(lengths)), dim, n_rows, expected, rng, longest
             library.memb_hip_ctx_destroy(context)
+
+
+def test_arbitrary_prefix_codes_through_the_c_abi(native):
+    # Storages the reference's writer cannot produce (its k-means prunes rare clusters, which bounds
+    # the code lengths): random complete prefix codes with up to 255 symbols and code lengths up to
+    # 16 bits -- the format's maximum, PrefixCode::code is a uint16 (reference src/prefix_code.h:10-13)
+    # -- handed to the C ABI as a crafted description, for several first-level table widths and
+    # batch sizes on both sides of the small-batch threshold. Expected rows: the symbols themselves.
+    import ctypes
+    longest = 0
+    for library, context, label, dim, n_rows, expected, rng, longest in prefix_code_contexts(native):
+        for count in (n_rows, min(n_rows, 100)):
+            ids = rng.permutation(n_rows)[:count].astype(np.uint32)
+            ids[::7] = 0xFFFFFFFF
+            out = np.full((count, dim), 5.0, dtype=np.float32)
+            code = library.memb_hip_decode_rows(
+                context, ids.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(count),
+                out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(dim), ctypes.c_size_t(0))
+            assert code == 0, library.memb_hip_last_error()
+            want = np.where((ids == 0xFFFFFFFF)[:, None], np.float32(0), expected[np.minimum(ids, n_rows - 1)])
+            assert bits_equal(out, want), (label, count)
     assert longest >= 15
 
 
@@ -336,9 +347,8 @@ def test_very_wide_rows(native, tmp_path, dim, bits, count):
     assert bits_equal(reader.batch_embedding(many), checker.batch_embedding(many))
 
 
-def test_degenerate_models(native, tmp_path):
-    # one-symbol codes (every stream is empty), two-symbol codes, a single word, heavy tails,
-    # constant / subnormal / near-overflow uniform rows, special values in full storage, odd words
+def degenerate_cases():
+    """(storage, bits, words, vectors) of test_degenerate_models"""
     rng = np.random.default_rng(0)
     words = ['w%04d' % i for i in range(300)]
     special = rng.standard_normal((300, 40)).astype(np.float32)
@@ -358,7 +368,13 @@ def test_degenerate_models(native, tmp_path):
         ('full', 8, words, special),
         ('trained', 4, ['\u00e9t\u00e9', '\u65e5\u672c', 'a b', '', '\U0001F600', 'z' * 300], rng.standard_normal((6, 8)).astype(np.float32)),
     ]
-    for index, (storage, bits, names, vectors) in enumerate(cases):
+    return cases
+
+
+def test_degenerate_models(native, tmp_path):
+    # one-symbol codes (every stream is empty), two-symbol codes, a single word, heavy tails,
+    # constant / subnormal / near-overflow uniform rows, special values in full storage, odd words
+    for index, (storage, bits, names, vectors) in enumerate(degenerate_cases()):
         path = str(tmp_path / 'degenerate_{}.bin'.format(index))
         builder = native.Builder(vectors.shape[1], storage, bits)
         builder.add_words(names, vectors)
