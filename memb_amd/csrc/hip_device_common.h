@@ -1,7 +1,7 @@
 // Helpers shared by all kernels: magic division, wave-level LDS fence, single-lane-op IEEE arithmetic, the accumulate / divide epilogue.
 //
-// Device code of libmemb_hip.so (gfx950 / CDNA4). Included by memb_hip.hip only,
-// inside its anonymous namespace; see that file for the overview.
+// Device code of libmemb_hip.so (gfx950 / CDNA4). Included by memb_hip.hip and memb_hip_narrow.hip,
+// inside their anonymous namespaces; see memb_hip.hip for the overview.
 #pragma once
 
 // q / d with a host-computed magic = ceil(2^32 / d) (exact while q * d < 2^32);

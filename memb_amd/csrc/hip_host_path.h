@@ -261,8 +261,9 @@ int decodeRowsAsKeys(
     const size_t rowBytes = keyRowBytes(ctx);
     const bool streaming = ctx->switches.hostStreaming == 2 ||
         (ctx->switches.hostStreaming == 1 && words * ctx->dim * sizeof(float) >= (size_t(64) << 20));
-    int code = launchTrained(
-        ctx, deviceRowIds, words, reinterpret_cast<float*>(deviceKeys), ctx->dim, 0, ctx->stream, Epilogue(), true);
+    Lookup keys = floatRows(deviceRowIds, words, reinterpret_cast<float*>(deviceKeys), ctx->dim, 0);
+    keys.keysOut = true;
+    int code = launchTrained(ctx, keys, ctx->stream);
     if (code != MEMB_HIP_OK) {
         return code;
     }

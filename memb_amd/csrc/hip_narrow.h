@@ -1,5 +1,5 @@
-// The kernels of memb_hip_narrow.hip (bf16 / fp16 rows) as memb_hip.hip launches them: host addresses for
-// hipLaunchKernel / hipFuncGetAttributes. Their parameters are the TrainedParams / UniformParams / FullParams of the device
+// The kernels of memb_hip_narrow.hip (bf16 / fp16 rows) as memb_hip.hip launches them (launchKernelAddress, launchRowwise):
+// host addresses for hipLaunchKernel / hipFuncGetAttributes. Their parameters are the TrainedParams / UniformParams / FullParams of the device
 // headers, which both translation units include.
 #pragma once
 

@@ -1,7 +1,7 @@
 // dequant_uniform / gather_full: one 16-byte piece of an output row per lane.
 //
-// Device code of libmemb_hip.so (gfx950 / CDNA4). Included by memb_hip.hip only,
-// inside its anonymous namespace; see that file for the overview.
+// Device code of libmemb_hip.so (gfx950 / CDNA4). Included by memb_hip.hip and memb_hip_narrow.hip,
+// inside their anonymous namespaces; see memb_hip.hip for the overview.
 #pragma once
 
 // ---------------------------------------------------------------------------

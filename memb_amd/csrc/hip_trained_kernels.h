@@ -1,8 +1,8 @@
 // decode_trained / decode_records_persistent / decode_union_split / decode_trained_union / repack_streams:
 // canonical-Huffman bitstream decode + codebook gather.
 //
-// Device code of libmemb_hip.so (gfx950 / CDNA4). Included by memb_hip.hip only,
-// inside its anonymous namespace; see that file for the overview.
+// Device code of libmemb_hip.so (gfx950 / CDNA4). Included by memb_hip.hip and memb_hip_narrow.hip,
+// inside their anonymous namespaces; see memb_hip.hip for the overview.
 #pragma once
 
 // ---------------------------------------------------------------------------

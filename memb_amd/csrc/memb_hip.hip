@@ -30,8 +30,10 @@
 //
 // Files: hip_device_common.h, hip_trained_kernels.h, hip_rowwise_kernels.h -- device
 // code; this file -- context, staging of a model to HBM, launch geometry, the C
-// ABI; hip_host_path.h -- how rows reach host buffers (pinned ring, copy threads,
-// centroid indices over PCIe).
+// ABI; memb_hip_narrow.hip -- the bf16 / fp16 kernels, a translation unit of its own
+// that includes the same device headers and hands its kernels over as addresses
+// (hip_narrow.h), planned and launched here; hip_host_path.h -- how rows reach host
+// buffers (pinned ring, copy threads, centroid indices over PCIe).
 #include <hip/hip_runtime.h>
 
 #include "../../include/memb_hip.h"
@@ -294,14 +296,47 @@ uint32_t trainedLdsBytes(const memb_hip_ctx* ctx, uint32_t waves, uint32_t words
     return 4u * (ctx->tableDwords + codebook + waves * perWave);
 }
 
-// How a kernel writes rows of dim floats to out + row * ld + colOff: in 16-byte pieces where every row starts 16-byte
-// aligned, as one dense run of pieces where the rows lie back to back, else one float at a time.
-int outputMode(uint32_t dim, size_t ld, size_t colOff, const void* out)
+// How a kernel writes rows of dim elements of elementBytes (4: fp32, 2: bf16 / fp16) to out + row * ld + colOff (ld and
+// colOff in elements). The two rules side by side:
+//   OUT_VEC4  pieces of four elements, row by row (16- / 8-byte stores): dim, ld and colOff multiples of four and `out`
+//             aligned to a piece; else OUT_SCALAR, one element per store
+//   OUT_FLAT  one dense run of 16-byte pieces where the rows lie back to back (ld == dim, colOff == 0). 4-byte elements:
+//             nothing more to ask. 2-byte elements: 16 bytes are eight values, so `out` must be 16-byte aligned and every
+//             tile of wordsPerWave rows must start on such a boundary -- dim a multiple of 8, or an even number of words
+//             per tile. (The row-wise kernels only ask whether the answer is OUT_SCALAR: wordsPerWave 0.)
+int outputMode(uint32_t dim, size_t ld, size_t colOff, const void* out, uint32_t elementBytes, uint32_t wordsPerWave)
 {
-    if (dim % 4 != 0 || ld % 4 != 0 || colOff % 4 != 0 || reinterpret_cast<uintptr_t>(out) % 16 != 0) {
+    const uintptr_t address = reinterpret_cast<uintptr_t>(out);
+    if (dim % 4 != 0 || ld % 4 != 0 || colOff % 4 != 0 || address % (4 * elementBytes) != 0) {
         return OUT_SCALAR;
     }
-    return ld == dim && colOff == 0 ? OUT_FLAT : OUT_VEC4;
+    bool dense = ld == dim && colOff == 0;
+    if (elementBytes == 2) {
+        dense = dense && address % 16 == 0 && (dim % 8 == 0 || wordsPerWave % 2 == 0);
+    }
+    return dense ? OUT_FLAT : OUT_VEC4;
+}
+
+// What a caller asks of a decode launch: rows[0 .. n) as rows of outType elements (MEMB_HIP_OUT_*) at out + i * ld + colOff
+// (ld, colOff in elements); fp32 rows may pass through the epilogue of a union (hip_device_common.h: accumulate, divide).
+struct Lookup {
+    const uint32_t* rows = nullptr;
+    size_t n = 0;
+    void* out = nullptr;
+    int outType = MEMB_HIP_OUT_F32;
+    size_t ld = 0;
+    size_t colOff = 0;
+    uint32_t accumulate = 0;
+    float divisor = 0.f;
+    bool randomOrder = false;   // the caller's hint MEMB_HIP_ROWS_IN_RANDOM_ORDER (launch geometry only)
+    bool keysOut = false;       // trained: `out` receives rows of centroid indices (OUT_KEYS) instead; ld = dim, colOff = 0
+
+    uint32_t elementBytes() const { return outType == MEMB_HIP_OUT_F32 ? 4u : 2u; }
+};
+
+Lookup floatRows(const uint32_t* rows, size_t n, float* out, size_t ld, size_t colOff)
+{
+    return Lookup{rows, n, out, MEMB_HIP_OUT_F32, ld, colOff};
 }
 
 // Wavefronts a CU holds in blocks of `waves` with ldsBytes of LDS each (0: the block does not fit). LDS is handed out in
@@ -324,9 +359,10 @@ uint32_t residentWaves(uint32_t ldsLimit, uint32_t waves, uint32_t ldsBytes, uin
 // fit: the size with the most resident wavefronts, in the order 4, 8, 2, 1. MEMB_HIP_WAVES / option waves_per_block forces a
 // size. registerWavesPerCu: how many wavefronts of the kernel about to be launched its registers let a CU hold (32 when
 // unknown): a block size whose LDS would allow more resident wavefronts than the registers do gains nothing by it.
+// outBytes: of the output element, whose codebook the kernel holds in LDS. (`mode` is not set here: planTrained.)
 TrainedGeometry chooseGeometry(
-    const memb_hip_ctx* ctx, uint32_t wordsPerWave, size_t ld, size_t colOff, const float* out,
-    uint32_t registerWavesPerCu = ONE_TILE_WAVES_PER_CU, uint32_t preferred = 4, uint32_t outBytes = 4)
+    const memb_hip_ctx* ctx, uint32_t wordsPerWave, uint32_t outBytes, uint32_t preferred = 4,
+    uint32_t registerWavesPerCu = ONE_TILE_WAVES_PER_CU)
 {
     TrainedGeometry best{};
     const uint32_t forcedWaves = ctx->switches.waves;   // (1 .. 16; anything but 1, 2, 4, 8: measurements)
@@ -356,7 +392,6 @@ TrainedGeometry chooseGeometry(
         best.ldsBytes = preferredLds;
         best.resident = preferredResident;
     }
-    best.mode = outputMode(ctx->dim, ld, colOff, out);
     return best;
 }
 
@@ -536,13 +571,13 @@ hipError_t kernelFacts(void (*kernel)(A...), KernelFacts* out, uint32_t threads 
     return kernelFacts(reinterpret_cast<const void*>(kernel), out, threads, ldsBytes);
 }
 
-// Enqueues kernel<<<grid, block, ldsBytes, stream>>>(args...) -- every kernel with dynamic LDS is launched here. The first
-// launch of a kernel on a device in a thread goes through kernelFacts, which raises its LDS limit; after that the check is
-// one lookup in this thread's own table, no lock: the latency of a single word is on this path.
-template <typename... A>
-hipError_t launchKernel(void (*kernel)(A...), dim3 grid, dim3 block, uint32_t ldsBytes, hipStream_t stream, A... args)
+// Enqueues kernel<<<grid, block, ldsBytes, stream>>>(*arguments[0], ...) -- every kernel with dynamic LDS is launched here,
+// the narrow ones of memb_hip_narrow.hip, known by their addresses, included. The first launch of a kernel on a device in a
+// thread goes through kernelFacts, which raises its LDS limit; after that the check is one lookup in this thread's own
+// table, no lock: the latency of a single word is on this path.
+hipError_t launchKernelAddress(const void* kernel, dim3 grid, dim3 block, uint32_t ldsBytes, hipStream_t stream, void** arguments)
 {
-    static thread_local std::unordered_map<void (*)(A...), int> configuredDevice;
+    static thread_local std::unordered_map<const void*, int> configuredDevice;
     if (!kernel) {
         return hipErrorInvalidDeviceFunction;
     }
@@ -557,8 +592,16 @@ hipError_t launchKernel(void (*kernel)(A...), dim3 grid, dim3 block, uint32_t ld
         }
         configured = device;
     }
-    hipLaunchKernelGGL(kernel, grid, block, ldsBytes, stream, args...);
-    return hipGetLastError();
+    const hipError_t status = hipLaunchKernel(kernel, grid, block, arguments, ldsBytes, stream);
+    return status != hipSuccess ? status : hipGetLastError();
+}
+
+// The kernels of this translation unit: argument types checked against the kernel's.
+template <typename... A>
+hipError_t launchKernel(void (*kernel)(A...), dim3 grid, dim3 block, uint32_t ldsBytes, hipStream_t stream, A... args)
+{
+    void* arguments[] = {&args...};
+    return launchKernelAddress(reinterpret_cast<const void*>(kernel), grid, block, ldsBytes, stream, arguments);
 }
 
 TrainedParams baseTrainedParams(const memb_hip_ctx* ctx)
@@ -584,12 +627,6 @@ TrainedParams baseTrainedParams(const memb_hip_ctx* ctx)
     params.tilesPerWave = 1;
     return params;
 }
-
-struct Epilogue {
-    uint32_t accumulate = 0;
-    float divisor = 0.f;
-    bool randomOrder = false;   // the caller's hint MEMB_HIP_ROWS_IN_RANDOM_ORDER (launch geometry only)
-};
 
 // The parameters of a lookup kernel that do not depend on the batch. fine: decode with the finer index (more lanes per
 // word, fewer words per wavefront; memb_hip_ctx::fineIndex).
@@ -697,11 +734,13 @@ bool rowsUnordered(const memb_hip_ctx* ctx, bool callerSaysRandom)
 // +2.5 %, +2.7 %, +2.1 %: the rule takes the dump's side for every key format and says what it costs the other order
 // (HISTORY.md, "(r5) 5.0", has the table; DESIGN.md section 5.0 the rule as it stands). The 8-bit model runs blocks of eight at every size: chooseGeometry.
 // force: -1 = by the rule, 0 = one tile per wavefront, 1 = decode_records_persistent where the layout allows.
-// outBytes: of the output element (2: decode_trained_narrow, whose codebook takes half the LDS)
-int planTrained(
-    const memb_hip_ctx* ctx, size_t n, size_t ld, size_t colOff, const float* out, bool keysOut, TrainedPlan* plan, int force = -1,
-    bool mayBeFine = true, bool randomOrder = false, uint32_t outBytes = 4)
+// mayBeFine: whether the finer index may be chosen at all. randomOrder: rowsUnordered's answer (very large batches).
+// Of the lookup, its size, the shape of its output (-> geometry.mode) and the size of its elements count: 2-byte ones
+// (decode_trained_narrow) take half the LDS for the codebook.
+int planTrained(const memb_hip_ctx* ctx, const Lookup& lookup, int force, bool mayBeFine, bool randomOrder, TrainedPlan* plan)
 {
+    const size_t n = lookup.n;
+    const uint32_t outBytes = lookup.elementBytes();
     uint32_t wordsPerWave = WAVE / ctx->lanesPerWord;
     const uint64_t tiles = (n + wordsPerWave - 1) / wordsPerWave;
     const uint64_t R = uint64_t(ctx->cuCount) * PIPELINE_WAVES_PER_CU;
@@ -725,13 +764,13 @@ int planTrained(
         const uint32_t fineWords = WAVE / ctx->fineLanes;
         const uint64_t fineTiles = (n + fineWords - 1) / fineWords;
         const uint64_t fineRound =
-            uint64_t(ctx->cuCount) * chooseGeometry(ctx, fineWords, ld, colOff, out, ONE_TILE_WAVES_PER_CU, 4, outBytes).resident;
+            uint64_t(ctx->cuCount) * chooseGeometry(ctx, fineWords, outBytes).resident;
         fineByRule = fineTiles <= fineRound;
     }
     plan->fine = mayBeFine && ctx->fineIndex && force != 1 && (ctx->switches.fineLanes == 2 || fineByRule);
     // (models whose tables leave a CU fewer than 1.5 R wavefronts -- the 8-bit one -- keep the edge at 2 R: not measured there)
     const uint64_t usualRound =
-        uint64_t(ctx->cuCount) * chooseGeometry(ctx, wordsPerWave, ld, colOff, out, ONE_TILE_WAVES_PER_CU, 4, outBytes).resident;
+        uint64_t(ctx->cuCount) * chooseGeometry(ctx, wordsPerWave, outBytes).resident;
     const uint64_t pipelineFrom = 2 * usualRound >= 3 * R ? std::min<uint64_t>(2 * R, usualRound) : 2 * R;
     if (plan->fine) {
         wordsPerWave = WAVE / ctx->fineLanes;
@@ -756,16 +795,15 @@ int planTrained(
     // (Batch 7, the 8-bit Student-t model, 21 resident in blocks of seven against 24: seven -2.0 % shuffled, +1.2 % key order.)
     uint32_t unorderedWaves = ctx->recordPieces >= 10 ? 7u : 4u;
     if (unorderedWaves == 7 && !ctx->switches.waves &&
-        chooseGeometry(ctx, wordsPerWave, ld, colOff, out, ONE_TILE_WAVES_PER_CU, 7, outBytes).resident <=
-            chooseGeometry(ctx, wordsPerWave, ld, colOff, out, ONE_TILE_WAVES_PER_CU, 8, outBytes).resident) {
+        chooseGeometry(ctx, wordsPerWave, outBytes, 7).resident <= chooseGeometry(ctx, wordsPerWave, outBytes, 8).resident) {
         unorderedWaves = 8;
     }
     const uint32_t preferred = !plan->persistent && tiles > 16 * R ? (randomOrder ? unorderedWaves : 8u) : 4u;
-    plan->geometry = chooseGeometry(ctx, wordsPerWave, ld, colOff, out, ONE_TILE_WAVES_PER_CU, preferred, outBytes);
-    if (keysOut) {
-        plan->geometry.mode = OUT_KEYS;
-    }
-    plan->kernel = &lookupKernel(ctx, plan->persistent, plan->geometry.mode);
+    plan->geometry = chooseGeometry(ctx, wordsPerWave, outBytes, preferred);
+    // (the fp32 instance; a narrow lookup runs memb_narrow::trainedKernel of the same mode: launchTrained)
+    const int mode = lookup.keysOut ? OUT_KEYS : outputMode(ctx->dim, lookup.ld, lookup.colOff, lookup.out, outBytes, wordsPerWave);
+    plan->geometry.mode = mode;
+    plan->kernel = &lookupKernel(ctx, plan->persistent, mode);
     if (plan->persistent && plan->geometry.waves) {
         // again with what the kernel's registers allow (a block size whose LDS would hold more wavefronts than
         // the registers admit is no better than a smaller one)
@@ -776,49 +814,65 @@ int planTrained(
         }
         plan->registerWavesPerCu = facts.registerWavesPerCu;
         plan->numRegs = facts.numRegs;
-        const int mode = plan->geometry.mode;
-        plan->geometry = chooseGeometry(ctx, wordsPerWave, ld, colOff, out, plan->registerWavesPerCu);
+        plan->geometry = chooseGeometry(ctx, wordsPerWave, outBytes, 4, plan->registerWavesPerCu);
         plan->geometry.mode = mode;
     }
     if (plan->fine && !plan->geometry.waves) {   // (cannot happen: fewer words per wavefront need less LDS)
         plan->fine = false;
-        return planTrained(ctx, n, ld, colOff, out, keysOut, plan, force, false, randomOrder, outBytes);
+        return planTrained(ctx, lookup, force, false, randomOrder, plan);
     }
     return MEMB_HIP_OK;
 }
 
-// keysOut: `out` receives rows of centroid indices (OUT_KEYS) instead of fp32 rows; ld = dim, colOff = 0.
-// Enqueues one kernel on `stream` and returns.
-int launchTrained(
-    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, float* out, size_t ld, size_t colOff, hipStream_t stream,
-    const Epilogue& epilogue, bool keysOut = false, int force = -1)
+// Grid of a launch of the one-tile kernels over `tiles` tiles in blocks of `waves` wavefronts: sets params->tilesPerWave
+// (oneTileSteps) and *blocks.
+int oneTileBlocks(const memb_hip_ctx* ctx, uint64_t tiles, uint32_t waves, TrainedParams* params, uint32_t* blocks)
 {
+    params->tilesPerWave = oneTileSteps(ctx, tiles, 4u * (params->tableDwords + params->codebookDwords), false);
+    const uint64_t perBlock = uint64_t(waves) * params->tilesPerWave;
+    const uint64_t count = (tiles + perBlock - 1) / perBlock;
+    if (count >= 0x7FFFFFFFull) {
+        return fail(MEMB_HIP_ERR_INVALID, "batches too large for one launch");
+    }
+    *blocks = static_cast<uint32_t>(count);
+    return MEMB_HIP_OK;
+}
+
+// Enqueues one kernel on `stream` and returns. A narrow lookup (bf16 / fp16) runs decode_trained_narrow, planned like
+// decode_trained with half the codebook in LDS. Its instances keep decode_trained's registers -- seven wavefronts per
+// SIMD, ONE_TILE_WAVES_PER_CU (tests/test_narrow_isa.py) -- and it runs at every batch size: no narrow
+// decode_records_persistent (force = 0). The batch-order word is read for the block size, never
+// written: a bf16 batch does not change what the next fp32 one picks.
+int launchTrained(memb_hip_ctx* ctx, const Lookup& lookup, hipStream_t stream)
+{
+    const bool narrow = lookup.outType != MEMB_HIP_OUT_F32;
     TrainedPlan plan;
-    int planned = planTrained(ctx, n, ld, colOff, out, keysOut, &plan, force, true, rowsUnordered(ctx, epilogue.randomOrder));
+    int planned = planTrained(ctx, lookup, narrow ? 0 : -1, true, rowsUnordered(ctx, lookup.randomOrder), &plan);
     if (planned != MEMB_HIP_OK) {
         return planned;
     }
-    const uint32_t wordsPerWave = WAVE / (plan.fine ? ctx->fineLanes : ctx->lanesPerWord);
-    const bool persistent = plan.persistent;
-    TrainedGeometry geometry = plan.geometry;
+    const TrainedGeometry geometry = plan.geometry;
     if (!geometry.waves) {
         return fail(MEMB_HIP_ERR_INVALID, "decode tables and bitstream slots do not fit into LDS");
     }
     TrainedParams params = lookupParams(ctx, plan.fine);
-    params.rows = rows;
-    params.out = out;
-    params.n = n;
-    params.ld = ld;
-    params.colOff = colOff;
-    params.accumulate = epilogue.accumulate;
-    params.divisor = epilogue.divisor;
-    if (!lookupParamsConsistent(ctx, params, geometry) || ld < colOff + params.dim) {
+    if (narrow) {
+        params.codebookDwords = codebookDwords(ctx) / 2;
+    }
+    params.rows = lookup.rows;
+    params.out = static_cast<float*>(lookup.out);   // (2-byte elements for a narrow type: outputTileNarrow)
+    params.n = lookup.n;
+    params.ld = lookup.ld;
+    params.colOff = lookup.colOff;
+    params.accumulate = lookup.accumulate;
+    params.divisor = lookup.divisor;
+    if (!lookupParamsConsistent(ctx, params, geometry) || lookup.ld < lookup.colOff + params.dim) {
         return fail(MEMB_HIP_ERR_INVALID, "internal error: inconsistent decode geometry");
     }
-    const size_t tiles = (n + wordsPerWave - 1) / wordsPerWave;
+    const size_t tiles = (lookup.n + params.wordsPerWave - 1) / params.wordsPerWave;
     const uint32_t threads = geometry.waves * WAVE;
     hipError_t status;
-    if (persistent) {
+    if (plan.persistent) {
         // as many blocks as are resident at once; each wavefront strides over the tiles. (Round 5, batch 11: a grid cut down so
         // that every wavefront gets the SAME number of tiles -- 12 500 tiles as 4 167 wavefronts x 3 instead of 5 120 wavefronts
         // of which 44 % run a third round -- is slower: 100 000 uncached rows +10 % (4-bit), +15 % (6-bit, 2-bit). More wavefronts
@@ -831,20 +885,29 @@ int launchTrained(
             status = launchKernel(plan.kernel->fn, dim3(std::min(tileBlocks, resident)), dim3(threads), geometry.ldsBytes, stream, params);
         }
     } else {
-        params.tilesPerWave = oneTileSteps(ctx, tiles, 4u * (params.tableDwords + params.codebookDwords), false);
+        uint32_t blocks = 0;
+        const int code = oneTileBlocks(ctx, tiles, geometry.waves, &params, &blocks);
+        if (code != MEMB_HIP_OK) {
+            return code;
+        }
         // very large batches leave word of their order for the next one (device-resident row ids only: the host-buffer
         // entry points stage slices of the caller's batch)
         const uint64_t R = uint64_t(ctx->cuCount) * PIPELINE_WAVES_PER_CU;
-        if (tiles > 16 * R && !keysOut && rows && ctx->orderSeenDevice) {
+        if (tiles > 16 * R && !narrow && !lookup.keysOut && lookup.rows && ctx->orderSeenDevice) {
             params.orderOut = ctx->orderSeenDevice;
         }
-        const size_t perBlock = size_t(geometry.waves) * params.tilesPerWave;
-        const uint32_t blocks = static_cast<uint32_t>((tiles + perBlock - 1) / perBlock);
         const uint32_t ldsBytes = std::min<uint32_t>(geometry.ldsBytes + ctx->switches.ldsPad, 160 * 1024);   // (ldsPad: measurement builds)
-        status = launchKernel(plan.kernel->fn, dim3(blocks), dim3(threads), ldsBytes, stream, params);
+        if (narrow) {
+            void* arguments[] = {&params};
+            status = launchKernelAddress(
+                memb_narrow::trainedKernel(lookupHasSub(ctx), geometry.mode, ctx->fast, lookup.outType), dim3(blocks), dim3(threads),
+                ldsBytes, stream, arguments);
+        } else {
+            status = launchKernel(plan.kernel->fn, dim3(blocks), dim3(threads), ldsBytes, stream, params);
+        }
     }
     if (status != hipSuccess) {
-        return fail(MEMB_HIP_ERR_DEVICE, std::string("decode_trained launch: ") + hipGetErrorString(status));
+        return fail(MEMB_HIP_ERR_DEVICE, std::string(narrow ? "decode_trained_narrow" : "decode_trained") + " launch: " + hipGetErrorString(status));
     }
     return MEMB_HIP_OK;
 }
@@ -860,11 +923,11 @@ int launchTrainedBatches(memb_hip_ctx* ctx, const memb_hip_batch* batches, size_
         const memb_hip_batch& batch = batches[k];
         words += batch.n;
         // one output mode for the launch: the most general one any batch needs (OUT_SCALAR < OUT_VEC4 < OUT_FLAT)
-        mode = std::min(mode, outputMode(ctx->dim, batch.ld, batch.col_off, batch.out));
+        mode = std::min(mode, outputMode(ctx->dim, batch.ld, batch.col_off, batch.out, 4, 0));
     }
     // (the finer index as for one batch of as many words: a serving loop's handful of small lookups is a small batch)
     TrainedPlan plan;
-    const int planned = planTrained(ctx, words, ctx->dim, 0, nullptr, false, &plan, 0, true);
+    const int planned = planTrained(ctx, floatRows(nullptr, words, nullptr, ctx->dim, 0), 0, true, false, &plan);
     if (planned != MEMB_HIP_OK) {
         return planned;
     }
@@ -892,15 +955,14 @@ int launchTrainedBatches(memb_hip_ctx* ctx, const memb_hip_batch* batches, size_
     if (!lookupParamsConsistent(ctx, params, geometry)) {
         return fail(MEMB_HIP_ERR_INVALID, "internal error: inconsistent decode geometry");
     }
-    params.tilesPerWave = oneTileSteps(ctx, tiles, 4u * (params.tableDwords + params.codebookDwords), false);
-    const size_t perBlock = size_t(geometry.waves) * params.tilesPerWave;
-    const uint64_t blocks = (tiles + perBlock - 1) / perBlock;
-    if (blocks >= 0x7FFFFFFFull) {
-        return fail(MEMB_HIP_ERR_INVALID, "batches too large for one launch");
+    uint32_t blocks = 0;
+    const int code = oneTileBlocks(ctx, tiles, geometry.waves, &params, &blocks);
+    if (code != MEMB_HIP_OK) {
+        return code;
     }
     const hipError_t status = launchKernel(
-        kernelTable().batches[lookupHasSub(ctx)][mode][ctx->fast].fn, dim3(static_cast<uint32_t>(blocks)), dim3(geometry.waves * WAVE),
-        geometry.ldsBytes, stream, params, list);
+        kernelTable().batches[lookupHasSub(ctx)][mode][ctx->fast].fn, dim3(blocks), dim3(geometry.waves * WAVE), geometry.ldsBytes,
+        stream, params, list);
     if (status != hipSuccess) {
         return fail(MEMB_HIP_ERR_DEVICE, std::string("decode_trained_batches launch: ") + hipGetErrorString(status));
     }
@@ -1175,10 +1237,11 @@ struct UniformTilePlan {
     uint32_t tileWords = 0;
 };
 
-UniformTilePlan planUniform(const memb_hip_ctx* ctx, size_t ld, size_t colOff, const float* out)
+UniformTilePlan planUniform(const memb_hip_ctx* ctx, const Lookup& lookup)
 {
     UniformTilePlan plan;
-    const bool vec = outputMode(ctx->dim, ld, colOff, out) != OUT_SCALAR;
+    // (fp32 only: a narrow uniform lookup runs the block kernel)
+    const bool vec = lookup.outType == MEMB_HIP_OUT_F32 && outputMode(ctx->dim, lookup.ld, lookup.colOff, lookup.out, 4, 0) != OUT_SCALAR;
     plan.tileWords = std::max<uint32_t>(1, std::min<uint32_t>(WAVE, (9600 + ctx->dim * 4 - 1) / (ctx->dim * 4)));
     plan.waves = 4;
     while (plan.waves > 1 && uint64_t(plan.waves) * plan.tileWords * ctx->regionPieces * 16 > ctx->ldsLimit) {
@@ -1189,35 +1252,60 @@ UniformTilePlan planUniform(const memb_hip_ctx* ctx, size_t ld, size_t colOff, c
     return plan;
 }
 
-int launchUniform(
-    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, float* out, size_t ld, size_t colOff, hipStream_t stream,
-    const Epilogue& epilogue)
+// The row-wise block kernels (dequant_uniform, gather_full and their narrow forms): `kernel` over n words, its one argument
+// *params. No dynamic LDS, so nothing to configure: a plain launch. vec: the form of four values per thread and store.
+template <typename Params>
+int launchRowwise(const char* name, const void* kernel, size_t n, bool vec, uint32_t dim, Params* params, hipStream_t stream)
 {
-    UniformParams params{};
-    params.accumulate = epilogue.accumulate;
-    params.divisor = epilogue.divisor;
-    params.rows = rows;
-    params.out = out;
-    params.n = n;
-    params.ld = ld;
-    params.colOff = colOff;
-    params.records = ctx->uniformRecords;
-    params.regionPieces = ctx->regionPieces;
+    if (vec) {
+        params->pieceMagic = magicFor(dim / 4, uint64_t(params->wordsPerBlock) * (dim / 4));
+    }
+    const uint32_t blocks = static_cast<uint32_t>((n + params->wordsPerBlock - 1) / params->wordsPerBlock);
+    void* arguments[] = {params};
+    hipError_t status = kernel ? hipLaunchKernel(kernel, dim3(blocks), dim3(ROWWISE_THREADS), arguments, 0, stream)
+                               : hipErrorInvalidDeviceFunction;
+    if (status == hipSuccess) {
+        status = hipGetLastError();
+    }
+    if (status != hipSuccess) {
+        return fail(MEMB_HIP_ERR_DEVICE, std::string(name) + " launch: " + hipGetErrorString(status));
+    }
+    return MEMB_HIP_OK;
+}
+
+// The fields UniformParams and FullParams share.
+template <typename Params>
+Params rowwiseParams(const memb_hip_ctx* ctx, const Lookup& lookup)
+{
+    Params params{};
+    params.accumulate = lookup.accumulate;
+    params.divisor = lookup.divisor;
+    params.rows = lookup.rows;
+    params.out = static_cast<float*>(lookup.out);   // (2-byte elements for a narrow type)
+    params.n = lookup.n;
+    params.ld = lookup.ld;
+    params.colOff = lookup.colOff;
     params.nRows = ctx->nRows;
     params.dim = ctx->dim;
     params.wordsPerBlock = rowwiseWordsPerBlock(ctx->dim);
+    return params;
+}
+
+int launchUniform(memb_hip_ctx* ctx, const Lookup& lookup, hipStream_t stream)
+{
+    UniformParams params = rowwiseParams<UniformParams>(ctx, lookup);
+    params.records = ctx->uniformRecords;
+    params.regionPieces = ctx->regionPieces;
     params.levels = ctx->levels;
-    const bool vec = outputMode(ctx->dim, ld, colOff, out) != OUT_SCALAR;
-    const UniformTilePlan tilePlan = planUniform(ctx, ld, colOff, out);
-    const uint32_t tileWords = tilePlan.tileWords;
-    const uint32_t waves = tilePlan.waves;
+    const UniformTilePlan tilePlan = planUniform(ctx, lookup);
     if (tilePlan.tiled) {
+        const uint32_t tileWords = tilePlan.tileWords, waves = tilePlan.waves;
         params.wordsPerWave = tileWords;
         params.regionMagic = magicFor(ctx->regionPieces, uint64_t(tileWords) * ctx->regionPieces + WAVE);
         params.pieceMagic = magicFor(ctx->dim / 4, uint64_t(tileWords) * (ctx->dim / 4));
         const uint32_t ldsBytes = waves * tileWords * ctx->regionPieces * 16;
-        const uint64_t tiles = (n + tileWords - 1) / tileWords;
-        const bool flat = ld == ctx->dim && colOff == 0;
+        const uint64_t tiles = (lookup.n + tileWords - 1) / tileWords;
+        const bool flat = lookup.ld == ctx->dim && lookup.colOff == 0;
         const hipError_t status = launchKernel(
             flat ? &dequant_uniform_tile<true> : &dequant_uniform_tile<false>, dim3(static_cast<uint32_t>((tiles + waves - 1) / waves)),
             dim3(waves * WAVE), ldsBytes, stream, params);
@@ -1226,202 +1314,44 @@ int launchUniform(
         }
         return MEMB_HIP_OK;
     }
-    const uint32_t blocks = static_cast<uint32_t>((n + params.wordsPerBlock - 1) / params.wordsPerBlock);
-    if (vec) {
-        params.pieceMagic = magicFor(ctx->dim / 4, uint64_t(params.wordsPerBlock) * (ctx->dim / 4));
-        hipLaunchKernelGGL(dequant_uniform<true>, dim3(blocks), dim3(ROWWISE_THREADS), 0, stream, params);
-    } else {
-        hipLaunchKernelGGL(dequant_uniform<false>, dim3(blocks), dim3(ROWWISE_THREADS), 0, stream, params);
-    }
-    hipError_t status = hipGetLastError();
-    if (status != hipSuccess) {
-        return fail(MEMB_HIP_ERR_DEVICE, std::string("dequant_uniform launch: ") + hipGetErrorString(status));
-    }
-    return MEMB_HIP_OK;
+    const bool vec = outputMode(ctx->dim, lookup.ld, lookup.colOff, lookup.out, lookup.elementBytes(), 0) != OUT_SCALAR;
+    void (*const fp32Kernel)(UniformParams) = vec ? &dequant_uniform<true> : &dequant_uniform<false>;
+    const bool narrow = lookup.outType != MEMB_HIP_OUT_F32;
+    return launchRowwise(
+        narrow ? "dequant_uniform_narrow" : "dequant_uniform",
+        narrow ? memb_narrow::uniformKernel(vec, lookup.outType) : reinterpret_cast<const void*>(fp32Kernel), lookup.n, vec, ctx->dim,
+        &params, stream);
 }
 
-int launchFull(
-    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, float* out, size_t ld, size_t colOff, hipStream_t stream,
-    const Epilogue& epilogue)
+int launchFull(memb_hip_ctx* ctx, const Lookup& lookup, hipStream_t stream)
 {
-    FullParams params{};
-    params.accumulate = epilogue.accumulate;
-    params.divisor = epilogue.divisor;
-    params.rows = rows;
-    params.out = out;
-    params.n = n;
-    params.ld = ld;
-    params.colOff = colOff;
+    FullParams params = rowwiseParams<FullParams>(ctx, lookup);
     params.values = ctx->fullValues;
-    params.nRows = ctx->nRows;
-    params.dim = ctx->dim;
-    params.wordsPerBlock = rowwiseWordsPerBlock(ctx->dim);
-    const bool vec = outputMode(ctx->dim, ld, colOff, out) != OUT_SCALAR;
-    const uint32_t blocks = static_cast<uint32_t>((n + params.wordsPerBlock - 1) / params.wordsPerBlock);
-    if (vec) {
-        params.pieceMagic = magicFor(ctx->dim / 4, uint64_t(params.wordsPerBlock) * (ctx->dim / 4));
-        hipLaunchKernelGGL(gather_full<true>, dim3(blocks), dim3(ROWWISE_THREADS), 0, stream, params);
-    } else {
-        hipLaunchKernelGGL(gather_full<false>, dim3(blocks), dim3(ROWWISE_THREADS), 0, stream, params);
-    }
-    hipError_t status = hipGetLastError();
-    if (status != hipSuccess) {
-        return fail(MEMB_HIP_ERR_DEVICE, std::string("gather_full launch: ") + hipGetErrorString(status));
-    }
-    return MEMB_HIP_OK;
+    const bool vec = outputMode(ctx->dim, lookup.ld, lookup.colOff, lookup.out, lookup.elementBytes(), 0) != OUT_SCALAR;
+    void (*const fp32Kernel)(FullParams) = vec ? &gather_full<true> : &gather_full<false>;
+    const bool narrow = lookup.outType != MEMB_HIP_OUT_F32;
+    return launchRowwise(
+        narrow ? "gather_full_narrow" : "gather_full",
+        narrow ? memb_narrow::fullKernel(vec, lookup.outType) : reinterpret_cast<const void*>(fp32Kernel), lookup.n, vec, ctx->dim,
+        &params, stream);
 }
 
-// ---- bf16 / fp16 rows (memb_hip_decode_rows_device_typed; the kernels: memb_hip_narrow.hip) ----
-
-// How decode_trained_narrow writes rows of dim 2-byte values to out + row * ld + colOff (ld, colOff in elements):
-// OUT_FLAT = 16-byte stores of 8 values over a tile's rows back to back, where every tile starts 16-byte aligned (dim a
-// multiple of 8, or an even number of words per tile); OUT_VEC4 = 8-byte stores of 4 values, row by row; else one value
-// per store.
-int narrowOutputMode(uint32_t dim, size_t ld, size_t colOff, const void* out, uint32_t wordsPerWave)
+// Every decode of rows into device memory, whatever the storage and the element type, starts here.
+int launch(memb_hip_ctx* ctx, const Lookup& lookup, hipStream_t stream)
 {
-    if (dim % 4 != 0 || ld % 4 != 0 || colOff % 4 != 0 || reinterpret_cast<uintptr_t>(out) % 8 != 0) {
-        return OUT_SCALAR;
-    }
-    const bool dense = ld == dim && colOff == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
-    return dense && (dim % 8 == 0 || wordsPerWave % 2 == 0) ? OUT_FLAT : OUT_VEC4;
-}
-
-// launchKernel for a kernel known by its address (the narrow kernels live in another translation unit): `params` is the
-// kernel's one argument.
-hipError_t launchKernelAt(const void* kernel, dim3 grid, dim3 block, uint32_t ldsBytes, hipStream_t stream, void* params)
-{
-    static thread_local std::unordered_map<const void*, int> configuredDevice;
-    if (!kernel) {
-        return hipErrorInvalidDeviceFunction;
-    }
-    int device = 0;
-    (void)hipGetDevice(&device);
-    int& configured = configuredDevice.try_emplace(kernel, -1).first->second;
-    if (configured != device) {
-        KernelFacts facts;
-        hipError_t status = kernelFacts(kernel, &facts);
-        if (status != hipSuccess) {
-            return status;
-        }
-        configured = device;
-    }
-    void* arguments[] = {params};
-    hipError_t status = hipLaunchKernel(kernel, grid, block, arguments, ldsBytes, stream);
-    return status != hipSuccess ? status : hipGetLastError();
-}
-
-// decode_trained_narrow: planned like decode_trained (planTrained), with half the codebook in LDS. Its instances keep
-// decode_trained's registers -- seven wavefronts per SIMD, ONE_TILE_WAVES_PER_CU (tests/test_narrow_isa.py) -- and it runs
-// at every batch size: no narrow decode_records_persistent. The batch-order word is read for the
-// block size, never written: a bf16 batch does not change what the next fp32 one picks.
-int launchNarrowTrained(
-    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, void* out, int outType, size_t ld, size_t colOff, hipStream_t stream)
-{
-    TrainedPlan plan;
-    const int planned = planTrained(ctx, n, ld, colOff, nullptr, false, &plan, 0, true, rowsUnordered(ctx, false), 2);
-    if (planned != MEMB_HIP_OK) {
-        return planned;
-    }
-    const TrainedGeometry geometry = plan.geometry;
-    if (!geometry.waves) {
-        return fail(MEMB_HIP_ERR_INVALID, "decode tables and bitstream slots do not fit into LDS");
-    }
-    TrainedParams params = lookupParams(ctx, plan.fine);
-    params.codebookDwords = codebookDwords(ctx) / 2;
-    params.rows = rows;
-    params.out = static_cast<float*>(out);   // (2-byte elements: outputTileNarrow)
-    params.n = n;
-    params.ld = ld;
-    params.colOff = colOff;
-    if (!lookupParamsConsistent(ctx, params, geometry) || ld < colOff + params.dim) {
-        return fail(MEMB_HIP_ERR_INVALID, "internal error: inconsistent decode geometry");
-    }
-    const uint32_t wordsPerWave = params.wordsPerWave;
-    const int mode = narrowOutputMode(ctx->dim, ld, colOff, out, wordsPerWave);
-    const void* kernel = memb_narrow::trainedKernel(lookupHasSub(ctx), mode, ctx->fast, outType);
-    const size_t tiles = (n + wordsPerWave - 1) / wordsPerWave;
-    params.tilesPerWave = oneTileSteps(ctx, tiles, 4u * (params.tableDwords + params.codebookDwords), false);
-    const size_t perBlock = size_t(geometry.waves) * params.tilesPerWave;
-    const uint32_t blocks = static_cast<uint32_t>((tiles + perBlock - 1) / perBlock);
-    const uint32_t ldsBytes = std::min<uint32_t>(geometry.ldsBytes + ctx->switches.ldsPad, 160 * 1024);
-    const hipError_t status = launchKernelAt(kernel, dim3(blocks), dim3(geometry.waves * WAVE), ldsBytes, stream, &params);
-    if (status != hipSuccess) {
-        return fail(MEMB_HIP_ERR_DEVICE, std::string("decode_trained_narrow launch: ") + hipGetErrorString(status));
-    }
-    return MEMB_HIP_OK;
-}
-
-// dequant_uniform_narrow / gather_full_narrow: the block kernels' geometry (launchUniform, launchFull), four values per
-// 8-byte store where rows allow it.
-int launchNarrowRowwise(
-    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, void* out, int outType, size_t ld, size_t colOff, hipStream_t stream)
-{
-    const bool vec = ctx->dim % 4 == 0 && ld % 4 == 0 && colOff % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0;
-    const uint32_t wordsPerBlock = rowwiseWordsPerBlock(ctx->dim);
-    const uint32_t pieceMagic = vec ? magicFor(ctx->dim / 4, uint64_t(wordsPerBlock) * (ctx->dim / 4)) : 0u;
-    const uint32_t blocks = static_cast<uint32_t>((n + wordsPerBlock - 1) / wordsPerBlock);
-    UniformParams uniform{};
-    FullParams full{};
-    const void* kernel;
-    void* params;
-    if (ctx->storage == memb::wire::Storage_Uniform) {
-        uniform.rows = rows;
-        uniform.out = static_cast<float*>(out);
-        uniform.n = n;
-        uniform.ld = ld;
-        uniform.colOff = colOff;
-        uniform.records = ctx->uniformRecords;
-        uniform.regionPieces = ctx->regionPieces;
-        uniform.nRows = ctx->nRows;
-        uniform.dim = ctx->dim;
-        uniform.wordsPerBlock = wordsPerBlock;
-        uniform.pieceMagic = pieceMagic;
-        uniform.levels = ctx->levels;
-        kernel = memb_narrow::uniformKernel(vec, outType);
-        params = &uniform;
-    } else {
-        full.rows = rows;
-        full.out = static_cast<float*>(out);
-        full.n = n;
-        full.ld = ld;
-        full.colOff = colOff;
-        full.values = ctx->fullValues;
-        full.nRows = ctx->nRows;
-        full.dim = ctx->dim;
-        full.wordsPerBlock = wordsPerBlock;
-        full.pieceMagic = pieceMagic;
-        kernel = memb_narrow::fullKernel(vec, outType);
-        params = &full;
-    }
-    void* arguments[] = {params};
-    hipError_t status = kernel ? hipLaunchKernel(kernel, dim3(blocks), dim3(ROWWISE_THREADS), arguments, 0, stream)
-                               : hipErrorInvalidDeviceFunction;
-    if (status == hipSuccess) {
-        status = hipGetLastError();
-    }
-    if (status != hipSuccess) {
-        return fail(MEMB_HIP_ERR_DEVICE, std::string("narrow row-wise launch: ") + hipGetErrorString(status));
-    }
-    return MEMB_HIP_OK;
-}
-
-int launch(
-    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, float* out, size_t ld, size_t colOff, hipStream_t stream,
-    const Epilogue& epilogue = Epilogue())
-{
-    if (n == 0) {
+    if (lookup.n == 0) {
         return MEMB_HIP_OK;
     }
-    if (n > (size_t(1) << 37)) {
+    if (lookup.n > (size_t(1) << 37)) {
         return fail(MEMB_HIP_ERR_INVALID, "batch too large");
     }
     switch (ctx->storage) {
         case memb::wire::Storage_Trained:
-            return launchTrained(ctx, rows, n, out, ld, colOff, stream, epilogue);
+            return launchTrained(ctx, lookup, stream);
         case memb::wire::Storage_Uniform:
-            return launchUniform(ctx, rows, n, out, ld, colOff, stream, epilogue);
+            return launchUniform(ctx, lookup, stream);
         case memb::wire::Storage_Full:
-            return launchFull(ctx, rows, n, out, ld, colOff, stream, epilogue);
+            return launchFull(ctx, lookup, stream);
         default:
             return fail(MEMB_HIP_ERR_INVALID, "context has no storage");
     }
@@ -1928,7 +1858,7 @@ void chooseLanes(memb_hip_ctx* ctx, const memb_hip_trained_desc* desc)
         lanes = std::min<uint32_t>(WAVE, lanes < 8 ? 8 : 2 * lanes);
     }
     // a forced block size (MEMB_HIP_WAVES, tests) may still need the room
-    while (!chooseGeometry(ctx, WAVE / ctx->lanesPerWord, ctx->dim, 0, nullptr).waves && narrowTable()) {
+    while (!chooseGeometry(ctx, WAVE / ctx->lanesPerWord, 4).waves && narrowTable()) {
     }
     ctx->indexWide = uint64_t(ctx->maxStreamBytes) * 8 + 64 >= 65536;
 }
@@ -2000,7 +1930,7 @@ int stageIndex(memb_hip_ctx* ctx, const memb_hip_trained_desc* desc)
 {
     int code = MEMB_HIP_OK;
     if (code == MEMB_HIP_OK) {
-        TrainedGeometry geometry = chooseGeometry(ctx, WAVE / ctx->lanesPerWord, ctx->dim, 0, nullptr);
+        TrainedGeometry geometry = chooseGeometry(ctx, WAVE / ctx->lanesPerWord, 4);
         if (!geometry.waves) {
             code = fail(MEMB_HIP_ERR_INVALID, "decode tables and bitstream slots do not fit into LDS");
         }
@@ -2314,7 +2244,8 @@ int fillInfo(const memb_hip_ctx* ctx, memb_hip_ctx_info* info, uint64_t batchWor
             DeviceScope deviceScope(ctx->device);
             HIP_TRY(deviceScope.status());
             const int planned = planTrained(
-                ctx, batchWords ? size_t(batchWords) : size_t(1) << 30, ctx->dim, 0, nullptr, false, &plan, -1, true, rowsUnordered(ctx, false));
+                ctx, floatRows(nullptr, batchWords ? size_t(batchWords) : size_t(1) << 30, nullptr, ctx->dim, 0), -1, true,
+                rowsUnordered(ctx, false), &plan);
             if (planned != MEMB_HIP_OK) {
                 return planned;
             }
@@ -2340,7 +2271,7 @@ int fillInfo(const memb_hip_ctx* ctx, memb_hip_ctx_info* info, uint64_t batchWor
         }
     } else {
         // (a dense, aligned device-resident batch: what bench.py and the tests report for)
-        const UniformTilePlan tilePlan = ctx->storage == memb::wire::Storage_Uniform ? planUniform(ctx, ctx->dim, 0, nullptr) : UniformTilePlan();
+        const UniformTilePlan tilePlan = ctx->storage == memb::wire::Storage_Uniform ? planUniform(ctx, floatRows(nullptr, 0, nullptr, ctx->dim, 0)) : UniformTilePlan();
         const bool tiled = tilePlan.tiled;
         info->waves_per_block = tiled ? tilePlan.waves : ROWWISE_THREADS / WAVE;
         info->lds_bytes_per_block = tiled ? tilePlan.waves * tilePlan.tileWords * ctx->regionPieces * 16 : 0;
@@ -2351,20 +2282,7 @@ int fillInfo(const memb_hip_ctx* ctx, memb_hip_ctx_info* info, uint64_t batchWor
     return MEMB_HIP_OK;
 }
 
-int decode_rows_device_checked(
-    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, float* out, size_t ld, size_t col_off, void* stream)
-{
-    if (!ctx || (n && (!rows || !out))) {
-        return fail(MEMB_HIP_ERR_INVALID, "null argument");
-    }
-    if (ld < col_off + ctx->dim) {
-        return fail(MEMB_HIP_ERR_INVALID, "ld must be at least col_off + dim");
-    }
-    DeviceScope deviceScope(ctx->device);
-    HIP_TRY(deviceScope.status());
-    return launch(ctx, rows, n, out, ld, col_off, static_cast<hipStream_t>(stream));
-}
-
+// (memb_hip_decode_rows_device: no flags, no divisor)
 int decode_rows_device_ex_checked(
     memb_hip_ctx* ctx, const uint32_t* rows, size_t n, float* out, size_t ld, size_t col_off, void* stream,
     uint32_t flags, float divisor)
@@ -2380,11 +2298,11 @@ int decode_rows_device_ex_checked(
     }
     DeviceScope deviceScope(ctx->device);
     HIP_TRY(deviceScope.status());
-    Epilogue epilogue;
-    epilogue.accumulate = (flags & MEMB_HIP_ACCUMULATE) ? 1u : 0u;
-    epilogue.divisor = divisor;
-    epilogue.randomOrder = (flags & MEMB_HIP_ROWS_IN_RANDOM_ORDER) != 0;
-    return launch(ctx, rows, n, out, ld, col_off, static_cast<hipStream_t>(stream), epilogue);
+    Lookup lookup = floatRows(rows, n, out, ld, col_off);
+    lookup.accumulate = (flags & MEMB_HIP_ACCUMULATE) ? 1u : 0u;
+    lookup.divisor = divisor;
+    lookup.randomOrder = (flags & MEMB_HIP_ROWS_IN_RANDOM_ORDER) != 0;
+    return launch(ctx, lookup, static_cast<hipStream_t>(stream));
 }
 
 int decode_rows_device_typed_checked(
@@ -2403,27 +2321,9 @@ int decode_rows_device_typed_checked(
     if (col_off > ld || ld - col_off < ctx->dim) {
         return fail(MEMB_HIP_ERR_INVALID, "ld must be at least col_off + dim");
     }
-    if (outType == MEMB_HIP_OUT_F32) {
-        return decode_rows_device_checked(ctx, rows, n, static_cast<float*>(out), ld, col_off, stream);
-    }
-    if (n == 0) {
-        return MEMB_HIP_OK;
-    }
-    if (n > (size_t(1) << 37)) {
-        return fail(MEMB_HIP_ERR_INVALID, "batch too large");
-    }
     DeviceScope deviceScope(ctx->device);
     HIP_TRY(deviceScope.status());
-    const hipStream_t hipStream = static_cast<hipStream_t>(stream);
-    switch (ctx->storage) {
-        case memb::wire::Storage_Trained:
-            return launchNarrowTrained(ctx, rows, n, out, outType, ld, col_off, hipStream);
-        case memb::wire::Storage_Uniform:
-        case memb::wire::Storage_Full:
-            return launchNarrowRowwise(ctx, rows, n, out, outType, ld, col_off, hipStream);
-        default:
-            return fail(MEMB_HIP_ERR_INVALID, "context has no storage");
-    }
+    return launch(ctx, Lookup{rows, n, out, outType, ld, col_off}, static_cast<hipStream_t>(stream));
 }
 
 int decode_batches_device_checked(memb_hip_ctx* ctx, const memb_hip_batch* batches, size_t count, void* stream)
@@ -2452,7 +2352,7 @@ int decode_batches_device_checked(memb_hip_ctx* ctx, const memb_hip_batch* batch
     if (ctx->storage != memb::wire::Storage_Trained || live.size() == 1) {
         // uniform / full: their kernels have no shared prologue worth one launch; a single batch: the plain call
         for (const memb_hip_batch& batch : live) {
-            const int code = launch(ctx, batch.rows, batch.n, batch.out, batch.ld, batch.col_off, static_cast<hipStream_t>(stream));
+            const int code = launch(ctx, floatRows(batch.rows, batch.n, batch.out, batch.ld, batch.col_off), static_cast<hipStream_t>(stream));
             if (code != MEMB_HIP_OK) {
                 return code;
             }
@@ -2523,7 +2423,7 @@ int decode_rows_checked(
         if (ctx->smallHost) {
             std::memcpy(ctx->smallHost, rows, n * sizeof(uint32_t));
             float* deviceOut = reinterpret_cast<float*>(static_cast<char*>(ctx->smallDevice) + outOffset);
-            int code = launch(ctx, static_cast<const uint32_t*>(ctx->smallDevice), n, deviceOut, ctx->dim, 0, ctx->stream);
+            int code = launch(ctx, floatRows(static_cast<const uint32_t*>(ctx->smallDevice), n, deviceOut, ctx->dim, 0), ctx->stream);
             if (code != MEMB_HIP_OK) {
                 return code;
             }
@@ -2603,7 +2503,7 @@ int decode_rows_checked(
             result = decodeRowsAsKeys(
                 ctx, ctx->stagedRows, rows + start, words, reinterpret_cast<uint8_t*>(ctx->stagedOut), destination, ld);
         } else {
-            result = launch(ctx, ctx->stagedRows, words, ctx->stagedOut, dim, 0, ctx->stream);
+            result = launch(ctx, floatRows(ctx->stagedRows, words, ctx->stagedOut, dim, 0), ctx->stream);
             if (result == MEMB_HIP_OK) {
                 result = copyRowsToHost(ctx, ctx->stagedOut, words, destination, ld);
             }
@@ -2802,7 +2702,7 @@ int memb_hip_ctx_set_option(memb_hip_ctx* ctx, const char* name, uint64_t value)
 
 int memb_hip_decode_rows_device(memb_hip_ctx* ctx, const uint32_t* rows, size_t n, float* out, size_t ld, size_t col_off, void* stream)
 {
-    return guarded([&] { return decode_rows_device_checked(ctx, rows, n, out, ld, col_off, stream); });
+    return guarded([&] { return decode_rows_device_ex_checked(ctx, rows, n, out, ld, col_off, stream, 0, 0.f); });
 }
 
 int memb_hip_decode_rows_device_ex(memb_hip_ctx* ctx, const uint32_t* rows, size_t n, float* out, size_t ld, size_t col_off, void* stream, uint32_t flags, float divisor)

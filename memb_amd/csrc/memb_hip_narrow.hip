@@ -1,7 +1,7 @@
 // bf16 / fp16 rows straight from the decoder (include/memb_hip_narrow.h): the kernels, gfx950 / CDNA4.
 //
 // A translation unit of its own, linked into libmemb_hip.so beside memb_hip.hip, which plans and launches these kernels
-// (launchNarrow) through the addresses below (hip_narrow.h). Every value is the fp32 value of the float kernels rounded
+// (launchTrained, launchUniform, launchFull) through the addresses below (hip_narrow.h). Every value is the fp32 value of the float kernels rounded
 // once, to nearest even, by a plain cast (hip_device_common.h: narrowBits):
 //   decode_trained_narrow<HAS_SUB, MODE, FAST, OUT>  decode_trained's body (hip_trained_kernels.h: decodeTilesOfBlock)
 //                      with the codebook rounded as the block copies it into LDS (half the LDS of fp32) and the output

@@ -1,4 +1,4 @@
-"""The bf16 / fp16 kernels (memb_hip_narrow.hip; outputTileNarrow, launchNarrowTrained, launchNarrowRowwise) over the
+"""The bf16 / fp16 kernels (memb_hip_narrow.hip; outputTileNarrow; memb_hip.hip: launchTrained, launchUniform, launchFull) over the
 geometry the fp32 path is walked through in test_gpu_parity.py: lanes per word and block sizes, the finer index forced on
 and off, key forms and table widths, row layouts, the batch-size edges of the plan, very wide rows, arbitrary prefix
 codes, degenerate models, a seeded sweep, threads on streams of their own.
@@ -57,7 +57,7 @@ def expected_of(checker, rows):
 
 
 def narrow_output_mode(dim, ld, col_off, pointer, words_per_wave):
-    """memb_hip.hip: narrowOutputMode, restated"""
+    """memb_hip.hip: outputMode for 2-byte elements, restated"""
     if dim % 4 or ld % 4 or col_off % 4 or pointer % 8:
         return OUT_SCALAR
     dense = ld == dim and col_off == 0 and pointer % 16 == 0
@@ -121,7 +121,7 @@ def check_reader(reader, storage, dim, rows, expected, label, fines=(1, 2), layo
                     modes.add(mode)
                     instance = (type_name, 'trained', has_sub, mode, fast)
                 else:
-                    vec4 = dim % 4 == 0 and ld % 4 == 0 and col_off % 4 == 0 and pointer % 8 == 0   # launchNarrowRowwise
+                    vec4 = dim % 4 == 0 and ld % 4 == 0 and col_off % 4 == 0 and pointer % 8 == 0   # launchUniform / launchFull: outputMode != OUT_SCALAR
                     instance = (type_name, storage, vec4)
                 REACHED.add(instance)
                 try:
@@ -465,7 +465,7 @@ def test_randomized_models_and_batches(native, tmp_path, monkeypatch):
 @pytest.mark.parametrize('bits,distribution', [(4, 'normal'), (8, 'student')])
 def test_six_threads_on_streams_of_their_own(native, make_model, bits, distribution):
     """One fresh Reader, six threads that start behind a barrier, each on a stream of its own: bf16, fp16 and fp32 calls of
-    1 .. 100 000 rows mixed, the first narrow launch of the process's per-thread kernel tables (launchKernelAt) among
+    1 .. 100 000 rows mixed, the first narrow launch of the process's per-thread kernel tables (launchKernelAddress) among
     them; every result against the checker."""
     import torch
     path, _ = make_model(20000, 300, 'trained', bits, distribution=distribution)
@@ -515,7 +515,7 @@ def test_six_threads_on_streams_of_their_own(native, make_model, bits, distribut
 # ---- 2. which instance ran ----
 
 def test_every_narrow_instance_is_reached(native, make_model, monkeypatch):
-    """info() does not name the narrow kernel: check_reader restates narrowOutputMode for every decode and takes HAS_SUB and
+    """info() does not name the narrow kernel: check_reader restates outputMode for every decode and takes HAS_SUB and
     FAST from the model's decode_trained instance. The cases below alone must reach the nine decode_trained_narrow
     instances and the four row-wise ones of each dtype; whatever the other tests of this file ran is counted as well."""
     before = set(REACHED)

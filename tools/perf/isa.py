@@ -2,11 +2,14 @@
 registers, scratch and LDS, read from the device assembly (no GPU needed).
 
     python tools/perf/isa.py [substring of the demangled kernel name] [-- extra hipcc flags]
+    python tools/perf/isa.py --digests     one line per kernel of both translation units, instruction digest and resources: run it
+                                           on two commits and diff the listings to see which kernels a change touched
 
 tests/test_isa.py uses kernel_table() to pin facts a source-level reading can get wrong: round 2 shipped
 `flag ? *p : __builtin_nontemporal_load(p)`, which LLVM folds into ONE plain load, and reported the
 `nt` loads as adopted.
 """
+import hashlib
 import os
 import re
 import shutil
@@ -79,11 +82,21 @@ def kernel_table(extra_flags=(), source=SOURCE):
             'sgpr': field('amdhsa_next_free_sgpr'),
             'accum_offset': field('amdhsa_accum_offset'),
             'private_segment': field('amdhsa_private_segment_fixed_size'),
+            'lds': field('amdhsa_group_segment_fixed_size'),
+            # digest of the instruction text with the function number taken out of its labels (.LBB<n>_<m> -> .LBB_<m>)
+            'digest': hashlib.sha256(re.sub(r'\.LBB\d+_(\d+)', r'.LBB_\1', code).encode()).hexdigest()[:16],
             'vgpr_count': field('vgpr_count:', meta) if meta else None,
             # (.sgpr_count of the metadata = next_free_sgpr + VCC / flat scratch / XNACK: what the hardware allocates by)
             'sgpr_count': field('sgpr_count:', meta) if meta else None,
         }
     return table
+
+
+def kernel_digests():
+    """{demangled kernel name: (digest of its instructions, vgpr, sgpr_count, LDS bytes, scratch bytes)} over both translation
+    units: equal before and after a change that is meant to leave the device code alone"""
+    return {pretty: (facts['digest'], facts['vgpr'], facts['sgpr_count'], facts['lds'], facts['private_segment'])
+            for source in (SOURCE, NARROW_SOURCE) for pretty, facts in kernel_table(source=source).items()}
 
 
 def waves_per_simd(vgpr, sgpr_count=None):
@@ -103,6 +116,10 @@ if __name__ == '__main__':
     if '--' in arguments:
         extra = arguments[arguments.index('--') + 1:]
         arguments = arguments[:arguments.index('--')]
+    if arguments[:1] == ['--digests']:   # one line per kernel, to diff against another commit's
+        for pretty, facts in sorted(kernel_digests().items()):
+            print(pretty.replace('(anonymous namespace)::', '').split('(')[0], *facts)
+        sys.exit(0)
     needle = arguments[0] if arguments else ''
     print('%-92s %5s %5s %4s %6s %6s %4s %4s %7s %8s' % (
         'kernel', 'ld.x4', 'nt', 'dma', 'st.x4', 'st.nt', 'vgpr', 'sgpr', 'scratch', 'waves/EU'))   # sgpr = .sgpr_count
