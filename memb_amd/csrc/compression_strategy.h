@@ -18,6 +18,7 @@
 #include "wire.h"
 #include "../../include/memb_hip.h"
 #include "../../include/memb_hip_narrow.h"
+#include "../../include/memb_hip_pooled.h"
 
 #include <atomic>
 #include <memory>
@@ -64,6 +65,11 @@ public:
     // Same with elements of outType (include/memb_hip_narrow.h: MEMB_HIP_OUT_*); ld and colOff count elements.
     void decodeRowsDeviceTyped(
         const uint32_t* rows, size_t n, void* out, int outType, size_t ld, size_t colOff, void* stream) const;
+    // The sum or mean (mode: MEMB_HIP_POOL_*) of each bag of rows, device buffers (include/memb_hip_pooled.h): bag b =
+    // rows[offsets[b] .. offsets[b + 1]) goes to out[b * ld + colOff ..].
+    void poolRowsDevice(
+        const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, float* out, size_t ld, size_t colOff, int mode,
+        void* stream) const;
 
     // device == HOST_DEVICE: rows are decoded by extractRowHost on host threads
     static constexpr int HOST_DEVICE = -2;

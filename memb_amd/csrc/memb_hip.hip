@@ -32,14 +32,17 @@
 // code; this file -- context, staging of a model to HBM, launch geometry, the C
 // ABI; memb_hip_narrow.hip -- the bf16 / fp16 kernels, a translation unit of its own
 // that includes the same device headers and hands its kernels over as addresses
-// (hip_narrow.h), planned and launched here; hip_host_path.h -- how rows reach host
+// (hip_narrow.h), planned and launched here; memb_hip_pooled.hip -- the pooled kernels (sum / mean
+// of each bag of rows), handed over the same way (hip_pooled.h); hip_host_path.h -- how rows reach host
 // buffers (pinned ring, copy threads, centroid indices over PCIe).
 #include <hip/hip_runtime.h>
 
 #include "../../include/memb_hip.h"
 #include "../../include/memb_hip_narrow.h"
+#include "../../include/memb_hip_pooled.h"
 #include "codec.h"
 #include "hip_narrow.h"
+#include "hip_pooled.h"
 #include "wire.h"
 #include "worker_pool.h"
 
@@ -1357,6 +1360,95 @@ int launch(memb_hip_ctx* ctx, const Lookup& lookup, hipStream_t stream)
     }
 }
 
+// A pooled lookup (include/memb_hip_pooled.h): `lookup` describes the ENTRIES (rows, n) and the bags' rows (out, ld, colOff),
+// `pool` the bags. One kernel of memb_hip_pooled.hip, whatever the storage.
+// Trained: planned like a decode of n rows by the one-tile kernel (planTrained, force = 0, usual index) -- pool_trained is
+// that kernel up to the symbol tile -- and a wavefront owns a run of consecutive bags sized so that it decodes about
+// POOLED_TILES_PER_WAVE tiles (option tiles_per_wave: that many), fewer while the grid would not fill the CUs. A bag is
+// never split: ONE enormous bag is walked by one wavefront, correct and slow.
+constexpr uint32_t POOLED_TILES_PER_WAVE = 4;
+
+int launchPooled(memb_hip_ctx* ctx, const Lookup& lookup, memb_pooled::PoolParams pool, hipStream_t stream)
+{
+    if (lookup.n > (size_t(1) << 37) || pool.bags >= (1ull << 37)) {
+        return fail(MEMB_HIP_ERR_INVALID, "batch too large");
+    }
+    const void* kernel = nullptr;
+    const char* name = "";
+    void* arguments[2] = {nullptr, &pool};
+    TrainedParams trained;
+    UniformParams uniform;
+    FullParams full;
+    uint32_t waves = memb_pooled::ROWWISE_WAVES;
+    uint32_t ldsBytes = 0;
+    pool.bagsPerWave = 1;
+    switch (ctx->storage) {
+        case memb::wire::Storage_Trained: {
+            Lookup planned = lookup;
+            planned.n = std::max<size_t>(lookup.n, 1);
+            TrainedPlan plan;
+            const int code = planTrained(ctx, planned, 0, false, rowsUnordered(ctx, false), &plan);
+            if (code != MEMB_HIP_OK) {
+                return code;
+            }
+            const TrainedGeometry geometry = plan.geometry;
+            if (!geometry.waves) {
+                return fail(MEMB_HIP_ERR_INVALID, "decode tables and bitstream slots do not fit into LDS");
+            }
+            trained = lookupParams(ctx);
+            trained.rows = lookup.rows;
+            trained.out = static_cast<float*>(lookup.out);
+            trained.n = lookup.n;
+            trained.ld = lookup.ld;
+            trained.colOff = lookup.colOff;
+            if (!lookupParamsConsistent(ctx, trained, geometry) || lookup.ld < lookup.colOff + trained.dim) {
+                return fail(MEMB_HIP_ERR_INVALID, "internal error: inconsistent decode geometry");
+            }
+            const bool vec4 = geometry.mode != OUT_SCALAR && ctx->dim <= memb_pooled::TRAINED_VEC4_MAX_DIM;
+            waves = geometry.waves;
+            ldsBytes = geometry.ldsBytes;
+            const uint64_t tilesPerWave = ctx->switches.tilesPerWave ? ctx->switches.tilesPerWave : POOLED_TILES_PER_WAVE;
+            const uint64_t entriesPerBag = std::max<uint64_t>(1, lookup.n / std::max<uint64_t>(pool.bags, 1));
+            const uint64_t fillsTheCus = std::max<uint64_t>(1, pool.bags / (uint64_t(ctx->cuCount) * ONE_TILE_WAVES_PER_CU));
+            pool.bagsPerWave = static_cast<uint32_t>(std::min<uint64_t>(
+                std::min<uint64_t>(std::max<uint64_t>(1, tilesPerWave * trained.wordsPerWave / entriesPerBag), fillsTheCus), 1u << 16));
+            kernel = memb_pooled::trainedKernel(lookupHasSub(ctx), ctx->fast, vec4);
+            name = "pool_trained";
+            arguments[0] = &trained;
+            break;
+        }
+        case memb::wire::Storage_Uniform:
+            uniform = rowwiseParams<UniformParams>(ctx, lookup);
+            uniform.records = ctx->uniformRecords;
+            uniform.regionPieces = ctx->regionPieces;
+            uniform.levels = ctx->levels;
+            kernel = memb_pooled::uniformKernel();
+            name = "pool_uniform";
+            arguments[0] = &uniform;
+            break;
+        case memb::wire::Storage_Full:
+            full = rowwiseParams<FullParams>(ctx, lookup);
+            full.values = ctx->fullValues;
+            kernel = memb_pooled::fullKernel();
+            name = "pool_full";
+            arguments[0] = &full;
+            break;
+        default:
+            return fail(MEMB_HIP_ERR_INVALID, "context has no storage");
+    }
+    const uint64_t perBlock = uint64_t(waves) * pool.bagsPerWave;
+    const uint64_t blocks = (pool.bags + perBlock - 1) / perBlock;
+    if (blocks >= 0x7FFFFFFFull) {
+        return fail(MEMB_HIP_ERR_INVALID, "batches too large for one launch");
+    }
+    const hipError_t status =
+        launchKernelAddress(kernel, dim3(static_cast<uint32_t>(blocks)), dim3(waves * WAVE), ldsBytes, stream, arguments);
+    if (status != hipSuccess) {
+        return fail(MEMB_HIP_ERR_DEVICE, std::string(name) + " launch: " + hipGetErrorString(status));
+    }
+    return MEMB_HIP_OK;
+}
+
 template <typename T>
 int deviceAlloc(memb_hip_ctx* ctx, T** pointer, size_t bytes)
 {
@@ -2326,6 +2418,69 @@ int decode_rows_device_typed_checked(
     return launch(ctx, Lookup{rows, n, out, outType, ld, col_off}, static_cast<hipStream_t>(stream));
 }
 
+int pool_rows_device_checked(
+    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, float* out, size_t ld,
+    size_t col_off, int mode, void* stream)
+{
+    if (mode != MEMB_HIP_POOL_SUM && mode != MEMB_HIP_POOL_MEAN) {
+        return fail(MEMB_HIP_ERR_INVALID, "unknown pooling mode " + std::to_string(mode));
+    }
+    if (!ctx || (n && !rows) || (bags && (!offsets || !out))) {
+        return fail(MEMB_HIP_ERR_INVALID, "null argument");
+    }
+    if (reinterpret_cast<uintptr_t>(out) % sizeof(float) != 0) {
+        return fail(MEMB_HIP_ERR_INVALID, "out must be aligned to its element (4 bytes)");
+    }
+    if (col_off > ld || ld - col_off < ctx->dim) {
+        return fail(MEMB_HIP_ERR_INVALID, "ld must be at least col_off + dim");
+    }
+    if (bags == 0) {
+        return MEMB_HIP_OK;
+    }
+    DeviceScope deviceScope(ctx->device);
+    HIP_TRY(deviceScope.status());
+    memb_pooled::PoolParams pool{};
+    pool.offsets = offsets;
+    pool.bags = bags;
+    pool.mean = mode == MEMB_HIP_POOL_MEAN ? 1u : 0u;
+    return launchPooled(ctx, floatRows(rows, n, out, ld, col_off), pool, static_cast<hipStream_t>(stream));
+}
+
+int pooled_algorithmic_bytes_checked(
+    const memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, uint64_t* bytes)
+{
+    if (!ctx || !bytes || (n && !rows) || (bags && !offsets)) {
+        return fail(MEMB_HIP_ERR_INVALID, "null argument");
+    }
+    uint64_t total = 0;
+    for (size_t bag = 0; bag < bags; ++bag) {
+        total += 8 + 4ull * ctx->dim;
+        const size_t begin = std::min<size_t>(offsets[bag], n);
+        const size_t end = std::min<size_t>(offsets[bag + 1], n);
+        for (size_t i = begin; i < end; ++i) {
+            total += 4;
+            if (rows[i] >= ctx->nRows) {
+                continue;
+            }
+            switch (ctx->storage) {
+                case memb::wire::Storage_Trained:
+                    total += 4 + ctx->streamBytes[rows[i]];
+                    break;
+                case memb::wire::Storage_Uniform:
+                    total += 12 + ctx->dim;
+                    break;
+                case memb::wire::Storage_Full:
+                    total += 4 + 4ull * ctx->dim;
+                    break;
+                default:
+                    break;
+            }
+        }
+    }
+    *bytes = total;
+    return MEMB_HIP_OK;
+}
+
 int decode_batches_device_checked(memb_hip_ctx* ctx, const memb_hip_batch* batches, size_t count, void* stream)
 {
     if (!ctx || (count && !batches)) {
@@ -2714,6 +2869,19 @@ int memb_hip_decode_rows_device_typed(
     memb_hip_ctx* ctx, const uint32_t* rows, size_t n, void* out, int out_type, size_t ld, size_t col_off, void* stream)
 {
     return guarded([&] { return decode_rows_device_typed_checked(ctx, rows, n, out, out_type, ld, col_off, stream); });
+}
+
+int memb_hip_pool_rows_device(
+    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, float* out, size_t ld,
+    size_t col_off, int mode, void* stream)
+{
+    return guarded([&] { return pool_rows_device_checked(ctx, rows, n, offsets, bags, out, ld, col_off, mode, stream); });
+}
+
+int memb_hip_pooled_algorithmic_bytes(
+    const memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, uint64_t* bytes)
+{
+    return guarded([&] { return pooled_algorithmic_bytes_checked(ctx, rows, n, offsets, bags, bytes); });
 }
 
 int memb_hip_decode_batches_device(memb_hip_ctx* ctx, const memb_hip_batch* batches, size_t count, void* stream)

@@ -456,6 +456,13 @@ void Reader::rowsToDeviceBufferTyped(
     compressedStorage_->decodeRowsDeviceTyped(rows, n, buffer, outType, ld, colOff, stream);
 }
 
+void Reader::poolRowsDevice(
+    const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, float* buffer, size_t ld, size_t colOff, int mode,
+    void* stream) const
+{
+    compressedStorage_->poolRowsDevice(rows, n, offsets, bags, buffer, ld, colOff, mode, stream);
+}
+
 std::vector<float> Reader::wordEmbedding(const std::string& word) const
 {
     std::vector<float> result(dim());

@@ -109,6 +109,34 @@ def host_offsets(offsets):
     return np.ascontiguousarray(array, dtype=np.uint32)
 
 
+POOL_MODES = {'sum': _memb.POOL_SUM, 'mean': _memb.POOL_MEAN}
+BAGS_HOST_CHUNK = 1 << 16   # entries bags_embedding of a device='cpu' reader decodes at a time
+
+
+def pool_mode(mode):
+    """'sum' / 'mean' as the C ABI's MEMB_HIP_POOL_*; anything else (max pooling, weights) is not built"""
+    if mode not in POOL_MODES:
+        raise ValueError("pooling mode must be 'sum' or 'mean', not {!r}".format(mode))
+    return POOL_MODES[mode]
+
+
+def bag_offsets(offsets, n):
+    """offsets of bags_embedding as a numpy.int64 array: bags + 1 integers, ascending, within 0 .. n. Anything else is a
+    ValueError: on the host nothing is clamped silently."""
+    array = np.asarray(offsets)
+    if array.ndim != 1 or array.size < 1:
+        raise ValueError('offsets needs bags + 1 entries')
+    if array.dtype.kind not in 'iu':
+        raise ValueError('offsets must be integers, not {}'.format(array.dtype))
+    array = array.astype(np.int64) if array.dtype != np.uint64 else array
+    if array.min() < 0 or array.max() > n:
+        raise ValueError('offsets must lie in 0 .. len(rows) = {}'.format(n))
+    array = array.astype(np.int64)
+    if np.any(array[1:] < array[:-1]):
+        raise ValueError('offsets must ascend')
+    return array
+
+
 def tokenizer_word_list(tokenizer):
     """The words of a keras Tokenizer placed at their indices, '' where an index
     has no word (index 0 never has one). With `num_words` set only indices below
@@ -284,6 +312,123 @@ class Reader(BaseReader):
         self._impl.rows_to_device(
             rows.data_ptr(), n, out.data_ptr(), out.stride(0), col_off, _current_stream(torch, index), accumulate, float(divisor),
             order == 'random')
+        return out
+
+    def bags_embedding_device(self, rows, offsets, mode='mean', out=None, col_off=0):
+        '''Pooled lookup that never leaves the GPU: the sum or mean of each bag of rows, decoded and reduced by one kernel
+        (the EmbeddingBag counterpart of rows_embedding_device). The bags' rows are never written: per entry the kernel
+        reads the row id and the compressed row, per bag it stores dim floats.
+        Parameters
+        ----------
+        rows : torch.Tensor, as in rows_embedding_device (n entries)
+        offsets : contiguous int32 / uint32 torch.Tensor of bags + 1 entries on this reader's device; bag b owns the
+            entries [min(offsets[b], n), min(offsets[b + 1], n)) and is empty when that range is (offsets are read as
+            uint32; no entry outside rows is read whatever they hold)
+        mode : 'mean' or 'sum'. Both add a bag's float32 rows one after the other in entry order (a row that is not in
+            the model is +0.0 and counts); 'mean' then divides once by the entry count. An empty bag is +0.0, a bag of
+            one entry that row's bits. Bit for bit the result of that loop over rows_embedding_device(rows).
+        out : float32 torch.Tensor (bags, >= col_off + dim) with unit column stride on the same device, optional
+        No bf16 / fp16 output, no accumulate into `out`, no per-entry weights, no 'max'.
+        '''
+        import torch
+        code = pool_mode(mode)
+        index = self._impl.device()
+        if index == _memb.HOST_DEVICE:
+            raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
+        device = rows.device
+        if device.type != 'cuda' or rows.dtype not in (torch.int32, torch.uint32) or not rows.is_contiguous():
+            raise TypeError('rows must be a contiguous int32/uint32 tensor on the GPU')
+        if (not isinstance(offsets, torch.Tensor) or offsets.device.type != 'cuda' or offsets.dtype not in (torch.int32, torch.uint32)
+                or not offsets.is_contiguous() or offsets.dim() != 1):
+            raise TypeError('offsets must be a contiguous int32/uint32 tensor of bags + 1 entries on the GPU')
+        if offsets.numel() < 1:
+            raise ValueError('offsets needs bags + 1 entries')
+        bags = offsets.numel() - 1
+        if out is None:
+            out = torch.empty((bags, col_off + self.dim), dtype=torch.float32, device=device)
+        if out.dtype != torch.float32:
+            raise TypeError('out is {}: pooled rows are float32 (a bf16 / fp16 sum would be rounded after every entry)'.format(out.dtype))
+        if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] != bags:
+            raise TypeError('out must be a float32 (bags, width) tensor with unit column stride')
+        if device.index != index or out.device != device or offsets.device != device:
+            raise ValueError('rows, offsets and out must be on cuda:{} (the device this reader is staged on), got {}, {} and {}'.format(
+                self.device, device, offsets.device, out.device))
+        if out.shape[1] < col_off + self.dim:
+            raise ValueError('out is narrower than col_off + dim')
+        self._impl.pool_rows_to_device(
+            rows.data_ptr(), rows.numel(), offsets.data_ptr(), bags, out.data_ptr(), out.stride(0) if bags > 1 else out.shape[1],
+            col_off, code, _current_stream(torch, index))
+        return out
+
+    def sentences_embedding_device(self, sentences, mode='mean'):
+        '''One vector per sentence, left on the GPU: `sentences` is a sequence of word sequences; the words are resolved on
+        the device (resolve_rows_device) and each sentence's rows are pooled by bags_embedding_device -- words never
+        become rows on the host. A sentence without words is a zero vector. Returns a float32 (len(sentences), dim) tensor.'''
+        import torch
+        pool_mode(mode)
+        index = self._impl.device()
+        if index == _memb.HOST_DEVICE:
+            raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
+        words = []
+        offsets = np.zeros(len(sentences) + 1, dtype=np.int64)
+        for position, sentence in enumerate(sentences):
+            if isinstance(sentence, (str, bytes)):
+                raise TypeError('a sentence is a sequence of words, not one string')
+            words.extend(sentence)
+            offsets[position + 1] = len(words)
+        if len(words) > 0xFFFFFFFF:
+            raise ValueError('more than 0xFFFFFFFF words in one call')
+        offsets = bag_offsets(offsets, len(words))   # (host-made: checked like a caller's)
+        device = 'cuda:{}'.format(index)
+        rows = self.resolve_rows_device(words) if words else torch.empty((0,), dtype=torch.int32, device=device)
+        on_device = torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).to(device)
+        return self.bags_embedding_device(rows, on_device, mode=mode)
+
+    def bags_embedding(self, rows, offsets, mode='mean'):
+        '''bags_embedding_device for host arrays: numpy row ids and offsets in, a numpy float32 (bags, dim) matrix out.
+        offsets: bags + 1 integers, ascending, within 0 .. len(rows) -- anything else is a ValueError. A reader on a GPU
+        sends the ids and offsets up and brings only bags x dim floats back (PCIe bounds the host API). A device='cpu'
+        reader decodes rows_embedding in bounded chunks and adds them in entry order in numpy: the same bits.'''
+        code = pool_mode(mode)
+        rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        offsets = bag_offsets(offsets, rows.size)
+        bags = offsets.size - 1
+        if self._impl.device() != _memb.HOST_DEVICE:
+            import torch
+            device = 'cuda:{}'.format(self._impl.device())
+            result = self.bags_embedding_device(
+                torch.from_numpy(rows.view(np.int32)).to(device),
+                torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).to(device), mode=mode)
+            return result.cpu().numpy()
+        out = np.zeros((bags, self.dim), dtype=np.float32)
+        begins, ends = offsets[:-1], offsets[1:]
+        for start in range(0, rows.size, BAGS_HOST_CHUNK):
+            stop = min(rows.size, start + BAGS_HOST_CHUNK)
+            first = int(np.searchsorted(ends, start, side='right'))    # the first bag that ends behind `start`
+            last = int(np.searchsorted(begins, stop, side='left'))     # bags below this one begin before `stop`
+            bag = np.arange(first, last)
+            low = np.maximum(begins[first:last], start)
+            high = np.minimum(ends[first:last], stop)
+            fresh = begins[first:last] >= start                        # the bag's first entry lies in this chunk
+            keep = high > low
+            bag, low, high, fresh = bag[keep], low[keep], high[keep], fresh[keep]
+            if not bag.size:
+                continue
+            values = self.rows_embedding(rows[start:stop])
+            for step in range(int((high - low).max())):
+                active = (high - low) > step
+                addend = values[low[active] + step - start]
+                target = bag[active]
+                if step == 0:
+                    begun = fresh[active]
+                    out[target[begun]] = addend[begun]
+                    out[target[~begun]] = out[target[~begun]] + addend[~begun]
+                else:
+                    out[target] = out[target] + addend
+        if code == _memb.POOL_MEAN:
+            counts = (ends - begins).astype(np.float32)
+            filled = counts > 0
+            out[filled] = out[filled] / counts[filled][:, None]
         return out
 
     def stage_words(self):

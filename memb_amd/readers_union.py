@@ -115,6 +115,12 @@ class ReadersUnion(BaseReader):
                 ids, out=merged, accumulate=position > 0, divisor=float(count) if position == count - 1 else 0.0)
         return merged
 
+    def bags_embedding_device(self, *args, **kwargs):
+        """Pooled lookups exist for a single Reader only (Reader.bags_embedding_device)"""
+        raise NotImplementedError('pooled lookups of a ReadersUnion are not built: pool each Reader and merge the results')
+
+    bags_embedding = sentences_embedding_device = bags_embedding_device
+
     def tokenizer_embedding(self, tokenizer):
         """Embedding-layer weights for a keras Tokenizer, merged over the readers"""
         return self.batch_embedding(tokenizer_word_list(tokenizer))

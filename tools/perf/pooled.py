@@ -1,0 +1,147 @@
+"""Pooled lookups (bags_embedding_device) against the two-step path a caller had before -- rows_embedding_device into an
+fp32 temporary, then a torch reduction over the bags -- on ONE Reader, with an A/A control.
+
+    python tools/perf/pooled.py [--rounds 5] [--reps 10] [--words 2196017] [--out FILE.json]
+
+Per configuration and round, in an order that alternates between rounds, the mean device time (CUDA events around `reps`
+calls after a warm-up) of
+    pooled     bags_embedding_device(rows, offsets, mode='mean', out=...)
+    pooledb    the same again: the A/A spread below which no difference stands
+    two_step   rows_embedding_device(rows, out=fp32), then out.index_add_(0, bag_of_entry, fp32) and a division by the counts
+    two_step_sr  the same decode, then torch.segment_reduce(fp32, 'mean', offsets=...) (where this torch has it on the GPU)
+The reductions of the two-step paths may add in another order: they are there for their time only.
+Configurations: seeded geometric bag lengths of mean 4, 16 and 64 over 100 000 entries and over `words` entries, row ids in
+key order and shuffled, on the 4-bit and the 6-bit trained model of `words` words and on the 500 000-word uniform model.
+Reports medians over rounds and, for the pooled call, the fraction of 8 TB/s that its algorithmic bytes stand for
+(memb_hip_pooled_algorithmic_bytes, DESIGN.md section 5.6: per entry the id, the metadata and the stream, per bag two
+offsets and 4 dim bytes).
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+import numpy as np
+import torch
+
+import memb_amd
+from memb_amd import synthetic
+
+HBM_BYTES_PER_S = 8.0e12   # MI355X_MICROARCH.md
+
+
+def timed(call, reps):
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    call()
+    start.record()
+    for _ in range(reps):
+        call()
+    stop.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(stop) / reps
+
+
+def bag_offsets(entries, mean_length, seed):
+    """seeded geometric bag lengths of this mean that cover `entries` entries exactly"""
+    rng = np.random.default_rng(seed)
+    lengths = rng.geometric(1.0 / mean_length, size=int(entries / mean_length * 1.2) + 16)
+    offsets = np.concatenate([[0], np.cumsum(lengths)])
+    offsets = offsets[:np.searchsorted(offsets, entries)]
+    return np.append(offsets, entries).astype(np.int64)
+
+
+def measure(reader, rows, offsets, rounds, reps):
+    n, bags, dim = rows.numel(), len(offsets) - 1, reader.dim
+    device_offsets = torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).cuda()
+    long_offsets = torch.from_numpy(offsets).cuda()
+    counts = (long_offsets[1:] - long_offsets[:-1])
+    bag_of_entry = torch.repeat_interleave(torch.arange(bags, device='cuda'), counts)
+    divisor = counts.clamp(min=1).to(torch.float32)[:, None]
+    fp32 = torch.empty((n, dim), dtype=torch.float32, device='cuda')
+    pooled = torch.empty((bags, dim), dtype=torch.float32, device='cuda')
+    reduced = torch.empty((bags, dim), dtype=torch.float32, device='cuda')
+
+    def two_step():
+        reader.rows_embedding_device(rows, out=fp32)
+        reduced.zero_()
+        reduced.index_add_(0, bag_of_entry, fp32)
+        reduced.div_(divisor)
+
+    def two_step_sr():
+        reader.rows_embedding_device(rows, out=fp32)
+        return torch.segment_reduce(fp32, 'mean', offsets=long_offsets, axis=0, initial=0.0)
+
+    variants = {
+        'pooled': lambda: reader.bags_embedding_device(rows, device_offsets, mode='mean', out=pooled),
+        'pooledb': lambda: reader.bags_embedding_device(rows, device_offsets, mode='mean', out=pooled),
+        'two_step': two_step,
+    }
+    try:
+        close = torch.allclose(two_step_sr(), reader.bags_embedding_device(rows, device_offsets), rtol=1e-4, atol=1e-5)
+        torch.cuda.synchronize()
+        if close:
+            variants['two_step_sr'] = two_step_sr
+    except (RuntimeError, NotImplementedError, TypeError):
+        pass
+    for call in variants.values():
+        call()
+    torch.cuda.synchronize()
+    # the paths agree (to the reassociation of the torch reduction) before anything is timed
+    assert torch.allclose(pooled, reduced, rtol=1e-4, atol=1e-5)
+    times = {name: [] for name in variants}
+    names = list(variants)
+    for round_ in range(rounds):
+        for name in (names if round_ % 2 == 0 else names[::-1]):
+            times[name].append(timed(variants[name], reps))
+    result = {name: {'median_ms': float(np.median(values)), 'ms': values} for name, values in times.items()}
+    best_two_step = min(result[name]['median_ms'] for name in result if name.startswith('two_step'))
+    pooled_ms = result['pooled']['median_ms']
+    algorithmic = reader._impl.pooled_algorithmic_bytes(rows.cpu().numpy().view(np.uint32), offsets.astype(np.uint32))
+    result['summary'] = {
+        'entries': n, 'bags': bags, 'pooled_ms': pooled_ms, 'two_step_ms': best_two_step,
+        'aa_spread': abs(result['pooledb']['median_ms'] - pooled_ms) / pooled_ms,
+        'speedup': best_two_step / pooled_ms,
+        'algorithmic_bytes': algorithmic, 'bytes_per_entry': algorithmic / n,
+        'frac_of_8TBps': algorithmic / (pooled_ms / 1e3) / HBM_BYTES_PER_S,
+    }
+    return result
+
+
+def main():
+    parser = argparse.ArgumentParser()
+    parser.add_argument('--rounds', type=int, default=5)
+    parser.add_argument('--reps', type=int, default=10)
+    parser.add_argument('--words', type=int, default=2196017)
+    parser.add_argument('--out', default='')
+    args = parser.parse_args()
+    if not torch.cuda.is_available() or memb_amd.hip_device_count() < 1:
+        raise SystemExit('pooled.py measures on a GPU; none found')
+    results = {}
+    generator = torch.Generator(device='cuda').manual_seed(1)
+    for label, words, storage, bits in (('4bit', args.words, 'trained', 4), ('6bit', args.words, 'trained', 6),
+                                        ('uniform_8bit_500k', 500000, 'uniform', 8)):
+        path, _ = synthetic.cached_model(words, 300, storage, bits)
+        reader = memb_amd.Reader(path)
+        for entries in sorted({100000, words}):
+            in_order = torch.arange(entries, dtype=torch.int32, device='cuda') if entries == words else \
+                torch.sort(torch.randint(0, words, (entries,), device='cuda', generator=generator, dtype=torch.int32)).values
+            orders = {'key_order': in_order,
+                      'shuffled': in_order[torch.randperm(entries, device='cuda', generator=generator)].contiguous()}
+            for order, rows in orders.items():
+                for mean_length in (4, 16, 64):
+                    name = '{}_{}_{}_bags_of_{}'.format(label, entries, order, mean_length)
+                    results[name] = measure(reader, rows, bag_offsets(entries, mean_length, mean_length), args.rounds, args.reps)
+                    summary = results[name]['summary']
+                    print('{:48s} pooled {:.4f} ms  A/A {:.1%}  two-step {:.4f} ms  x{:.2f}  {:.0f} B/entry  {:.3f} of 8 TB/s'.format(
+                        name, summary['pooled_ms'], summary['aa_spread'], summary['two_step_ms'], summary['speedup'],
+                        summary['bytes_per_entry'], summary['frac_of_8TBps']), flush=True)
+                    if args.out:   # (kept up to date: a run that is cut short leaves what it measured)
+                        with open(args.out, 'w') as f:
+                            json.dump(results, f, indent=1)
+        del reader
+        torch.cuda.empty_cache()
+
+
+if __name__ == '__main__':
+    main()
