@@ -925,11 +925,11 @@ PYBIND11_MODULE(_memb, m) {
         .def(
             "pool_rows_to_device",
             [](memb::Reader& reader, uintptr_t rows, size_t n, uintptr_t offsets, size_t bags, uintptr_t out, size_t ld,
-               size_t colOff, int mode, uintptr_t stream)
+               size_t colOff, int mode, uintptr_t stream, int outType)
             {
                 reader.poolRowsDevice(
                     reinterpret_cast<const uint32_t*>(rows), n, reinterpret_cast<const uint32_t*>(offsets), bags,
-                    reinterpret_cast<float*>(out), ld, colOff, mode, reinterpret_cast<void*>(stream));
+                    reinterpret_cast<void*>(out), outType, ld, colOff, mode, reinterpret_cast<void*>(stream));
             },
             py::arg("rows_ptr"),
             py::arg("n"),
@@ -939,26 +939,29 @@ PYBIND11_MODULE(_memb, m) {
             py::arg("ld"),
             py::arg("col_off") = 0,
             py::arg("mode") = MEMB_HIP_POOL_MEAN,
-            py::arg("stream") = 0)
+            py::arg("stream") = 0,
+            py::arg("out_type") = MEMB_HIP_OUT_F32)
         .def(
             "pooled_algorithmic_bytes",
             [](memb::Reader& reader,
                py::array_t<uint32_t, py::array::c_style | py::array::forcecast> rows,
-               py::array_t<uint32_t, py::array::c_style | py::array::forcecast> offsets)
+               py::array_t<uint32_t, py::array::c_style | py::array::forcecast> offsets,
+               int outType)
             {
                 if (offsets.size() < 1) {
                     throw std::invalid_argument("offsets needs bags + 1 entries");
                 }
                 uint64_t bytes = 0;
-                if (memb_hip_pooled_algorithmic_bytes(
+                if (memb_hip_pooled_algorithmic_bytes_typed(
                         reader.deviceContext(), rows.data(), static_cast<size_t>(rows.size()), offsets.data(),
-                        static_cast<size_t>(offsets.size() - 1), &bytes) != MEMB_HIP_OK) {
-                    throw std::runtime_error(std::string("memb_hip_pooled_algorithmic_bytes: ") + memb_hip_last_error());
+                        static_cast<size_t>(offsets.size() - 1), outType, &bytes) != MEMB_HIP_OK) {
+                    throw std::runtime_error(std::string("memb_hip_pooled_algorithmic_bytes_typed: ") + memb_hip_last_error());
                 }
                 return bytes;
             },
             py::arg("rows"),
-            py::arg("offsets"));
+            py::arg("offsets"),
+            py::arg("out_type") = MEMB_HIP_OUT_F32);
 
     m.attr("OUT_F32") = MEMB_HIP_OUT_F32;
     m.attr("OUT_BF16") = MEMB_HIP_OUT_BF16;

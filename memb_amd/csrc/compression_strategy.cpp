@@ -149,13 +149,14 @@ void CompressedStorage::decodeRowsDeviceTyped(
 }
 
 void CompressedStorage::poolRowsDevice(
-    const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, float* out, size_t ld, size_t colOff, int mode,
-    void* stream) const
+    const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int outType, size_t ld, size_t colOff,
+    int mode, void* stream) const
 {
     if (onHost()) {
         throw std::runtime_error("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device");
     }
-    if (memb_hip_pool_rows_device(deviceContext(), rows, n, offsets, bags, out, ld, colOff, mode, stream) != MEMB_HIP_OK) {
+    if (memb_hip_pool_rows_device_typed(deviceContext(), rows, n, offsets, bags, out, outType, ld, colOff, mode, stream) !=
+        MEMB_HIP_OK) {
         throwDeviceError("HIP pooled lookup failed");
     }
 }

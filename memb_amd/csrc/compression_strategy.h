@@ -66,10 +66,11 @@ public:
     void decodeRowsDeviceTyped(
         const uint32_t* rows, size_t n, void* out, int outType, size_t ld, size_t colOff, void* stream) const;
     // The sum or mean (mode: MEMB_HIP_POOL_*) of each bag of rows, device buffers (include/memb_hip_pooled.h): bag b =
-    // rows[offsets[b] .. offsets[b + 1]) goes to out[b * ld + colOff ..].
+    // rows[offsets[b] .. offsets[b + 1]) goes to out[b * ld + colOff ..], as elements of outType (MEMB_HIP_OUT_*; ld and
+    // colOff count elements).
     void poolRowsDevice(
-        const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, float* out, size_t ld, size_t colOff, int mode,
-        void* stream) const;
+        const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int outType, size_t ld, size_t colOff,
+        int mode, void* stream) const;
 
     // device == HOST_DEVICE: rows are decoded by extractRowHost on host threads
     static constexpr int HOST_DEVICE = -2;

@@ -1366,6 +1366,8 @@ int launch(memb_hip_ctx* ctx, const Lookup& lookup, hipStream_t stream)
 // that kernel up to the symbol tile -- and a wavefront owns a run of consecutive bags sized so that it decodes about
 // POOLED_TILES_PER_WAVE tiles (option tiles_per_wave: that many), fewer while the grid would not fill the CUs. A bag is
 // never split: ONE enormous bag is walked by one wavefront, correct and slow.
+// Bags' rows of a narrow outType run the kernels of memb_hip_pooled_narrow.hip on the same plan: they add fp32 centroids,
+// so LDS is planned for an fp32 codebook whatever the element, and only the choice of the piece form follows it.
 constexpr uint32_t POOLED_TILES_PER_WAVE = 4;
 
 int launchPooled(memb_hip_ctx* ctx, const Lookup& lookup, memb_pooled::PoolParams pool, hipStream_t stream)
@@ -1382,10 +1384,12 @@ int launchPooled(memb_hip_ctx* ctx, const Lookup& lookup, memb_pooled::PoolParam
     uint32_t waves = memb_pooled::ROWWISE_WAVES;
     uint32_t ldsBytes = 0;
     pool.bagsPerWave = 1;
+    const bool narrow = lookup.outType != MEMB_HIP_OUT_F32;
     switch (ctx->storage) {
         case memb::wire::Storage_Trained: {
             Lookup planned = lookup;
             planned.n = std::max<size_t>(lookup.n, 1);
+            planned.outType = MEMB_HIP_OUT_F32;
             TrainedPlan plan;
             const int code = planTrained(ctx, planned, 0, false, rowsUnordered(ctx, false), &plan);
             if (code != MEMB_HIP_OK) {
@@ -1404,7 +1408,9 @@ int launchPooled(memb_hip_ctx* ctx, const Lookup& lookup, memb_pooled::PoolParam
             if (!lookupParamsConsistent(ctx, trained, geometry) || lookup.ld < lookup.colOff + trained.dim) {
                 return fail(MEMB_HIP_ERR_INVALID, "internal error: inconsistent decode geometry");
             }
-            const bool vec4 = geometry.mode != OUT_SCALAR && ctx->dim <= memb_pooled::TRAINED_VEC4_MAX_DIM;
+            const bool pieces =
+                outputMode(ctx->dim, lookup.ld, lookup.colOff, lookup.out, lookup.elementBytes(), trained.wordsPerWave) != OUT_SCALAR;
+            const bool vec4 = pieces && ctx->dim <= memb_pooled::TRAINED_VEC4_MAX_DIM;
             waves = geometry.waves;
             ldsBytes = geometry.ldsBytes;
             const uint64_t tilesPerWave = ctx->switches.tilesPerWave ? ctx->switches.tilesPerWave : POOLED_TILES_PER_WAVE;
@@ -1412,7 +1418,8 @@ int launchPooled(memb_hip_ctx* ctx, const Lookup& lookup, memb_pooled::PoolParam
             const uint64_t fillsTheCus = std::max<uint64_t>(1, pool.bags / (uint64_t(ctx->cuCount) * ONE_TILE_WAVES_PER_CU));
             pool.bagsPerWave = static_cast<uint32_t>(std::min<uint64_t>(
                 std::min<uint64_t>(std::max<uint64_t>(1, tilesPerWave * trained.wordsPerWave / entriesPerBag), fillsTheCus), 1u << 16));
-            kernel = memb_pooled::trainedKernel(lookupHasSub(ctx), ctx->fast, vec4);
+            kernel = narrow ? memb_pooled::trainedKernelNarrow(lookupHasSub(ctx), ctx->fast, vec4, lookup.outType)
+                            : memb_pooled::trainedKernel(lookupHasSub(ctx), ctx->fast, vec4);
             name = "pool_trained";
             arguments[0] = &trained;
             break;
@@ -1422,19 +1429,22 @@ int launchPooled(memb_hip_ctx* ctx, const Lookup& lookup, memb_pooled::PoolParam
             uniform.records = ctx->uniformRecords;
             uniform.regionPieces = ctx->regionPieces;
             uniform.levels = ctx->levels;
-            kernel = memb_pooled::uniformKernel();
+            kernel = narrow ? memb_pooled::uniformKernelNarrow(lookup.outType) : memb_pooled::uniformKernel();
             name = "pool_uniform";
             arguments[0] = &uniform;
             break;
         case memb::wire::Storage_Full:
             full = rowwiseParams<FullParams>(ctx, lookup);
             full.values = ctx->fullValues;
-            kernel = memb_pooled::fullKernel();
+            kernel = narrow ? memb_pooled::fullKernelNarrow(lookup.outType) : memb_pooled::fullKernel();
             name = "pool_full";
             arguments[0] = &full;
             break;
         default:
             return fail(MEMB_HIP_ERR_INVALID, "context has no storage");
+    }
+    if (!kernel) {
+        return fail(MEMB_HIP_ERR_INVALID, std::string("internal error: no ") + name + " kernel for this output");
     }
     const uint64_t perBlock = uint64_t(waves) * pool.bagsPerWave;
     const uint64_t blocks = (pool.bags + perBlock - 1) / perBlock;
@@ -2418,18 +2428,27 @@ int decode_rows_device_typed_checked(
     return launch(ctx, Lookup{rows, n, out, outType, ld, col_off}, static_cast<hipStream_t>(stream));
 }
 
+bool knownOutType(int outType)
+{
+    return outType == MEMB_HIP_OUT_F32 || outType == MEMB_HIP_OUT_BF16 || outType == MEMB_HIP_OUT_F16;
+}
+
 int pool_rows_device_checked(
-    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, float* out, size_t ld,
+    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int outType, size_t ld,
     size_t col_off, int mode, void* stream)
 {
+    if (!knownOutType(outType)) {
+        return fail(MEMB_HIP_ERR_INVALID, "unknown out_type " + std::to_string(outType));
+    }
     if (mode != MEMB_HIP_POOL_SUM && mode != MEMB_HIP_POOL_MEAN) {
         return fail(MEMB_HIP_ERR_INVALID, "unknown pooling mode " + std::to_string(mode));
     }
     if (!ctx || (n && !rows) || (bags && (!offsets || !out))) {
         return fail(MEMB_HIP_ERR_INVALID, "null argument");
     }
-    if (reinterpret_cast<uintptr_t>(out) % sizeof(float) != 0) {
-        return fail(MEMB_HIP_ERR_INVALID, "out must be aligned to its element (4 bytes)");
+    const size_t elementBytes = outType == MEMB_HIP_OUT_F32 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(out) % elementBytes != 0) {
+        return fail(MEMB_HIP_ERR_INVALID, "out must be aligned to its element (" + std::to_string(elementBytes) + " bytes)");
     }
     if (col_off > ld || ld - col_off < ctx->dim) {
         return fail(MEMB_HIP_ERR_INVALID, "ld must be at least col_off + dim");
@@ -2443,18 +2462,22 @@ int pool_rows_device_checked(
     pool.offsets = offsets;
     pool.bags = bags;
     pool.mean = mode == MEMB_HIP_POOL_MEAN ? 1u : 0u;
-    return launchPooled(ctx, floatRows(rows, n, out, ld, col_off), pool, static_cast<hipStream_t>(stream));
+    return launchPooled(ctx, Lookup{rows, n, out, outType, ld, col_off}, pool, static_cast<hipStream_t>(stream));
 }
 
 int pooled_algorithmic_bytes_checked(
-    const memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, uint64_t* bytes)
+    const memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, int outType, uint64_t* bytes)
 {
+    if (!knownOutType(outType)) {
+        return fail(MEMB_HIP_ERR_INVALID, "unknown out_type " + std::to_string(outType));
+    }
     if (!ctx || !bytes || (n && !rows) || (bags && !offsets)) {
         return fail(MEMB_HIP_ERR_INVALID, "null argument");
     }
+    const uint64_t elementBytes = outType == MEMB_HIP_OUT_F32 ? 4 : 2;
     uint64_t total = 0;
     for (size_t bag = 0; bag < bags; ++bag) {
-        total += 8 + 4ull * ctx->dim;
+        total += 8 + elementBytes * ctx->dim;
         const size_t begin = std::min<size_t>(offsets[bag], n);
         const size_t end = std::min<size_t>(offsets[bag + 1], n);
         for (size_t i = begin; i < end; ++i) {
@@ -2875,13 +2898,28 @@ int memb_hip_pool_rows_device(
     memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, float* out, size_t ld,
     size_t col_off, int mode, void* stream)
 {
-    return guarded([&] { return pool_rows_device_checked(ctx, rows, n, offsets, bags, out, ld, col_off, mode, stream); });
+    return guarded([&] {
+        return pool_rows_device_checked(ctx, rows, n, offsets, bags, out, MEMB_HIP_OUT_F32, ld, col_off, mode, stream);
+    });
+}
+
+int memb_hip_pool_rows_device_typed(
+    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int out_type, size_t ld,
+    size_t col_off, int mode, void* stream)
+{
+    return guarded([&] { return pool_rows_device_checked(ctx, rows, n, offsets, bags, out, out_type, ld, col_off, mode, stream); });
 }
 
 int memb_hip_pooled_algorithmic_bytes(
     const memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, uint64_t* bytes)
 {
-    return guarded([&] { return pooled_algorithmic_bytes_checked(ctx, rows, n, offsets, bags, bytes); });
+    return guarded([&] { return pooled_algorithmic_bytes_checked(ctx, rows, n, offsets, bags, MEMB_HIP_OUT_F32, bytes); });
+}
+
+int memb_hip_pooled_algorithmic_bytes_typed(
+    const memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, int out_type, uint64_t* bytes)
+{
+    return guarded([&] { return pooled_algorithmic_bytes_checked(ctx, rows, n, offsets, bags, out_type, bytes); });
 }
 
 int memb_hip_decode_batches_device(memb_hip_ctx* ctx, const memb_hip_batch* batches, size_t count, void* stream)

@@ -457,10 +457,10 @@ void Reader::rowsToDeviceBufferTyped(
 }
 
 void Reader::poolRowsDevice(
-    const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, float* buffer, size_t ld, size_t colOff, int mode,
-    void* stream) const
+    const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* buffer, int outType, size_t ld, size_t colOff,
+    int mode, void* stream) const
 {
-    compressedStorage_->poolRowsDevice(rows, n, offsets, bags, buffer, ld, colOff, mode, stream);
+    compressedStorage_->poolRowsDevice(rows, n, offsets, bags, buffer, outType, ld, colOff, mode, stream);
 }
 
 std::vector<float> Reader::wordEmbedding(const std::string& word) const

@@ -115,10 +115,11 @@ public:
     void rowsToDeviceBufferTyped(
         const uint32_t* rows, size_t n, void* buffer, int outType, size_t ld, size_t colOff, void* stream) const;
     // Pooled device lookup (include/memb_hip_pooled.h): the sum or mean (mode: MEMB_HIP_POOL_*) of each bag
-    // rows[offsets[b] .. offsets[b + 1]) goes to buffer[b * ld + colOff .. + dim); all three are device pointers.
+    // rows[offsets[b] .. offsets[b + 1]) goes to buffer[b * ld + colOff .. + dim), as elements of outType (MEMB_HIP_OUT_*;
+    // ld and colOff count elements); all three are device pointers.
     void poolRowsDevice(
-        const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, float* buffer, size_t ld, size_t colOff,
-        int mode, void* stream) const;
+        const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* buffer, int outType, size_t ld,
+        size_t colOff, int mode, void* stream) const;
 
     // Several device-buffer lookups in one kernel launch (include/memb_hip.h: memb_hip_decode_batches_device).
     void batchesToDeviceBuffers(const memb_hip_batch* batches, size_t count, void* stream) const;

@@ -314,10 +314,10 @@ class Reader(BaseReader):
             order == 'random')
         return out
 
-    def bags_embedding_device(self, rows, offsets, mode='mean', out=None, col_off=0):
+    def bags_embedding_device(self, rows, offsets, mode='mean', out=None, col_off=0, dtype=None):
         '''Pooled lookup that never leaves the GPU: the sum or mean of each bag of rows, decoded and reduced by one kernel
         (the EmbeddingBag counterpart of rows_embedding_device). The bags' rows are never written: per entry the kernel
-        reads the row id and the compressed row, per bag it stores dim floats.
+        reads the row id and the compressed row, per bag it stores dim elements.
         Parameters
         ----------
         rows : torch.Tensor, as in rows_embedding_device (n entries)
@@ -327,8 +327,13 @@ class Reader(BaseReader):
         mode : 'mean' or 'sum'. Both add a bag's float32 rows one after the other in entry order (a row that is not in
             the model is +0.0 and counts); 'mean' then divides once by the entry count. An empty bag is +0.0, a bag of
             one entry that row's bits. Bit for bit the result of that loop over rows_embedding_device(rows).
-        out : float32 torch.Tensor (bags, >= col_off + dim) with unit column stride on the same device, optional
-        No bf16 / fp16 output, no accumulate into `out`, no per-entry weights, no 'max'.
+        out : torch.Tensor (bags, >= col_off + dim) with unit column stride on the same device, optional: float32, or of
+            `dtype` where one is given
+        dtype : None (float32), torch.float32, torch.bfloat16 or torch.float16. A bf16 / fp16 result is the float32 result
+            rounded once to nearest even (the bits of .to(dtype)): the sums and the division stay float32 and only the
+            finished value is narrowed as the same kernel stores it -- no float32 (bags, dim) temporary, no second kernel. A
+            narrow result is asked for by name: a bf16 / fp16 `out` without `dtype` is a TypeError.
+        No accumulate into `out`, no per-entry weights, no 'max'.
         '''
         import torch
         code = pool_mode(mode)
@@ -344,26 +349,34 @@ class Reader(BaseReader):
         if offsets.numel() < 1:
             raise ValueError('offsets needs bags + 1 entries')
         bags = offsets.numel() - 1
+        if dtype is None:
+            if out is not None and out.dtype != torch.float32:
+                raise TypeError('out is {}: pooled rows are float32 unless dtype asks for bfloat16 / float16'.format(out.dtype))
+            dtype = torch.float32
+        elif dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise TypeError('dtype must be torch.float32, torch.bfloat16 or torch.float16, not {}'.format(dtype))
+        elif out is not None and out.dtype != dtype:
+            raise TypeError('out is {} but dtype is {}'.format(out.dtype, dtype))
         if out is None:
-            out = torch.empty((bags, col_off + self.dim), dtype=torch.float32, device=device)
-        if out.dtype != torch.float32:
-            raise TypeError('out is {}: pooled rows are float32 (a bf16 / fp16 sum would be rounded after every entry)'.format(out.dtype))
+            out = torch.empty((bags, col_off + self.dim), dtype=dtype, device=device)
         if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] != bags:
-            raise TypeError('out must be a float32 (bags, width) tensor with unit column stride')
+            raise TypeError('out must be a {} (bags, width) tensor with unit column stride'.format(dtype))
         if device.index != index or out.device != device or offsets.device != device:
             raise ValueError('rows, offsets and out must be on cuda:{} (the device this reader is staged on), got {}, {} and {}'.format(
                 self.device, device, offsets.device, out.device))
         if out.shape[1] < col_off + self.dim:
             raise ValueError('out is narrower than col_off + dim')
+        out_type = {torch.float32: _memb.OUT_F32, torch.bfloat16: _memb.OUT_BF16, torch.float16: _memb.OUT_F16}[dtype]
         self._impl.pool_rows_to_device(
             rows.data_ptr(), rows.numel(), offsets.data_ptr(), bags, out.data_ptr(), out.stride(0) if bags > 1 else out.shape[1],
-            col_off, code, _current_stream(torch, index))
+            col_off, code, _current_stream(torch, index), out_type)
         return out
 
-    def sentences_embedding_device(self, sentences, mode='mean'):
+    def sentences_embedding_device(self, sentences, mode='mean', dtype=None):
         '''One vector per sentence, left on the GPU: `sentences` is a sequence of word sequences; the words are resolved on
         the device (resolve_rows_device) and each sentence's rows are pooled by bags_embedding_device -- words never
-        become rows on the host. A sentence without words is a zero vector. Returns a float32 (len(sentences), dim) tensor.'''
+        become rows on the host. A sentence without words is a zero vector. Returns a (len(sentences), dim) tensor of
+        `dtype` (bags_embedding_device: float32 by default; torch.bfloat16 / torch.float16 are that result rounded once).'''
         import torch
         pool_mode(mode)
         index = self._impl.device()
@@ -382,7 +395,7 @@ class Reader(BaseReader):
         device = 'cuda:{}'.format(index)
         rows = self.resolve_rows_device(words) if words else torch.empty((0,), dtype=torch.int32, device=device)
         on_device = torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).to(device)
-        return self.bags_embedding_device(rows, on_device, mode=mode)
+        return self.bags_embedding_device(rows, on_device, mode=mode, dtype=dtype)
 
     def bags_embedding(self, rows, offsets, mode='mean'):
         '''bags_embedding_device for host arrays: numpy row ids and offsets in, a numpy float32 (bags, dim) matrix out.

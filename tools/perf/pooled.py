@@ -2,6 +2,7 @@
 fp32 temporary, then a torch reduction over the bags -- on ONE Reader, with an A/A control.
 
     python tools/perf/pooled.py [--rounds 5] [--reps 10] [--words 2196017] [--out FILE.json]
+                                [--dtype bfloat16|float16] [--lengths 1,4,16,64] [--models 4bit]
 
 Per configuration and round, in an order that alternates between rounds, the mean device time (CUDA events around `reps`
 calls after a warm-up) of
@@ -15,6 +16,10 @@ key order and shuffled, on the 4-bit and the 6-bit trained model of `words` word
 Reports medians over rounds and, for the pooled call, the fraction of 8 TB/s that its algorithmic bytes stand for
 (memb_hip_pooled_algorithmic_bytes, DESIGN.md section 5.6: per entry the id, the metadata and the stream, per bag two
 offsets and 4 dim bytes).
+With --dtype bfloat16 / float16 `pooled` and `pooledb` are the one-kernel narrow call (dtype=...), and two more variants are
+timed in the same rounds: `fp32_then_cast` (the float32 pooled call, then .to(dtype): what a caller had before) and `fp32`
+(the float32 pooled call alone). The fraction of 8 TB/s then comes from the typed byte count
+(memb_hip_pooled_algorithmic_bytes_typed: 2 dim bytes stored per bag); the two-step paths are left out.
 """
 import argparse
 import json
@@ -49,6 +54,52 @@ def bag_offsets(entries, mean_length, seed):
     offsets = np.concatenate([[0], np.cumsum(lengths)])
     offsets = offsets[:np.searchsorted(offsets, entries)]
     return np.append(offsets, entries).astype(np.int64)
+
+
+OUT_TYPES = {'float32': (torch.float32, 0), 'bfloat16': (torch.bfloat16, 1), 'float16': (torch.float16, 2)}   # MEMB_HIP_OUT_*
+
+
+def measure_narrow(reader, rows, offsets, rounds, reps, dtype_name):
+    dtype, out_type = OUT_TYPES[dtype_name]
+    n, bags, dim = rows.numel(), len(offsets) - 1, reader.dim
+    device_offsets = torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).cuda()
+    narrow = torch.empty((bags, dim), dtype=dtype, device='cuda')
+    fp32 = torch.empty((bags, dim), dtype=torch.float32, device='cuda')
+    cast = torch.empty((bags, dim), dtype=dtype, device='cuda')
+
+    def fp32_then_cast():
+        reader.bags_embedding_device(rows, device_offsets, mode='mean', out=fp32)
+        cast.copy_(fp32)
+
+    variants = {
+        'pooled': lambda: reader.bags_embedding_device(rows, device_offsets, mode='mean', out=narrow, dtype=dtype),
+        'pooledb': lambda: reader.bags_embedding_device(rows, device_offsets, mode='mean', out=narrow, dtype=dtype),
+        'fp32_then_cast': fp32_then_cast,
+        'fp32': lambda: reader.bags_embedding_device(rows, device_offsets, mode='mean', out=fp32),
+    }
+    for call in variants.values():
+        call()
+    torch.cuda.synchronize()
+    assert torch.equal(narrow.view(torch.int16), cast.view(torch.int16))   # the same bits before anything is timed
+    times = {name: [] for name in variants}
+    names = list(variants)
+    for round_ in range(rounds):
+        for name in (names if round_ % 2 == 0 else names[::-1]):
+            times[name].append(timed(variants[name], reps))
+    result = {name: {'median_ms': float(np.median(values)), 'ms': values} for name, values in times.items()}
+    host_rows, host_offsets = rows.cpu().numpy().view(np.uint32), offsets.astype(np.uint32)
+    typed = reader._impl.pooled_algorithmic_bytes(host_rows, host_offsets, out_type)
+    fp32_bytes = reader._impl.pooled_algorithmic_bytes(host_rows, host_offsets)
+    pooled_ms = result['pooled']['median_ms']
+    result['summary'] = {
+        'dtype': dtype_name, 'entries': n, 'bags': bags, 'pooled_ms': pooled_ms,
+        'fp32_then_cast_ms': result['fp32_then_cast']['median_ms'], 'fp32_ms': result['fp32']['median_ms'],
+        'aa_spread': abs(result['pooledb']['median_ms'] - pooled_ms) / pooled_ms,
+        'algorithmic_bytes': typed, 'fp32_algorithmic_bytes': fp32_bytes, 'bytes_ratio': typed / fp32_bytes,
+        'frac_of_8TBps': typed / (pooled_ms / 1e3) / HBM_BYTES_PER_S,
+        'fp32_frac_of_8TBps': fp32_bytes / (result['fp32']['median_ms'] / 1e3) / HBM_BYTES_PER_S,
+    }
+    return result
 
 
 def measure(reader, rows, offsets, rounds, reps):
@@ -114,13 +165,19 @@ def main():
     parser.add_argument('--reps', type=int, default=10)
     parser.add_argument('--words', type=int, default=2196017)
     parser.add_argument('--out', default='')
+    parser.add_argument('--dtype', default='float32', choices=sorted(OUT_TYPES))
+    parser.add_argument('--lengths', default='4,16,64', help='mean bag lengths (1: every bag one entry)')
+    parser.add_argument('--models', default='4bit,6bit,uniform_8bit_500k')
     args = parser.parse_args()
+    lengths = [int(length) for length in args.lengths.split(',')]
     if not torch.cuda.is_available() or memb_amd.hip_device_count() < 1:
         raise SystemExit('pooled.py measures on a GPU; none found')
     results = {}
     generator = torch.Generator(device='cuda').manual_seed(1)
     for label, words, storage, bits in (('4bit', args.words, 'trained', 4), ('6bit', args.words, 'trained', 6),
                                         ('uniform_8bit_500k', 500000, 'uniform', 8)):
+        if label not in args.models.split(','):
+            continue
         path, _ = synthetic.cached_model(words, 300, storage, bits)
         reader = memb_amd.Reader(path)
         for entries in sorted({100000, words}):
@@ -129,9 +186,20 @@ def main():
             orders = {'key_order': in_order,
                       'shuffled': in_order[torch.randperm(entries, device='cuda', generator=generator)].contiguous()}
             for order, rows in orders.items():
-                for mean_length in (4, 16, 64):
+                for mean_length in lengths:
                     name = '{}_{}_{}_bags_of_{}'.format(label, entries, order, mean_length)
-                    results[name] = measure(reader, rows, bag_offsets(entries, mean_length, mean_length), args.rounds, args.reps)
+                    offsets = bag_offsets(entries, mean_length, mean_length)
+                    if args.dtype != 'float32':
+                        results[name] = measure_narrow(reader, rows, offsets, args.rounds, args.reps, args.dtype)
+                        summary = results[name]['summary']
+                        print('{:48s} {} {:.4f} ms  A/A {:.1%}  fp32 + cast {:.4f} ms  fp32 {:.4f} ms  bytes x{:.3f}  {:.3f} of 8 TB/s'.format(
+                            name, args.dtype, summary['pooled_ms'], summary['aa_spread'], summary['fp32_then_cast_ms'], summary['fp32_ms'],
+                            summary['bytes_ratio'], summary['frac_of_8TBps']), flush=True)
+                        if args.out:
+                            with open(args.out, 'w') as f:
+                                json.dump(results, f, indent=1)
+                        continue
+                    results[name] = measure(reader, rows, offsets, args.rounds, args.reps)
                     summary = results[name]['summary']
                     print('{:48s} pooled {:.4f} ms  A/A {:.1%}  two-step {:.4f} ms  x{:.2f}  {:.0f} B/entry  {:.3f} of 8 TB/s'.format(
                         name, summary['pooled_ms'], summary['aa_spread'], summary['two_step_ms'], summary['speedup'],
