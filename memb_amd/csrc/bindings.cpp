@@ -942,6 +942,27 @@ PYBIND11_MODULE(_memb, m) {
             py::arg("stream") = 0,
             py::arg("out_type") = MEMB_HIP_OUT_F32)
         .def(
+            "pool_known_rows_to_device",
+            [](memb::Reader& reader, uintptr_t rows, size_t n, uintptr_t offsets, size_t bags, uintptr_t out, size_t ld,
+               size_t colOff, int mode, uintptr_t stream, int outType, uintptr_t counts)
+            {
+                reader.poolKnownRowsDevice(
+                    reinterpret_cast<const uint32_t*>(rows), n, reinterpret_cast<const uint32_t*>(offsets), bags,
+                    reinterpret_cast<void*>(out), outType, ld, colOff, mode, reinterpret_cast<uint32_t*>(counts),
+                    reinterpret_cast<void*>(stream));
+            },
+            py::arg("rows_ptr"),
+            py::arg("n"),
+            py::arg("offsets_ptr"),
+            py::arg("bags"),
+            py::arg("out_ptr"),
+            py::arg("ld"),
+            py::arg("col_off") = 0,
+            py::arg("mode") = MEMB_HIP_POOL_MEAN,
+            py::arg("stream") = 0,
+            py::arg("out_type") = MEMB_HIP_OUT_F32,
+            py::arg("counts_ptr") = 0)
+        .def(
             "pooled_algorithmic_bytes",
             [](memb::Reader& reader,
                py::array_t<uint32_t, py::array::c_style | py::array::forcecast> rows,

@@ -161,6 +161,19 @@ void CompressedStorage::poolRowsDevice(
     }
 }
 
+void CompressedStorage::poolKnownRowsDevice(
+    const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int outType, size_t ld, size_t colOff,
+    int mode, uint32_t* counts, void* stream) const
+{
+    if (onHost()) {
+        throw std::runtime_error("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device");
+    }
+    if (memb_hip_pool_known_rows_device_typed(
+            deviceContext(), rows, n, offsets, bags, out, outType, ld, colOff, mode, counts, stream) != MEMB_HIP_OK) {
+        throwDeviceError("HIP pooled lookup failed");
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Word -> row on the device
 // ---------------------------------------------------------------------------

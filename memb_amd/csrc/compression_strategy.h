@@ -19,6 +19,7 @@
 #include "../../include/memb_hip.h"
 #include "../../include/memb_hip_narrow.h"
 #include "../../include/memb_hip_pooled.h"
+#include "../../include/memb_hip_pooled_known.h"
 
 #include <atomic>
 #include <memory>
@@ -71,6 +72,10 @@ public:
     void poolRowsDevice(
         const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int outType, size_t ld, size_t colOff,
         int mode, void* stream) const;
+    // ... over the entries the model knows (include/memb_hip_pooled_known.h); counts: null, or bags entries on the device
+    void poolKnownRowsDevice(
+        const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int outType, size_t ld, size_t colOff,
+        int mode, uint32_t* counts, void* stream) const;
 
     // device == HOST_DEVICE: rows are decoded by extractRowHost on host threads
     static constexpr int HOST_DEVICE = -2;

@@ -30,15 +30,17 @@ __device__ __forceinline__ void bagRange(
 struct PoolTile {
     unsigned long long start = 0;
     unsigned long long end = 0;
-    unsigned long long absent = 0;       // nibble keys: bit w * lanesPerWord = word w is a missing row (outputTile's ballot)
+    unsigned long long absent = 0;       // nibble keys: bit w * lanesPerWord = word w is a missing row (outputTile's ballot);
+                                         // every key form where decodePoolTile is asked for it (ABSENT_MASK)
     unsigned long long nextStart = ~0ull;   // the tile whose row ids are in flight already (nextRow), and its limit
     unsigned long long nextLimit = 0;
     uint32_t nextRow = MISSING;
 };
 
 // decodeTilesOfBlock's body for ONE tile that starts at ANY entry: row ids -> row regions -> LDS slots -> symbol tile.
-// Entries from `limit` (<= n) on are not read; their words decode as missing rows.
-template <bool HAS_SUB, bool FAST>
+// Entries from `limit` (<= n) on are not read; their words decode as missing rows. ABSENT_MASK: tile.absent is filled --
+// what gatherPiece / gatherColumn need for nibble keys only, the kernels that skip missing rows for every key form.
+template <bool HAS_SUB, bool FAST, bool ABSENT_MASK = FAST>
 __device__ __forceinline__ void decodePoolTile(
     const TrainedParams& p, const WaveLds& mem, uint32_t lane, unsigned long long start, unsigned long long limit, PoolTile& tile)
 {
@@ -76,7 +78,7 @@ __device__ __forceinline__ void decodePoolTile(
     recordSegmentBits(p, mem.slots, role, meta);
     decodeSegment<HAS_SUB, OUT_VEC4, FAST, PACKED>(p, mem.table, mem.slots, mem.keyTile, role, meta);
     waveLdsFence();
-    if (FAST) {
+    if (ABSENT_MASK) {
         tile.absent = __ballot(!(meta.row < p.nRows) && !role.spare && role.segment == 0);
     }
 }

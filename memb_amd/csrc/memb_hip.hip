@@ -40,9 +40,11 @@
 #include "../../include/memb_hip.h"
 #include "../../include/memb_hip_narrow.h"
 #include "../../include/memb_hip_pooled.h"
+#include "../../include/memb_hip_pooled_known.h"
 #include "codec.h"
 #include "hip_narrow.h"
 #include "hip_pooled.h"
+#include "hip_pooled_known.h"
 #include "wire.h"
 #include "worker_pool.h"
 
@@ -1368,16 +1370,21 @@ int launch(memb_hip_ctx* ctx, const Lookup& lookup, hipStream_t stream)
 // never split: ONE enormous bag is walked by one wavefront, correct and slow.
 // Bags' rows of a narrow outType run the kernels of memb_hip_pooled_narrow.hip on the same plan: they add fp32 centroids,
 // so LDS is planned for an fp32 codebook whatever the element, and only the choice of the piece form follows it.
+// known (include/memb_hip_pooled_known.h): the kernels of memb_hip_pooled_known.hip, which leave a bag's unknown entries
+// out and take the counts as a third parameter -- the same plan, the same geometry.
 constexpr uint32_t POOLED_TILES_PER_WAVE = 4;
 
-int launchPooled(memb_hip_ctx* ctx, const Lookup& lookup, memb_pooled::PoolParams pool, hipStream_t stream)
+int launchPooled(
+    memb_hip_ctx* ctx, const Lookup& lookup, memb_pooled::PoolParams pool, hipStream_t stream,
+    const memb_pooled::KnownParams* known = nullptr)
 {
     if (lookup.n > (size_t(1) << 37) || pool.bags >= (1ull << 37)) {
         return fail(MEMB_HIP_ERR_INVALID, "batch too large");
     }
     const void* kernel = nullptr;
     const char* name = "";
-    void* arguments[2] = {nullptr, &pool};
+    memb_pooled::KnownParams counted = known ? *known : memb_pooled::KnownParams{};
+    void* arguments[3] = {nullptr, &pool, &counted};   // (the third: kernels of memb_hip_pooled_known.hip only)
     TrainedParams trained;
     UniformParams uniform;
     FullParams full;
@@ -1418,9 +1425,10 @@ int launchPooled(memb_hip_ctx* ctx, const Lookup& lookup, memb_pooled::PoolParam
             const uint64_t fillsTheCus = std::max<uint64_t>(1, pool.bags / (uint64_t(ctx->cuCount) * ONE_TILE_WAVES_PER_CU));
             pool.bagsPerWave = static_cast<uint32_t>(std::min<uint64_t>(
                 std::min<uint64_t>(std::max<uint64_t>(1, tilesPerWave * trained.wordsPerWave / entriesPerBag), fillsTheCus), 1u << 16));
-            kernel = narrow ? memb_pooled::trainedKernelNarrow(lookupHasSub(ctx), ctx->fast, vec4, lookup.outType)
-                            : memb_pooled::trainedKernel(lookupHasSub(ctx), ctx->fast, vec4);
-            name = "pool_trained";
+            kernel = known    ? memb_pooled::trainedKernelKnown(lookupHasSub(ctx), ctx->fast, vec4, lookup.outType)
+                     : narrow ? memb_pooled::trainedKernelNarrow(lookupHasSub(ctx), ctx->fast, vec4, lookup.outType)
+                              : memb_pooled::trainedKernel(lookupHasSub(ctx), ctx->fast, vec4);
+            name = known ? "pool_known_trained" : "pool_trained";
             arguments[0] = &trained;
             break;
         }
@@ -1429,15 +1437,19 @@ int launchPooled(memb_hip_ctx* ctx, const Lookup& lookup, memb_pooled::PoolParam
             uniform.records = ctx->uniformRecords;
             uniform.regionPieces = ctx->regionPieces;
             uniform.levels = ctx->levels;
-            kernel = narrow ? memb_pooled::uniformKernelNarrow(lookup.outType) : memb_pooled::uniformKernel();
-            name = "pool_uniform";
+            kernel = known    ? memb_pooled::uniformKernelKnown(lookup.outType)
+                     : narrow ? memb_pooled::uniformKernelNarrow(lookup.outType)
+                              : memb_pooled::uniformKernel();
+            name = known ? "pool_known_uniform" : "pool_uniform";
             arguments[0] = &uniform;
             break;
         case memb::wire::Storage_Full:
             full = rowwiseParams<FullParams>(ctx, lookup);
             full.values = ctx->fullValues;
-            kernel = narrow ? memb_pooled::fullKernelNarrow(lookup.outType) : memb_pooled::fullKernel();
-            name = "pool_full";
+            kernel = known    ? memb_pooled::fullKernelKnown(lookup.outType)
+                     : narrow ? memb_pooled::fullKernelNarrow(lookup.outType)
+                              : memb_pooled::fullKernel();
+            name = known ? "pool_known_full" : "pool_full";
             arguments[0] = &full;
             break;
         default:
@@ -2433,9 +2445,10 @@ bool knownOutType(int outType)
     return outType == MEMB_HIP_OUT_F32 || outType == MEMB_HIP_OUT_BF16 || outType == MEMB_HIP_OUT_F16;
 }
 
+// known: memb_hip_pool_known_rows_device_typed -- the same checks, the kernels that skip unknown entries, counts or null
 int pool_rows_device_checked(
     memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int outType, size_t ld,
-    size_t col_off, int mode, void* stream)
+    size_t col_off, int mode, void* stream, bool known = false, uint32_t* counts = nullptr)
 {
     if (!knownOutType(outType)) {
         return fail(MEMB_HIP_ERR_INVALID, "unknown out_type " + std::to_string(outType));
@@ -2462,7 +2475,9 @@ int pool_rows_device_checked(
     pool.offsets = offsets;
     pool.bags = bags;
     pool.mean = mode == MEMB_HIP_POOL_MEAN ? 1u : 0u;
-    return launchPooled(ctx, Lookup{rows, n, out, outType, ld, col_off}, pool, static_cast<hipStream_t>(stream));
+    const memb_pooled::KnownParams counted{counts};
+    return launchPooled(
+        ctx, Lookup{rows, n, out, outType, ld, col_off}, pool, static_cast<hipStream_t>(stream), known ? &counted : nullptr);
 }
 
 int pooled_algorithmic_bytes_checked(
@@ -2908,6 +2923,15 @@ int memb_hip_pool_rows_device_typed(
     size_t col_off, int mode, void* stream)
 {
     return guarded([&] { return pool_rows_device_checked(ctx, rows, n, offsets, bags, out, out_type, ld, col_off, mode, stream); });
+}
+
+int memb_hip_pool_known_rows_device_typed(
+    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int out_type, size_t ld,
+    size_t col_off, int mode, uint32_t* counts, void* stream)
+{
+    return guarded([&] {
+        return pool_rows_device_checked(ctx, rows, n, offsets, bags, out, out_type, ld, col_off, mode, stream, true, counts);
+    });
 }
 
 int memb_hip_pooled_algorithmic_bytes(

@@ -463,6 +463,13 @@ void Reader::poolRowsDevice(
     compressedStorage_->poolRowsDevice(rows, n, offsets, bags, buffer, outType, ld, colOff, mode, stream);
 }
 
+void Reader::poolKnownRowsDevice(
+    const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* buffer, int outType, size_t ld, size_t colOff,
+    int mode, uint32_t* counts, void* stream) const
+{
+    compressedStorage_->poolKnownRowsDevice(rows, n, offsets, bags, buffer, outType, ld, colOff, mode, counts, stream);
+}
+
 std::vector<float> Reader::wordEmbedding(const std::string& word) const
 {
     std::vector<float> result(dim());

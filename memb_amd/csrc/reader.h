@@ -120,6 +120,11 @@ public:
     void poolRowsDevice(
         const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* buffer, int outType, size_t ld,
         size_t colOff, int mode, void* stream) const;
+    // The same over the entries the model knows (include/memb_hip_pooled_known.h): an entry that is not in the model is
+    // left out of its bag and of the mean's count; counts: null, or where the bags' known entries are counted (device).
+    void poolKnownRowsDevice(
+        const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* buffer, int outType, size_t ld,
+        size_t colOff, int mode, uint32_t* counts, void* stream) const;
 
     // Several device-buffer lookups in one kernel launch (include/memb_hip.h: memb_hip_decode_batches_device).
     void batchesToDeviceBuffers(const memb_hip_batch* batches, size_t count, void* stream) const;

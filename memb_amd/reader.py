@@ -120,6 +120,19 @@ def pool_mode(mode):
     return POOL_MODES[mode]
 
 
+POOL_MISSING = ('zero', 'skip')
+
+
+def pool_missing(missing, return_counts):
+    """missing='zero' (an entry that is not in the model is a row of +0.0 that counts) or 'skip' (it is left out of its bag
+    and of the mean's count); counts exist for the skipping call only. Returns whether to skip."""
+    if missing not in POOL_MISSING:
+        raise ValueError("missing must be 'zero' or 'skip', not {!r}".format(missing))
+    if return_counts and missing != 'skip':
+        raise ValueError("return_counts needs missing='skip': counts are of the entries the model knows")
+    return missing == 'skip'
+
+
 def bag_offsets(offsets, n):
     """offsets of bags_embedding as a numpy.int64 array: bags + 1 integers, ascending, within 0 .. n. Anything else is a
     ValueError: on the host nothing is clamped silently."""
@@ -314,7 +327,8 @@ class Reader(BaseReader):
             order == 'random')
         return out
 
-    def bags_embedding_device(self, rows, offsets, mode='mean', out=None, col_off=0, dtype=None):
+    def bags_embedding_device(self, rows, offsets, mode='mean', out=None, col_off=0, dtype=None, missing='zero',
+                              return_counts=False):
         '''Pooled lookup that never leaves the GPU: the sum or mean of each bag of rows, decoded and reduced by one kernel
         (the EmbeddingBag counterpart of rows_embedding_device). The bags' rows are never written: per entry the kernel
         reads the row id and the compressed row, per bag it stores dim elements.
@@ -333,10 +347,18 @@ class Reader(BaseReader):
             rounded once to nearest even (the bits of .to(dtype)): the sums and the division stay float32 and only the
             finished value is narrowed as the same kernel stores it -- no float32 (bags, dim) temporary, no second kernel. A
             narrow result is asked for by name: a bf16 / fp16 `out` without `dtype` is a TypeError.
+        missing : 'zero' (the default: the loop above) or 'skip'. With 'skip' an entry that is not in the model -- 0xFFFFFFFF
+            or any id >= len(reader) -- is left out of its bag, as torch.nn.EmbeddingBag leaves out padding_idx: it adds
+            nothing, not even +0.0 (a bag [missing, row of -0.0] is -0.0), and 'mean' divides by the number of KNOWN
+            entries. A bag without a known entry is +0.0. Still one kernel: no compaction of ids or offsets. Bit for bit
+            the missing='zero' result for the batch with the unknown entries taken out.
+        return_counts : True returns (vectors, counts), counts a torch.int32 tensor of shape (bags,) on the device: the
+            known entries of each bag. With missing='skip' only; a ValueError otherwise.
         No accumulate into `out`, no per-entry weights, no 'max'.
         '''
         import torch
         code = pool_mode(mode)
+        skip = pool_missing(missing, return_counts)
         index = self._impl.device()
         if index == _memb.HOST_DEVICE:
             raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
@@ -367,18 +389,29 @@ class Reader(BaseReader):
         if out.shape[1] < col_off + self.dim:
             raise ValueError('out is narrower than col_off + dim')
         out_type = {torch.float32: _memb.OUT_F32, torch.bfloat16: _memb.OUT_BF16, torch.float16: _memb.OUT_F16}[dtype]
+        ld = out.stride(0) if bags > 1 else out.shape[1]
+        if skip:
+            counts = torch.empty((bags,), dtype=torch.int32, device=device) if return_counts else None
+            self._impl.pool_known_rows_to_device(
+                rows.data_ptr(), rows.numel(), offsets.data_ptr(), bags, out.data_ptr(), ld, col_off, code,
+                _current_stream(torch, index), out_type, counts.data_ptr() if return_counts else 0)
+            return (out, counts) if return_counts else out
         self._impl.pool_rows_to_device(
-            rows.data_ptr(), rows.numel(), offsets.data_ptr(), bags, out.data_ptr(), out.stride(0) if bags > 1 else out.shape[1],
-            col_off, code, _current_stream(torch, index), out_type)
+            rows.data_ptr(), rows.numel(), offsets.data_ptr(), bags, out.data_ptr(), ld, col_off, code,
+            _current_stream(torch, index), out_type)
         return out
 
-    def sentences_embedding_device(self, sentences, mode='mean', dtype=None):
+    def sentences_embedding_device(self, sentences, mode='mean', dtype=None, missing='zero', return_counts=False):
         '''One vector per sentence, left on the GPU: `sentences` is a sequence of word sequences; the words are resolved on
         the device (resolve_rows_device) and each sentence's rows are pooled by bags_embedding_device -- words never
         become rows on the host. A sentence without words is a zero vector. Returns a (len(sentences), dim) tensor of
-        `dtype` (bags_embedding_device: float32 by default; torch.bfloat16 / torch.float16 are that result rounded once).'''
+        `dtype` (bags_embedding_device: float32 by default; torch.bfloat16 / torch.float16 are that result rounded once).
+        missing='skip' leaves the words the model does not know out of their sentences -- the mean is over the known words,
+        a sentence of unknown words is a zero vector -- and return_counts=True then returns (vectors, counts), the known
+        words per sentence (bags_embedding_device).'''
         import torch
         pool_mode(mode)
+        pool_missing(missing, return_counts)
         index = self._impl.device()
         if index == _memb.HOST_DEVICE:
             raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
@@ -395,14 +428,17 @@ class Reader(BaseReader):
         device = 'cuda:{}'.format(index)
         rows = self.resolve_rows_device(words) if words else torch.empty((0,), dtype=torch.int32, device=device)
         on_device = torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).to(device)
-        return self.bags_embedding_device(rows, on_device, mode=mode, dtype=dtype)
+        return self.bags_embedding_device(rows, on_device, mode=mode, dtype=dtype, missing=missing, return_counts=return_counts)
 
-    def bags_embedding(self, rows, offsets, mode='mean'):
+    def bags_embedding(self, rows, offsets, mode='mean', missing='zero', return_counts=False):
         '''bags_embedding_device for host arrays: numpy row ids and offsets in, a numpy float32 (bags, dim) matrix out.
         offsets: bags + 1 integers, ascending, within 0 .. len(rows) -- anything else is a ValueError. A reader on a GPU
         sends the ids and offsets up and brings only bags x dim floats back (PCIe bounds the host API). A device='cpu'
-        reader decodes rows_embedding in bounded chunks and adds them in entry order in numpy: the same bits.'''
+        reader decodes rows_embedding in bounded chunks and adds them in entry order in numpy: the same bits.
+        missing='skip' leaves the entries that are not in the model out of their bags (bags_embedding_device), on either
+        path; return_counts=True then returns (vectors, counts), counts a numpy.uint32 array of the bags' known entries.'''
         code = pool_mode(mode)
+        skip = pool_missing(missing, return_counts)
         rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
         offsets = bag_offsets(offsets, rows.size)
         bags = offsets.size - 1
@@ -411,10 +447,14 @@ class Reader(BaseReader):
             device = 'cuda:{}'.format(self._impl.device())
             result = self.bags_embedding_device(
                 torch.from_numpy(rows.view(np.int32)).to(device),
-                torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).to(device), mode=mode)
+                torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).to(device), mode=mode, missing=missing,
+                return_counts=return_counts)
+            if return_counts:
+                return result[0].cpu().numpy(), result[1].cpu().numpy().view(np.uint32)
             return result.cpu().numpy()
         out = np.zeros((bags, self.dim), dtype=np.float32)
         begins, ends = offsets[:-1], offsets[1:]
+        known_counts = np.zeros(bags, dtype=np.int64)   # missing='skip': the bags' known entries in the chunks so far
         for start in range(0, rows.size, BAGS_HOST_CHUNK):
             stop = min(rows.size, start + BAGS_HOST_CHUNK)
             first = int(np.searchsorted(ends, start, side='right'))    # the first bag that ends behind `start`
@@ -427,7 +467,23 @@ class Reader(BaseReader):
             bag, low, high, fresh = bag[keep], low[keep], high[keep], fresh[keep]
             if not bag.size:
                 continue
-            values = self.rows_embedding(rows[start:stop])
+            if skip:
+                # the chunk's known entries side by side: a bag's range among them, and whether its sum starts here; only
+                # they are decoded, and a chunk without one is not decoded at all
+                known = rows[start:stop] < len(self)
+                if not known.any():
+                    continue
+                before = np.concatenate(([0], np.cumsum(known)))
+                low, high = before[low - start] + start, before[high - start] + start
+                fresh = known_counts[bag] == 0
+                known_counts[bag] += high - low
+                keep = high > low
+                bag, low, high, fresh = bag[keep], low[keep], high[keep], fresh[keep]
+                if not bag.size:
+                    continue
+                values = self.rows_embedding(rows[start:stop][known])
+            else:
+                values = self.rows_embedding(rows[start:stop])
             for step in range(int((high - low).max())):
                 active = (high - low) > step
                 addend = values[low[active] + step - start]
@@ -439,9 +495,11 @@ class Reader(BaseReader):
                 else:
                     out[target] = out[target] + addend
         if code == _memb.POOL_MEAN:
-            counts = (ends - begins).astype(np.float32)
+            counts = (known_counts if skip else ends - begins).astype(np.float32)
             filled = counts > 0
             out[filled] = out[filled] / counts[filled][:, None]
+        if return_counts:
+            return out, known_counts.astype(np.uint32)
         return out
 
     def stage_words(self):

@@ -22,6 +22,7 @@ SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip.hip')
 NARROW_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_narrow.hip')
 POOLED_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_pooled.hip')
 POOLED_NARROW_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_pooled_narrow.hip')
+POOLED_KNOWN_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_pooled_known.hip')
 # the flags of build_native.build_hip_library
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt',
          '-Wno-unused-value', '-Wno-align-mismatch', '-Wno-pass-failed', '-Wno-unused-command-line-argument']
@@ -45,7 +46,8 @@ def device_assembly(extra_flags=(), source=SOURCE):
 
 def kernel_table(extra_flags=(), source=SOURCE):
     """{demangled kernel name: facts} for every kernel of one translation unit of libmemb_hip.so (default memb_hip.hip;
-    NARROW_SOURCE: the bf16 / fp16 kernels; POOLED_SOURCE: the pooled ones; POOLED_NARROW_SOURCE: their bf16 / fp16 forms)"""
+    NARROW_SOURCE: the bf16 / fp16 kernels; POOLED_SOURCE: the pooled ones; POOLED_NARROW_SOURCE: their bf16 / fp16 forms;
+    POOLED_KNOWN_SOURCE: the pooled kernels that skip missing rows)"""
     text = device_assembly(extra_flags, source)
     names = re.findall(r'^\s*\.amdhsa_kernel (\S+)$', text, flags=re.M)
     demangled = subprocess.run([_tool('c++filt')], input='\n'.join(names), stdout=subprocess.PIPE, text=True,

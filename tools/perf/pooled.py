@@ -20,6 +20,11 @@ With --dtype bfloat16 / float16 `pooled` and `pooledb` are the one-kernel narrow
 timed in the same rounds: `fp32_then_cast` (the float32 pooled call, then .to(dtype): what a caller had before) and `fp32`
 (the float32 pooled call alone). The fraction of 8 TB/s then comes from the typed byte count
 (memb_hip_pooled_algorithmic_bytes_typed: 2 dim bytes stored per bag); the two-step paths are left out.
+With --missing skip [--missing-share P[,P..]] a seeded share P of the entries is set to 0xFFFFFFFF and three variants are timed in
+the same rounds (float32): `skip` / `skipb` (bags_embedding_device(..., missing='skip'), and again: the A/A spread),
+`compact_then_pool` (what a caller had before: the ids compacted and the offsets rebuilt by torch on the device, then the
+existing call -- the same bits, asserted before anything is timed) and `zero` (the existing call on the same uncompacted
+inputs, missing='zero': another result, the cost floor).
 """
 import argparse
 import json
@@ -102,6 +107,50 @@ def measure_narrow(reader, rows, offsets, rounds, reps, dtype_name):
     return result
 
 
+def measure_skip(reader, rows, offsets, rounds, reps, share, seed):
+    n, bags, dim = rows.numel(), len(offsets) - 1, reader.dim
+    rows = rows.clone()
+    generator = torch.Generator(device='cuda').manual_seed(seed)
+    rows[torch.rand(n, device='cuda', generator=generator) < share] = -1   # 0xFFFFFFFF
+    device_offsets = torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).cuda()
+    long_offsets = torch.from_numpy(offsets).cuda()
+    skipped = torch.empty((bags, dim), dtype=torch.float32, device='cuda')
+    compact = torch.empty((bags, dim), dtype=torch.float32, device='cuda')
+    counted = torch.empty((bags, dim), dtype=torch.float32, device='cuda')
+    zero = torch.zeros(1, dtype=torch.int64, device='cuda')
+
+    def compact_then_pool():
+        keep = rows != -1
+        before = torch.cat([zero, torch.cumsum(keep, 0)])
+        reader.bags_embedding_device(rows[keep], before[long_offsets].to(torch.int32), mode='mean', out=compact)
+
+    variants = {
+        'skip': lambda: reader.bags_embedding_device(rows, device_offsets, mode='mean', out=skipped, missing='skip'),
+        'skipb': lambda: reader.bags_embedding_device(rows, device_offsets, mode='mean', out=skipped, missing='skip'),
+        'compact_then_pool': compact_then_pool,
+        'zero': lambda: reader.bags_embedding_device(rows, device_offsets, mode='mean', out=counted),
+    }
+    for call in variants.values():
+        call()
+    torch.cuda.synchronize()
+    assert torch.equal(skipped.view(torch.int32), compact.view(torch.int32))   # the same bits before anything is timed
+    times = {name: [] for name in variants}
+    names = list(variants)
+    for round_ in range(rounds):
+        for name in (names if round_ % 2 == 0 else names[::-1]):
+            times[name].append(timed(variants[name], reps))
+    result = {name: {'median_ms': float(np.median(values)), 'ms': values} for name, values in times.items()}
+    skip_ms = result['skip']['median_ms']
+    result['summary'] = {
+        'entries': n, 'bags': bags, 'missing_share': share, 'unknown_entries': int((rows == -1).sum()), 'skip_ms': skip_ms,
+        'compact_then_pool_ms': result['compact_then_pool']['median_ms'], 'zero_ms': result['zero']['median_ms'],
+        'aa_spread': abs(result['skipb']['median_ms'] - skip_ms) / skip_ms,
+        'skip_over_compact': skip_ms / result['compact_then_pool']['median_ms'],
+        'skip_over_zero': skip_ms / result['zero']['median_ms'],
+    }
+    return result
+
+
 def measure(reader, rows, offsets, rounds, reps):
     n, bags, dim = rows.numel(), len(offsets) - 1, reader.dim
     device_offsets = torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).cuda()
@@ -168,6 +217,8 @@ def main():
     parser.add_argument('--dtype', default='float32', choices=sorted(OUT_TYPES))
     parser.add_argument('--lengths', default='4,16,64', help='mean bag lengths (1: every bag one entry)')
     parser.add_argument('--models', default='4bit,6bit,uniform_8bit_500k')
+    parser.add_argument('--missing', default='zero', choices=['zero', 'skip'], help="skip: time missing='skip' (float32)")
+    parser.add_argument('--missing-share', default='0', help='seeded share(s) of the entries set to 0xFFFFFFFF, e.g. 0,0.1,0.5')
     args = parser.parse_args()
     lengths = [int(length) for length in args.lengths.split(',')]
     if not torch.cuda.is_available() or memb_amd.hip_device_count() < 1:
@@ -189,6 +240,18 @@ def main():
                 for mean_length in lengths:
                     name = '{}_{}_{}_bags_of_{}'.format(label, entries, order, mean_length)
                     offsets = bag_offsets(entries, mean_length, mean_length)
+                    if args.missing == 'skip':
+                        for share in (float(share) for share in args.missing_share.split(',')):
+                            shared = '{}_missing_{:g}'.format(name, share)
+                            results[shared] = measure_skip(reader, rows, offsets, args.rounds, args.reps, share, mean_length)
+                            summary = results[shared]['summary']
+                            print('{:60s} skip {:.4f} ms  A/A {:.1%}  compact + pool {:.4f} ms (x{:.2f})  zero {:.4f} ms (x{:.3f})'.format(
+                                shared, summary['skip_ms'], summary['aa_spread'], summary['compact_then_pool_ms'],
+                                1 / summary['skip_over_compact'], summary['zero_ms'], summary['skip_over_zero']), flush=True)
+                            if args.out:
+                                with open(args.out, 'w') as f:
+                                    json.dump(results, f, indent=1)
+                        continue
                     if args.dtype != 'float32':
                         results[name] = measure_narrow(reader, rows, offsets, args.rounds, args.reps, args.dtype)
                         summary = results[name]['summary']
