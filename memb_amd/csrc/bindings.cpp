@@ -963,6 +963,36 @@ PYBIND11_MODULE(_memb, m) {
             py::arg("out_type") = MEMB_HIP_OUT_F32,
             py::arg("counts_ptr") = 0)
         .def(
+            "pool_chunked_workspace_bytes",
+            [](memb::Reader& reader, size_t n, size_t bags) { return reader.poolChunkedWorkspaceBytes(n, bags); },
+            py::arg("n"),
+            py::arg("bags"))
+        .def(
+            "pool_rows_chunked_to_device",
+            [](memb::Reader& reader, uintptr_t rows, size_t n, uintptr_t offsets, size_t bags, uintptr_t out, size_t ld,
+               size_t colOff, int mode, uintptr_t stream, int outType, bool skipMissing, uintptr_t counts, uintptr_t workspace,
+               size_t workspaceBytes)
+            {
+                reader.poolRowsChunkedDevice(
+                    reinterpret_cast<const uint32_t*>(rows), n, reinterpret_cast<const uint32_t*>(offsets), bags,
+                    reinterpret_cast<void*>(out), outType, ld, colOff, mode, skipMissing, reinterpret_cast<uint32_t*>(counts),
+                    reinterpret_cast<void*>(workspace), workspaceBytes, reinterpret_cast<void*>(stream));
+            },
+            py::arg("rows_ptr"),
+            py::arg("n"),
+            py::arg("offsets_ptr"),
+            py::arg("bags"),
+            py::arg("out_ptr"),
+            py::arg("ld"),
+            py::arg("col_off") = 0,
+            py::arg("mode") = MEMB_HIP_POOL_MEAN,
+            py::arg("stream") = 0,
+            py::arg("out_type") = MEMB_HIP_OUT_F32,
+            py::arg("skip_missing") = false,
+            py::arg("counts_ptr") = 0,
+            py::arg("workspace_ptr") = 0,
+            py::arg("workspace_bytes") = 0)
+        .def(
             "pooled_algorithmic_bytes",
             [](memb::Reader& reader,
                py::array_t<uint32_t, py::array::c_style | py::array::forcecast> rows,
@@ -989,6 +1019,7 @@ PYBIND11_MODULE(_memb, m) {
     m.attr("OUT_F16") = MEMB_HIP_OUT_F16;
     m.attr("POOL_SUM") = MEMB_HIP_POOL_SUM;
     m.attr("POOL_MEAN") = MEMB_HIP_POOL_MEAN;
+    m.attr("POOL_CHUNK") = MEMB_HIP_POOL_CHUNK;
 
     m.def("available_compression_strategies", &memb::availableCompressionStrategies);
 

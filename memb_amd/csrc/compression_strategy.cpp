@@ -174,6 +174,28 @@ void CompressedStorage::poolKnownRowsDevice(
     }
 }
 
+size_t CompressedStorage::poolChunkedWorkspaceBytes(size_t n, size_t bags) const
+{
+    if (onHost()) {
+        throw std::runtime_error("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device");
+    }
+    return memb_hip_pool_chunked_workspace_bytes(deviceContext(), n, bags);
+}
+
+void CompressedStorage::poolRowsChunkedDevice(
+    const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int outType, size_t ld, size_t colOff,
+    int mode, bool skipMissing, uint32_t* counts, void* workspace, size_t workspaceBytes, void* stream) const
+{
+    if (onHost()) {
+        throw std::runtime_error("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device");
+    }
+    if (memb_hip_pool_rows_chunked_device_typed(
+            deviceContext(), rows, n, offsets, bags, out, outType, ld, colOff, mode, skipMissing ? 1 : 0, counts, workspace,
+            workspaceBytes, stream) != MEMB_HIP_OK) {
+        throwDeviceError("HIP pooled lookup failed");
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Word -> row on the device
 // ---------------------------------------------------------------------------

@@ -20,6 +20,7 @@
 #include "../../include/memb_hip_narrow.h"
 #include "../../include/memb_hip_pooled.h"
 #include "../../include/memb_hip_pooled_known.h"
+#include "../../include/memb_hip_pooled_chunked.h"
 
 #include <atomic>
 #include <memory>
@@ -76,6 +77,12 @@ public:
     void poolKnownRowsDevice(
         const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int outType, size_t ld, size_t colOff,
         int mode, uint32_t* counts, void* stream) const;
+    // Either of the two under the chunked order (include/memb_hip_pooled_chunked.h): workspace, a device buffer of at least
+    // poolChunkedWorkspaceBytes(n, bags) bytes, is the caller's for the duration of the work on `stream`.
+    size_t poolChunkedWorkspaceBytes(size_t n, size_t bags) const;
+    void poolRowsChunkedDevice(
+        const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int outType, size_t ld, size_t colOff,
+        int mode, bool skipMissing, uint32_t* counts, void* workspace, size_t workspaceBytes, void* stream) const;
 
     // device == HOST_DEVICE: rows are decoded by extractRowHost on host threads
     static constexpr int HOST_DEVICE = -2;

@@ -41,10 +41,12 @@
 #include "../../include/memb_hip_narrow.h"
 #include "../../include/memb_hip_pooled.h"
 #include "../../include/memb_hip_pooled_known.h"
+#include "../../include/memb_hip_pooled_chunked.h"
 #include "codec.h"
 #include "hip_narrow.h"
 #include "hip_pooled.h"
 #include "hip_pooled_known.h"
+#include "hip_pooled_chunked.h"
 #include "wire.h"
 #include "worker_pool.h"
 
@@ -2480,6 +2482,129 @@ int pool_rows_device_checked(
         ctx, Lookup{rows, n, out, outType, ld, col_off}, pool, static_cast<hipStream_t>(stream), known ? &counted : nullptr);
 }
 
+// memb_hip_pool_rows_chunked_device_typed (include/memb_hip_pooled_chunked.h): the chunk plan, the partial sums of the
+// chunks -- launchPooled with MEMB_HIP_POOL_SUM over the derived offsets, into the caller's workspace -- and the bags' sums
+// of those, all enqueued on `stream`. The host knows no chunk count: every launch is sized by the workspace's bound.
+int pool_rows_chunked_checked(
+    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int outType, size_t ld,
+    size_t col_off, int mode, bool skip, uint32_t* counts, void* workspace, size_t workspaceBytes, void* stream)
+{
+    if (!knownOutType(outType)) {
+        return fail(MEMB_HIP_ERR_INVALID, "unknown out_type " + std::to_string(outType));
+    }
+    if (mode != MEMB_HIP_POOL_SUM && mode != MEMB_HIP_POOL_MEAN) {
+        return fail(MEMB_HIP_ERR_INVALID, "unknown pooling mode " + std::to_string(mode));
+    }
+    if (!ctx || (n && !rows) || (bags && (!offsets || !out))) {
+        return fail(MEMB_HIP_ERR_INVALID, "null argument");
+    }
+    const size_t elementBytes = outType == MEMB_HIP_OUT_F32 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(out) % elementBytes != 0) {
+        return fail(MEMB_HIP_ERR_INVALID, "out must be aligned to its element (" + std::to_string(elementBytes) + " bytes)");
+    }
+    if (col_off > ld || ld - col_off < ctx->dim) {
+        return fail(MEMB_HIP_ERR_INVALID, "ld must be at least col_off + dim");
+    }
+    if (counts && !skip) {
+        return fail(MEMB_HIP_ERR_INVALID, "counts need skip_missing: they are of the entries the model knows");
+    }
+    if (bags == 0) {
+        return MEMB_HIP_OK;
+    }
+    if (n > (size_t(1) << 37) || bags >= (1ull << 37)) {
+        return fail(MEMB_HIP_ERR_INVALID, "batch too large");
+    }
+    const memb_pooled::ChunkWorkspace layout = memb_pooled::chunkWorkspace(n, bags, ctx->dim);
+    if (layout.maxChunks >= 0xFFFFFFFFull) {
+        return fail(MEMB_HIP_ERR_INVALID, "batch too large");
+    }
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 16 != 0) {
+        return fail(MEMB_HIP_ERR_INVALID, "workspace must be a device pointer aligned to 16 bytes");
+    }
+    if (workspaceBytes < layout.bytes) {
+        return fail(
+            MEMB_HIP_ERR_INVALID,
+            "workspace of " + std::to_string(workspaceBytes) + " bytes, " + std::to_string(layout.bytes) + " needed");
+    }
+    DeviceScope deviceScope(ctx->device);
+    HIP_TRY(deviceScope.status());
+    const hipStream_t queue = static_cast<hipStream_t>(stream);
+    char* const base = static_cast<char*>(workspace);
+    uint32_t* const derived = reinterpret_cast<uint32_t*>(base + layout.derived);
+    uint32_t* const chunkCounts = reinterpret_cast<uint32_t*>(base + layout.chunkCounts);
+    float* const partials = reinterpret_cast<float*>(base + layout.partials);
+
+    memb_pooled::ChunkPlanParams plan{};
+    plan.offsets = offsets;
+    plan.bags = bags;
+    plan.n = n;
+    plan.maxChunks = layout.maxChunks;
+    plan.planBlocks = layout.planBlocks;
+    plan.blockSums = reinterpret_cast<unsigned long long*>(base + layout.blockSums);
+    plan.bagStart = reinterpret_cast<uint32_t*>(base + layout.bagStart);
+    plan.derived = derived;
+    void* planArguments[] = {&plan};
+    const auto enqueue = [&](const char* name, const void* kernel, uint64_t blocks, void** arguments) {
+        // (no dynamic LDS: launched as they are, not through launchKernelAddress, which raises a kernel's dynamic LDS limit
+        // to the whole 160 KiB -- refused for a kernel that has static LDS of its own, as the scan kernels have)
+        hipError_t status = !kernel ? hipErrorInvalidDeviceFunction
+                                    : hipLaunchKernel(kernel, dim3(static_cast<uint32_t>(blocks)), dim3(memb_pooled::PLAN_THREADS),
+                                                      arguments, 0, queue);
+        status = status != hipSuccess ? status : hipGetLastError();
+        return status == hipSuccess ? MEMB_HIP_OK
+                                    : fail(MEMB_HIP_ERR_DEVICE, std::string(name) + " launch: " + hipGetErrorString(status));
+    };
+    int code = MEMB_HIP_OK;
+    if (layout.planBlocks > 1) {   // (one block: its bags' starts need no other block's sum)
+        code = enqueue("chunk_block_sums", memb_pooled::chunkBlockSumsKernel(), layout.planBlocks, planArguments);
+        if (code == MEMB_HIP_OK) {
+            code = enqueue("chunk_scan_sums", memb_pooled::chunkScanSumsKernel(), 1, planArguments);
+        }
+    }
+    if (code == MEMB_HIP_OK) {
+        code = enqueue("chunk_bag_starts", memb_pooled::chunkBagStartsKernel(), layout.planBlocks, planArguments);
+    }
+    if (code == MEMB_HIP_OK) {
+        code = enqueue(
+            "chunk_offsets", memb_pooled::chunkOffsetsKernel(), layout.maxChunks / memb_pooled::PLAN_THREADS + 1, planArguments);
+    }
+    if (code != MEMB_HIP_OK) {
+        return code;
+    }
+
+    memb_pooled::PoolParams chunks{};
+    chunks.offsets = derived;
+    chunks.bags = layout.maxChunks;
+    chunks.mean = 0;
+    const memb_pooled::KnownParams counted{chunkCounts};
+    code = launchPooled(
+        ctx, Lookup{rows, n, partials, MEMB_HIP_OUT_F32, ctx->dim, 0}, chunks, queue, skip ? &counted : nullptr);
+    if (code != MEMB_HIP_OK) {
+        return code;
+    }
+
+    memb_pooled::ChunkSumParams sums{};
+    sums.offsets = offsets;
+    sums.bagStart = plan.bagStart;
+    sums.partials = partials;
+    sums.chunkCounts = skip ? chunkCounts : nullptr;
+    sums.out = out;
+    sums.counts = counts;
+    sums.bags = bags;
+    sums.n = n;
+    sums.ld = ld;
+    sums.colOff = col_off;
+    sums.dim = ctx->dim;
+    sums.mean = mode == MEMB_HIP_POOL_MEAN ? 1u : 0u;
+    const uint64_t waves = uint64_t(bags) * ((ctx->dim + WAVE - 1) / WAVE);
+    const uint64_t blocks = (waves + memb_pooled::PLAN_THREADS / WAVE - 1) / (memb_pooled::PLAN_THREADS / WAVE);
+    if (blocks >= 0x7FFFFFFFull) {
+        return fail(MEMB_HIP_ERR_INVALID, "batches too large for one launch");
+    }
+    void* sumArguments[] = {&sums};
+    return enqueue("pool_chunks", memb_pooled::poolChunksKernel(outType), blocks, sumArguments);
+}
+
 int pooled_algorithmic_bytes_checked(
     const memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, int outType, uint64_t* bytes)
 {
@@ -2931,6 +3056,22 @@ int memb_hip_pool_known_rows_device_typed(
 {
     return guarded([&] {
         return pool_rows_device_checked(ctx, rows, n, offsets, bags, out, out_type, ld, col_off, mode, stream, true, counts);
+    });
+}
+
+size_t memb_hip_pool_chunked_workspace_bytes(memb_hip_ctx* ctx, size_t n, size_t bags)
+{
+    return ctx ? memb_pooled::chunkWorkspace(n, bags, ctx->dim).bytes : 0;
+}
+
+int memb_hip_pool_rows_chunked_device_typed(
+    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int out_type, size_t ld,
+    size_t col_off, int mode, int skip_missing, uint32_t* counts, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return guarded([&] {
+        return pool_rows_chunked_checked(
+            ctx, rows, n, offsets, bags, out, out_type, ld, col_off, mode, skip_missing != 0, counts, workspace, workspace_bytes,
+            stream);
     });
 }
 

@@ -470,6 +470,19 @@ void Reader::poolKnownRowsDevice(
     compressedStorage_->poolKnownRowsDevice(rows, n, offsets, bags, buffer, outType, ld, colOff, mode, counts, stream);
 }
 
+size_t Reader::poolChunkedWorkspaceBytes(size_t n, size_t bags) const
+{
+    return compressedStorage_->poolChunkedWorkspaceBytes(n, bags);
+}
+
+void Reader::poolRowsChunkedDevice(
+    const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* buffer, int outType, size_t ld, size_t colOff,
+    int mode, bool skipMissing, uint32_t* counts, void* workspace, size_t workspaceBytes, void* stream) const
+{
+    compressedStorage_->poolRowsChunkedDevice(
+        rows, n, offsets, bags, buffer, outType, ld, colOff, mode, skipMissing, counts, workspace, workspaceBytes, stream);
+}
+
 std::vector<float> Reader::wordEmbedding(const std::string& word) const
 {
     std::vector<float> result(dim());

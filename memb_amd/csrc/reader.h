@@ -125,6 +125,13 @@ public:
     void poolKnownRowsDevice(
         const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* buffer, int outType, size_t ld,
         size_t colOff, int mode, uint32_t* counts, void* stream) const;
+    // Either of the two under the chunked order (include/memb_hip_pooled_chunked.h): long bags are cut into chunks of
+    // MEMB_HIP_POOL_CHUNK entries whose sums are added in chunk order. workspace: a device buffer of at least
+    // poolChunkedWorkspaceBytes(n, bags) bytes that the caller keeps until the work on `stream` has ended.
+    size_t poolChunkedWorkspaceBytes(size_t n, size_t bags) const;
+    void poolRowsChunkedDevice(
+        const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* buffer, int outType, size_t ld,
+        size_t colOff, int mode, bool skipMissing, uint32_t* counts, void* workspace, size_t workspaceBytes, void* stream) const;
 
     // Several device-buffer lookups in one kernel launch (include/memb_hip.h: memb_hip_decode_batches_device).
     void batchesToDeviceBuffers(const memb_hip_batch* batches, size_t count, void* stream) const;

@@ -133,6 +133,29 @@ def pool_missing(missing, return_counts):
     return missing == 'skip'
 
 
+POOL_REDUCTIONS = ('sequential', 'chunked')
+POOL_CHUNK = _memb.POOL_CHUNK   # entries per chunk of reduction='chunked' (MEMB_HIP_POOL_CHUNK): a constant of the API
+
+
+def pool_reduction(reduction):
+    """reduction='sequential' (a bag's rows are added one after the other) or 'chunked' (a bag is cut into chunks of
+    POOL_CHUNK entries whose sums are added in chunk order). Returns whether to chunk."""
+    if reduction not in POOL_REDUCTIONS:
+        raise ValueError("reduction must be 'sequential' or 'chunked', not {!r}".format(reduction))
+    return reduction == 'chunked'
+
+
+def chunk_offsets(offsets):
+    """The chunks of reduction='chunked' as bags: (derived, first) for ascending int64 offsets -- derived the offsets of
+    one bag per chunk (bag b: max(1, ceil(L / POOL_CHUNK)) of them), first[b] the first chunk of bag b, first[bags] all."""
+    begins, lengths = offsets[:-1], offsets[1:] - offsets[:-1]
+    per_bag = np.maximum(1, -(-lengths // POOL_CHUNK))
+    first = np.concatenate(([0], np.cumsum(per_bag))).astype(np.int64)
+    within = np.arange(first[-1], dtype=np.int64) - np.repeat(first[:-1], per_bag)
+    derived = np.concatenate((np.repeat(begins, per_bag) + POOL_CHUNK * within, offsets[-1:])).astype(np.int64)
+    return derived, first
+
+
 def bag_offsets(offsets, n):
     """offsets of bags_embedding as a numpy.int64 array: bags + 1 integers, ascending, within 0 .. n. Anything else is a
     ValueError: on the host nothing is clamped silently."""
@@ -328,7 +351,7 @@ class Reader(BaseReader):
         return out
 
     def bags_embedding_device(self, rows, offsets, mode='mean', out=None, col_off=0, dtype=None, missing='zero',
-                              return_counts=False):
+                              return_counts=False, reduction='sequential'):
         '''Pooled lookup that never leaves the GPU: the sum or mean of each bag of rows, decoded and reduced by one kernel
         (the EmbeddingBag counterpart of rows_embedding_device). The bags' rows are never written: per entry the kernel
         reads the row id and the compressed row, per bag it stores dim elements.
@@ -354,11 +377,21 @@ class Reader(BaseReader):
             the missing='zero' result for the batch with the unknown entries taken out.
         return_counts : True returns (vectors, counts), counts a torch.int32 tensor of shape (bags,) on the device: the
             known entries of each bag. With missing='skip' only; a ValueError otherwise.
+        reduction : 'sequential' (the default: the loops above, one wavefront per bag) or 'chunked', for LONG bags --
+            documents, paragraphs. A bag is cut into chunks of memb_amd.POOL_CHUNK entries, chunk j owning the entries
+            [begin + C j, min(end, begin + C (j + 1))); many wavefronts sum the chunks at once with the loop above, and the
+            chunks' float32 sums are then added in chunk order, one IEEE addition each (with missing='skip' a chunk
+            without a known entry adds nothing); 'mean' divides once by the bag's count. The order is fixed by the
+            inputs alone; a bag of at most POOL_CHUNK entries has the bits of 'sequential'. Bit for bit mode='sum' of
+            the sequential path over the chunks as bags, then that loop. Every bag's sum crosses a float32 workspace
+            once (a torch tensor of this call): for short bags 'sequential' stays the faster choice. offsets must
+            ascend; where they do not, the bags at and behind a decrease hold unspecified values.
         No accumulate into `out`, no per-entry weights, no 'max'.
         '''
         import torch
         code = pool_mode(mode)
         skip = pool_missing(missing, return_counts)
+        chunked = pool_reduction(reduction)
         index = self._impl.device()
         if index == _memb.HOST_DEVICE:
             raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
@@ -390,6 +423,16 @@ class Reader(BaseReader):
             raise ValueError('out is narrower than col_off + dim')
         out_type = {torch.float32: _memb.OUT_F32, torch.bfloat16: _memb.OUT_BF16, torch.float16: _memb.OUT_F16}[dtype]
         ld = out.stride(0) if bags > 1 else out.shape[1]
+        if chunked:
+            counts = torch.empty((bags,), dtype=torch.int32, device=device) if return_counts else None
+            workspace_bytes = self._impl.pool_chunked_workspace_bytes(rows.numel(), bags)
+            # this call's own: torch's allocator keeps it alive for the work enqueued on the current stream
+            workspace = torch.empty((workspace_bytes,), dtype=torch.uint8, device=device)
+            self._impl.pool_rows_chunked_to_device(
+                rows.data_ptr(), rows.numel(), offsets.data_ptr(), bags, out.data_ptr(), ld, col_off, code,
+                _current_stream(torch, index), out_type, skip, counts.data_ptr() if return_counts else 0,
+                workspace.data_ptr(), workspace_bytes)
+            return (out, counts) if return_counts else out
         if skip:
             counts = torch.empty((bags,), dtype=torch.int32, device=device) if return_counts else None
             self._impl.pool_known_rows_to_device(
@@ -401,17 +444,20 @@ class Reader(BaseReader):
             _current_stream(torch, index), out_type)
         return out
 
-    def sentences_embedding_device(self, sentences, mode='mean', dtype=None, missing='zero', return_counts=False):
+    def sentences_embedding_device(self, sentences, mode='mean', dtype=None, missing='zero', return_counts=False,
+                                   reduction='sequential'):
         '''One vector per sentence, left on the GPU: `sentences` is a sequence of word sequences; the words are resolved on
         the device (resolve_rows_device) and each sentence's rows are pooled by bags_embedding_device -- words never
         become rows on the host. A sentence without words is a zero vector. Returns a (len(sentences), dim) tensor of
         `dtype` (bags_embedding_device: float32 by default; torch.bfloat16 / torch.float16 are that result rounded once).
         missing='skip' leaves the words the model does not know out of their sentences -- the mean is over the known words,
         a sentence of unknown words is a zero vector -- and return_counts=True then returns (vectors, counts), the known
-        words per sentence (bags_embedding_device).'''
+        words per sentence (bags_embedding_device). reduction='chunked' pools long sentences -- documents -- under
+        bags_embedding_device's chunked order.'''
         import torch
         pool_mode(mode)
         pool_missing(missing, return_counts)
+        pool_reduction(reduction)
         index = self._impl.device()
         if index == _memb.HOST_DEVICE:
             raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
@@ -428,17 +474,20 @@ class Reader(BaseReader):
         device = 'cuda:{}'.format(index)
         rows = self.resolve_rows_device(words) if words else torch.empty((0,), dtype=torch.int32, device=device)
         on_device = torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).to(device)
-        return self.bags_embedding_device(rows, on_device, mode=mode, dtype=dtype, missing=missing, return_counts=return_counts)
+        return self.bags_embedding_device(
+            rows, on_device, mode=mode, dtype=dtype, missing=missing, return_counts=return_counts, reduction=reduction)
 
-    def bags_embedding(self, rows, offsets, mode='mean', missing='zero', return_counts=False):
+    def bags_embedding(self, rows, offsets, mode='mean', missing='zero', return_counts=False, reduction='sequential'):
         '''bags_embedding_device for host arrays: numpy row ids and offsets in, a numpy float32 (bags, dim) matrix out.
         offsets: bags + 1 integers, ascending, within 0 .. len(rows) -- anything else is a ValueError. A reader on a GPU
         sends the ids and offsets up and brings only bags x dim floats back (PCIe bounds the host API). A device='cpu'
         reader decodes rows_embedding in bounded chunks and adds them in entry order in numpy: the same bits.
         missing='skip' leaves the entries that are not in the model out of their bags (bags_embedding_device), on either
-        path; return_counts=True then returns (vectors, counts), counts a numpy.uint32 array of the bags' known entries.'''
+        path; return_counts=True then returns (vectors, counts), counts a numpy.uint32 array of the bags' known entries.
+        reduction='chunked' is bags_embedding_device's chunked order, on either path with the same bits.'''
         code = pool_mode(mode)
         skip = pool_missing(missing, return_counts)
+        chunked = pool_reduction(reduction)
         rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
         offsets = bag_offsets(offsets, rows.size)
         bags = offsets.size - 1
@@ -448,10 +497,12 @@ class Reader(BaseReader):
             result = self.bags_embedding_device(
                 torch.from_numpy(rows.view(np.int32)).to(device),
                 torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).to(device), mode=mode, missing=missing,
-                return_counts=return_counts)
+                return_counts=return_counts, reduction=reduction)
             if return_counts:
                 return result[0].cpu().numpy(), result[1].cpu().numpy().view(np.uint32)
             return result.cpu().numpy()
+        if chunked:
+            return self._bags_embedding_chunked(rows, offsets, code, skip, return_counts)
         out = np.zeros((bags, self.dim), dtype=np.float32)
         begins, ends = offsets[:-1], offsets[1:]
         known_counts = np.zeros(bags, dtype=np.int64)   # missing='skip': the bags' known entries in the chunks so far
@@ -496,6 +547,38 @@ class Reader(BaseReader):
                     out[target] = out[target] + addend
         if code == _memb.POOL_MEAN:
             counts = (known_counts if skip else ends - begins).astype(np.float32)
+            filled = counts > 0
+            out[filled] = out[filled] / counts[filled][:, None]
+        if return_counts:
+            return out, known_counts.astype(np.uint32)
+        return out
+
+    def _bags_embedding_chunked(self, rows, offsets, code, skip, return_counts):
+        """bags_embedding(reduction='chunked') of a device='cpu' reader: the sequential sums of the chunks as bags, then the
+        chunks' sums added in chunk order, all bags at once per step."""
+        bags = offsets.size - 1
+        derived, first = chunk_offsets(offsets)
+        if skip:
+            partial, chunk_counts = self.bags_embedding(rows, derived, mode='sum', missing='skip', return_counts=True)
+            chunk_counts = chunk_counts.astype(np.int64)
+        else:
+            partial = self.bags_embedding(rows, derived, mode='sum')
+            chunk_counts = np.ones(derived.size - 1, dtype=np.int64)   # every chunk counts, an empty bag's one too
+        out = np.zeros((bags, self.dim), dtype=np.float32)
+        started = np.zeros(bags, dtype=bool)
+        per_bag = first[1:] - first[:-1]
+        for step in range(int(per_bag.max()) if bags else 0):
+            bag = np.nonzero(per_bag > step)[0]
+            chunk = first[bag] + step
+            used = chunk_counts[chunk] > 0
+            bag, chunk = bag[used], chunk[used]
+            fresh = ~started[bag]
+            out[bag[fresh]] = partial[chunk[fresh]]
+            out[bag[~fresh]] = out[bag[~fresh]] + partial[chunk[~fresh]]
+            started[bag] = True
+        known_counts = np.add.reduceat(chunk_counts, first[:-1]) if bags else np.zeros(0, dtype=np.int64)
+        if code == _memb.POOL_MEAN:
+            counts = (known_counts if skip else offsets[1:] - offsets[:-1]).astype(np.float32)
             filled = counts > 0
             out[filled] = out[filled] / counts[filled][:, None]
         if return_counts:

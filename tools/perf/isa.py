@@ -23,6 +23,7 @@ NARROW_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_narrow.hip')
 POOLED_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_pooled.hip')
 POOLED_NARROW_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_pooled_narrow.hip')
 POOLED_KNOWN_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_pooled_known.hip')
+POOLED_CHUNKED_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_pooled_chunked.hip')
 # the flags of build_native.build_hip_library
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt',
          '-Wno-unused-value', '-Wno-align-mismatch', '-Wno-pass-failed', '-Wno-unused-command-line-argument']

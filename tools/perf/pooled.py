@@ -25,6 +25,11 @@ the same rounds (float32): `skip` / `skipb` (bags_embedding_device(..., missing=
 `compact_then_pool` (what a caller had before: the ids compacted and the offsets rebuilt by torch on the device, then the
 existing call -- the same bits, asserted before anything is timed) and `zero` (the existing call on the same uncompacted
 inputs, missing='zero': another result, the cost floor).
+
+With --reduction sequential,chunked the two summation orders of bags_embedding_device are timed in the same rounds (float32,
+mean): `chunked` / `chunkedb` (reduction='chunked', and again: the A/A spread), `sequential` (the default order: one wavefront
+walks a whole bag) and the two-step paths above. --fixed BAGSxLENGTH[,..] adds batches of equal bags (1x100000: one bag of
+100 000 entries; 1000x2000), shuffled rows of the model.
 """
 import argparse
 import json
@@ -208,6 +213,79 @@ def measure(reader, rows, offsets, rounds, reps):
     return result
 
 
+def measure_reduction(reader, rows, offsets, rounds, reps):
+    n, bags, dim = rows.numel(), len(offsets) - 1, reader.dim
+    device_offsets = torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).cuda()
+    long_offsets = torch.from_numpy(offsets).cuda()
+    counts = (long_offsets[1:] - long_offsets[:-1])
+    bag_of_entry = torch.repeat_interleave(torch.arange(bags, device='cuda'), counts)
+    divisor = counts.clamp(min=1).to(torch.float32)[:, None]
+    fp32 = torch.empty((n, dim), dtype=torch.float32, device='cuda')
+    chunked = torch.empty((bags, dim), dtype=torch.float32, device='cuda')
+    sequential = torch.empty((bags, dim), dtype=torch.float32, device='cuda')
+    reduced = torch.empty((bags, dim), dtype=torch.float32, device='cuda')
+
+    def two_step():
+        reader.rows_embedding_device(rows, out=fp32)
+        reduced.zero_()
+        reduced.index_add_(0, bag_of_entry, fp32)
+        reduced.div_(divisor)
+
+    def two_step_sr():
+        reader.rows_embedding_device(rows, out=fp32)
+        return torch.segment_reduce(fp32, 'mean', offsets=long_offsets, axis=0, initial=0.0)
+
+    variants = {
+        'chunked': lambda: reader.bags_embedding_device(rows, device_offsets, mode='mean', out=chunked, reduction='chunked'),
+        'chunkedb': lambda: reader.bags_embedding_device(rows, device_offsets, mode='mean', out=chunked, reduction='chunked'),
+        'sequential': lambda: reader.bags_embedding_device(rows, device_offsets, mode='mean', out=sequential),
+        'two_step': two_step,
+    }
+    try:
+        close = torch.allclose(two_step_sr(), reader.bags_embedding_device(rows, device_offsets), rtol=1e-3, atol=1e-4)
+        torch.cuda.synchronize()
+        if close:
+            variants['two_step_sr'] = two_step_sr
+    except (RuntimeError, NotImplementedError, TypeError):
+        pass
+    for call in variants.values():
+        call()
+    torch.cuda.synchronize()
+    # the orders agree to their reassociation before anything is timed; bags of at most a chunk in bits
+    assert torch.allclose(chunked, sequential, rtol=1e-3, atol=1e-4)
+    short = (counts <= memb_amd.POOL_CHUNK)
+    assert torch.equal(chunked[short].view(torch.int32), sequential[short].view(torch.int32))
+    times = {name: [] for name in variants}
+    names = list(variants)
+    for round_ in range(rounds):
+        for name in (names if round_ % 2 == 0 else names[::-1]):
+            times[name].append(timed(variants[name], reps))
+    result = {name: {'median_ms': float(np.median(values)), 'ms': values} for name, values in times.items()}
+    best_two_step = min(result[name]['median_ms'] for name in result if name.startswith('two_step'))
+    chunked_ms = result['chunked']['median_ms']
+    result['summary'] = {
+        'entries': n, 'bags': bags, 'chunk': memb_amd.POOL_CHUNK, 'chunked_ms': chunked_ms,
+        'sequential_ms': result['sequential']['median_ms'], 'two_step_ms': best_two_step,
+        'aa_spread': abs(result['chunkedb']['median_ms'] - chunked_ms) / chunked_ms,
+        'chunked_over_sequential': result['sequential']['median_ms'] / chunked_ms,
+        'chunked_over_two_step': best_two_step / chunked_ms,
+        'sequential_over_two_step': best_two_step / result['sequential']['median_ms'],
+        'workspace_bytes': reader._impl.pool_chunked_workspace_bytes(n, bags),
+    }
+    return result
+
+
+def report_reduction(results, name, reader, rows, offsets, args):
+    results[name] = measure_reduction(reader, rows, offsets, args.rounds, args.reps)
+    summary = results[name]['summary']
+    print('{:48s} chunked {:.4f} ms  A/A {:.1%}  sequential {:.4f} ms (x{:.2f})  two-step {:.4f} ms (x{:.2f})'.format(
+        name, summary['chunked_ms'], summary['aa_spread'], summary['sequential_ms'], summary['chunked_over_sequential'],
+        summary['two_step_ms'], summary['chunked_over_two_step']), flush=True)
+    if args.out:
+        with open(args.out, 'w') as f:
+            json.dump(results, f, indent=1)
+
+
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument('--rounds', type=int, default=5)
@@ -219,7 +297,11 @@ def main():
     parser.add_argument('--models', default='4bit,6bit,uniform_8bit_500k')
     parser.add_argument('--missing', default='zero', choices=['zero', 'skip'], help="skip: time missing='skip' (float32)")
     parser.add_argument('--missing-share', default='0', help='seeded share(s) of the entries set to 0xFFFFFFFF, e.g. 0,0.1,0.5')
+    parser.add_argument('--reduction', default='', help="sequential,chunked: time reduction='chunked' beside the default order")
+    parser.add_argument('--fixed', default='', help='with --reduction: batches of equal bags, BAGSxLENGTH[,..] (shuffled rows)')
     args = parser.parse_args()
+    if args.reduction and sorted(args.reduction.split(',')) != ['chunked', 'sequential']:
+        raise SystemExit('--reduction takes sequential,chunked')
     lengths = [int(length) for length in args.lengths.split(',')]
     if not torch.cuda.is_available() or memb_amd.hip_device_count() < 1:
         raise SystemExit('pooled.py measures on a GPU; none found')
@@ -231,6 +313,11 @@ def main():
             continue
         path, _ = synthetic.cached_model(words, 300, storage, bits)
         reader = memb_amd.Reader(path)
+        for shape in (args.fixed.split(',') if args.reduction and args.fixed else ()):
+            bags, length = (int(value) for value in shape.split('x'))
+            rows = torch.randint(0, words, (bags * length,), device='cuda', generator=generator, dtype=torch.int32)
+            report_reduction(results, '{}_{}_bags_of_exactly_{}'.format(label, bags, length), reader, rows,
+                             np.arange(bags + 1, dtype=np.int64) * length, args)
         for entries in sorted({100000, words}):
             in_order = torch.arange(entries, dtype=torch.int32, device='cuda') if entries == words else \
                 torch.sort(torch.randint(0, words, (entries,), device='cuda', generator=generator, dtype=torch.int32)).values
@@ -240,6 +327,9 @@ def main():
                 for mean_length in lengths:
                     name = '{}_{}_{}_bags_of_{}'.format(label, entries, order, mean_length)
                     offsets = bag_offsets(entries, mean_length, mean_length)
+                    if args.reduction:
+                        report_reduction(results, name, reader, rows, offsets, args)
+                        continue
                     if args.missing == 'skip':
                         for share in (float(share) for share in args.missing_share.split(',')):
                             shared = '{}_missing_{:g}'.format(name, share)
