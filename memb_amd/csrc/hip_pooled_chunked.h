@@ -3,7 +3,7 @@
 // sides lay it out. Three stages on one stream:
 //   (a) the chunk plan    chunk_block_sums -> chunk_scan_sums -> chunk_bag_starts -> chunk_offsets (ChunkPlanParams)
 //   (b) partial sums      launchPooled, MEMB_HIP_POOL_SUM over the derived offsets into the workspace: the kernels of
-//                         memb_hip_pooled.hip / memb_hip_pooled_known.hip as they are
+//                         memb_hip_pooled.hip (plain or known) as they are
 //   (c) the bags' sums    pool_chunks<OUT> (ChunkSumParams)
 #pragma once
 

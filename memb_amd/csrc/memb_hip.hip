@@ -32,8 +32,9 @@
 // code; this file -- context, staging of a model to HBM, launch geometry, the C
 // ABI; memb_hip_narrow.hip -- the bf16 / fp16 kernels, a translation unit of its own
 // that includes the same device headers and hands its kernels over as addresses
-// (hip_narrow.h), planned and launched here; memb_hip_pooled.hip -- the pooled kernels (sum / mean
-// of each bag of rows), handed over the same way (hip_pooled.h); hip_host_path.h -- how rows reach host
+// (hip_narrow.h), planned and launched here; memb_hip_pooled.hip -- every sequential pooled kernel (sum / mean
+// of each bag of rows or of its known rows, as fp32, bf16 or fp16), handed over the same way through one selector
+// (hip_pooled.h); memb_hip_pooled_chunked.hip -- the chunked order's (hip_pooled_chunked.h); hip_host_path.h -- how rows reach host
 // buffers (pinned ring, copy threads, centroid indices over PCIe).
 #include <hip/hip_runtime.h>
 
@@ -45,7 +46,6 @@
 #include "codec.h"
 #include "hip_narrow.h"
 #include "hip_pooled.h"
-#include "hip_pooled_known.h"
 #include "hip_pooled_chunked.h"
 #include "wire.h"
 #include "worker_pool.h"
@@ -1365,15 +1365,16 @@ int launch(memb_hip_ctx* ctx, const Lookup& lookup, hipStream_t stream)
 }
 
 // A pooled lookup (include/memb_hip_pooled.h): `lookup` describes the ENTRIES (rows, n) and the bags' rows (out, ld, colOff),
-// `pool` the bags. One kernel of memb_hip_pooled.hip, whatever the storage.
+// `pool` the bags. One kernel of memb_hip_pooled.hip, whatever the storage, the element and `known`
+// (memb_pooled::pooledKernel).
 // Trained: planned like a decode of n rows by the one-tile kernel (planTrained, force = 0, usual index) -- pool_trained is
 // that kernel up to the symbol tile -- and a wavefront owns a run of consecutive bags sized so that it decodes about
 // POOLED_TILES_PER_WAVE tiles (option tiles_per_wave: that many), fewer while the grid would not fill the CUs. A bag is
 // never split: ONE enormous bag is walked by one wavefront, correct and slow.
-// Bags' rows of a narrow outType run the kernels of memb_hip_pooled_narrow.hip on the same plan: they add fp32 centroids,
-// so LDS is planned for an fp32 codebook whatever the element, and only the choice of the piece form follows it.
-// known (include/memb_hip_pooled_known.h): the kernels of memb_hip_pooled_known.hip, which leave a bag's unknown entries
-// out and take the counts as a third parameter -- the same plan, the same geometry.
+// Bags' rows of a narrow outType run the bf16 / fp16 kernels on the same plan: they add fp32 centroids, so LDS is planned
+// for an fp32 codebook whatever the element, and only the choice of the piece form follows it.
+// known (include/memb_hip_pooled_known.h): the pool_known_* kernels, which leave a bag's unknown entries out and take the
+// counts as a third parameter -- the same plan, the same geometry.
 constexpr uint32_t POOLED_TILES_PER_WAVE = 4;
 
 int launchPooled(
@@ -1383,19 +1384,19 @@ int launchPooled(
     if (lookup.n > (size_t(1) << 37) || pool.bags >= (1ull << 37)) {
         return fail(MEMB_HIP_ERR_INVALID, "batch too large");
     }
-    const void* kernel = nullptr;
-    const char* name = "";
+    memb_pooled::PoolStorage storage;
+    bool vec4 = false;
     memb_pooled::KnownParams counted = known ? *known : memb_pooled::KnownParams{};
-    void* arguments[3] = {nullptr, &pool, &counted};   // (the third: kernels of memb_hip_pooled_known.hip only)
+    void* arguments[3] = {nullptr, &pool, &counted};   // (the third: the pool_known_* kernels only)
     TrainedParams trained;
     UniformParams uniform;
     FullParams full;
     uint32_t waves = memb_pooled::ROWWISE_WAVES;
     uint32_t ldsBytes = 0;
     pool.bagsPerWave = 1;
-    const bool narrow = lookup.outType != MEMB_HIP_OUT_F32;
     switch (ctx->storage) {
         case memb::wire::Storage_Trained: {
+            storage = memb_pooled::PoolStorage::Trained;
             Lookup planned = lookup;
             planned.n = std::max<size_t>(lookup.n, 1);
             planned.outType = MEMB_HIP_OUT_F32;
@@ -1419,7 +1420,7 @@ int launchPooled(
             }
             const bool pieces =
                 outputMode(ctx->dim, lookup.ld, lookup.colOff, lookup.out, lookup.elementBytes(), trained.wordsPerWave) != OUT_SCALAR;
-            const bool vec4 = pieces && ctx->dim <= memb_pooled::TRAINED_VEC4_MAX_DIM;
+            vec4 = pieces && ctx->dim <= memb_pooled::TRAINED_VEC4_MAX_DIM;
             waves = geometry.waves;
             ldsBytes = geometry.ldsBytes;
             const uint64_t tilesPerWave = ctx->switches.tilesPerWave ? ctx->switches.tilesPerWave : POOLED_TILES_PER_WAVE;
@@ -1427,36 +1428,30 @@ int launchPooled(
             const uint64_t fillsTheCus = std::max<uint64_t>(1, pool.bags / (uint64_t(ctx->cuCount) * ONE_TILE_WAVES_PER_CU));
             pool.bagsPerWave = static_cast<uint32_t>(std::min<uint64_t>(
                 std::min<uint64_t>(std::max<uint64_t>(1, tilesPerWave * trained.wordsPerWave / entriesPerBag), fillsTheCus), 1u << 16));
-            kernel = known    ? memb_pooled::trainedKernelKnown(lookupHasSub(ctx), ctx->fast, vec4, lookup.outType)
-                     : narrow ? memb_pooled::trainedKernelNarrow(lookupHasSub(ctx), ctx->fast, vec4, lookup.outType)
-                              : memb_pooled::trainedKernel(lookupHasSub(ctx), ctx->fast, vec4);
-            name = known ? "pool_known_trained" : "pool_trained";
             arguments[0] = &trained;
             break;
         }
         case memb::wire::Storage_Uniform:
+            storage = memb_pooled::PoolStorage::Uniform;
             uniform = rowwiseParams<UniformParams>(ctx, lookup);
             uniform.records = ctx->uniformRecords;
             uniform.regionPieces = ctx->regionPieces;
             uniform.levels = ctx->levels;
-            kernel = known    ? memb_pooled::uniformKernelKnown(lookup.outType)
-                     : narrow ? memb_pooled::uniformKernelNarrow(lookup.outType)
-                              : memb_pooled::uniformKernel();
-            name = known ? "pool_known_uniform" : "pool_uniform";
             arguments[0] = &uniform;
             break;
         case memb::wire::Storage_Full:
+            storage = memb_pooled::PoolStorage::Full;
             full = rowwiseParams<FullParams>(ctx, lookup);
             full.values = ctx->fullValues;
-            kernel = known    ? memb_pooled::fullKernelKnown(lookup.outType)
-                     : narrow ? memb_pooled::fullKernelNarrow(lookup.outType)
-                              : memb_pooled::fullKernel();
-            name = known ? "pool_known_full" : "pool_full";
             arguments[0] = &full;
             break;
         default:
             return fail(MEMB_HIP_ERR_INVALID, "context has no storage");
     }
+    const memb_pooled::PoolKernel chosen =
+        memb_pooled::pooledKernel(storage, lookupHasSub(ctx), ctx->fast, vec4, lookup.outType, known != nullptr);
+    const void* kernel = chosen.address;
+    const char* name = chosen.name;
     if (!kernel) {
         return fail(MEMB_HIP_ERR_INVALID, std::string("internal error: no ") + name + " kernel for this output");
     }

@@ -3,8 +3,8 @@
 //
 // A translation unit of its own, linked into libmemb_hip.so; memb_hip.hip lays out the caller's workspace and launches these
 // kernels through the addresses below (hip_pooled_chunked.h). The partial sums themselves -- one per chunk of
-// MEMB_HIP_POOL_CHUNK entries -- are MEMB_HIP_POOL_SUM of the sequential kernels (memb_hip_pooled.hip,
-// memb_hip_pooled_known.hip) over the derived offsets that the plan writes; those kernels are not touched.
+// MEMB_HIP_POOL_CHUNK entries -- are MEMB_HIP_POOL_SUM of the sequential kernels (memb_hip_pooled.hip, plain or known)
+// over the derived offsets that the plan writes; those kernels are not touched.
 //   chunk_block_sums / chunk_scan_sums / chunk_bag_starts
 //       the exclusive scan of the bags' chunk counts max(1, ceil(L / C)), in three passes: sums per block of bags, the scan
 //       of those sums by ONE block, the scan inside each block on top of its sum. No block reads what a block of the same

@@ -1,5 +1,6 @@
 """Pooled lookups without a GPU: the C header and entry points of include/memb_hip_pooled.h, and what the compiler made of
-the kernels of memb_hip_pooled.hip (tools/perf/isa.py, source=POOLED_SOURCE)."""
+the kernels of memb_hip_pooled.hip (tools/perf/isa.py, source=POOLED_SOURCE), family by family: the fp32 kernels, their
+bf16 / fp16 forms and the kernels that skip missing rows."""
 import collections
 import ctypes
 import os
@@ -56,54 +57,109 @@ def test_pooled_entry_is_exported_and_refuses_bad_arguments(native):
     assert hasattr(_memb.Reader, 'pool_rows_to_device')
 
 
+KEY_FORMS = (('false', 'true'), ('false', 'false'), ('true', 'false'))   # <HAS_SUB, FAST>
+# family: the trained kernel (the row-wise ones are named alike), its out types as template arguments (None: fp32, not a
+# template argument), the least v_add_f32_e32 its code must hold
+FAMILIES = {
+    'fp32': ('pool_trained', None, 8),
+    'narrow': ('pool_trained_narrow', ('1', '2'), 16),
+    'known': ('pool_known_trained', ('0', '1', '2'), 24),
+}
+
+
+def family_names(family):
+    trained = FAMILIES[family][0]
+    return trained, trained.replace('trained', 'uniform'), trained.replace('trained', 'full')
+
+
+def kernel_family(name):
+    return name.split('(')[0].split('<')[0].split(' ')[-1]
+
+
+def template_arguments(name):
+    return name.split('<')[1].split('>')[0].split(', ')
+
+
 @pytest.fixture(scope='module')
-def kernels():
+def unit():
     import isa
     return {name.replace('(anonymous namespace)::', ''): facts for name, facts in isa.kernel_table(source=isa.POOLED_SOURCE).items()}
 
 
-@needs_hipcc
-def test_the_pooled_kernel_families(kernels):
-    # pool_trained: three key forms x (column form, 16-byte pieces); one row-wise kernel per other storage. Nothing else:
-    # the staging kernels stay in memb_hip.hip alone.
-    families = collections.Counter(name.split('(')[0].split('<')[0].split(' ')[-1] for name in kernels)
-    assert families == {'pool_trained': 6, 'pool_uniform': 1, 'pool_full': 1}, families
-    forms = sorted(name.split('<')[1].split('>')[0] for name in kernels if 'pool_trained<' in name)
-    assert forms == sorted('{}, {}, {}'.format(has_sub, fast, vec4) for has_sub, fast in
-                           (('false', 'true'), ('false', 'false'), ('true', 'false')) for vec4 in ('false', 'true')), forms
+@pytest.fixture(params=sorted(FAMILIES))
+def family(request):
+    return request.param
+
+
+@pytest.fixture
+def kernels(unit, family):
+    return {name: facts for name, facts in unit.items() if kernel_family(name) in family_names(family)}
+
+
+@pytest.fixture
+def code(kernels):
+    return '\n'.join(facts['code'] for facts in kernels.values())
 
 
 @needs_hipcc
-def test_pooled_kernels_spill_nothing_and_store_plainly(kernels):
-    import isa
+def test_the_unit_holds_the_three_families_and_nothing_else(unit):
+    # the staging kernels stay in memb_hip.hip alone, the chunked order's in memb_hip_pooled_chunked.hip
+    assert {kernel_family(name) for name in unit} == {name for family in FAMILIES for name in family_names(family)}
+    assert len(unit) == 8 + 16 + 24
+
+
+@needs_hipcc
+def test_the_pooled_kernel_families(kernels, family):
+    # trained: three key forms x (column form, pieces) x the family's out types; one row-wise kernel per other storage and type
+    trained, uniform, full = family_names(family)
+    outs = FAMILIES[family][1]
+    types = len(outs or (None,))
+    assert collections.Counter(kernel_family(name) for name in kernels) == {trained: 6 * types, uniform: types, full: types}
+    forms = sorted(tuple(template_arguments(name)) for name in kernels if trained + '<' in name)
+    assert forms == sorted((has_sub, fast, vec4) + ((out,) if outs else ()) for has_sub, fast in KEY_FORMS
+                           for vec4 in ('false', 'true') for out in outs or (None,)), forms
+    for rowwise in (uniform, full) if outs else ():
+        assert sorted(template_arguments(name)[0] for name in kernels if rowwise + '<' in name) == list(outs)
+
+
+@needs_hipcc
+def test_pooled_kernels_spill_nothing_and_store_plainly(kernels, code):
     for name, facts in kernels.items():
         assert facts['private_segment'] == 0 and facts['scratch_ops'] == 0, (name, facts)
         assert facts['load_nt'] == 0 and facts['store_nt'] == 0, (name, facts)
-    text = isa.device_assembly(source=isa.POOLED_SOURCE)
-    stores = re.findall(r'^\s*(?:global|flat|buffer)_store_\w+\s.*$', text, flags=re.M)
+    stores = re.findall(r'^\s*(?:global|flat|buffer)_store_\w+\s.*$', code, flags=re.M)
     assert stores and not [line for line in stores if re.search(r'\b(sc0|sc1|nt)\b', line)]
     # no atomics: the result is a function of the inputs alone
-    assert not re.findall(r'^\s*(?:global|flat|buffer|ds)_atomic_\w+\s', text, flags=re.M)
-    assert not re.findall(r'^\s*ds_\w+_rtn_\w+\s', text, flags=re.M)
+    assert not re.findall(r'^\s*(?:global|flat|buffer|ds)_atomic_\w+\s', code, flags=re.M)
+    assert not re.findall(r'^\s*ds_\w+_rtn_\w+\s', code, flags=re.M)
 
 
 @needs_hipcc
-def test_every_accumulator_add_is_a_single_lane_op():
+def test_every_accumulator_add_is_a_single_lane_op(code, family):
     # the packed forms flush subnormals on gfx950: the sums are v_add_f32 only
-    import isa
-    text = isa.device_assembly(source=isa.POOLED_SOURCE)
-    assert not re.findall(r'^\s*v_pk_(?:add|mul|fma)_f32\s', text, flags=re.M)
-    assert len(re.findall(r'^\s*v_add_f32_e32\s', text, flags=re.M)) >= 8
-    assert not re.findall(r'^\s*v_(?:fmac|fma|mac)_f32\s.*;.*addRn', text, flags=re.M)
+    assert not re.findall(r'^\s*v_pk_(?:add|mul|fma)_f32\s', code, flags=re.M)
+    assert len(re.findall(r'^\s*v_add_f32_e32\s', code, flags=re.M)) >= FAMILIES[family][2]
+    assert not re.findall(r'^\s*v_(?:fmac|fma|mac)_f32\s.*;.*addRn', code, flags=re.M)
 
 
 @needs_hipcc
-def test_trained_pooled_kernels_keep_the_one_tile_residency(kernels):
-    # memb_hip.hip plans pool_trained like decode_trained, with ONE_TILE_WAVES_PER_CU = 28: seven per SIMD was planned for
-    # (eight accumulator registers on top of the decode's), and seven is what the compiler gave
+def test_trained_pooled_kernels_keep_the_one_tile_residency_and_their_store_widths(kernels, family):
+    # memb_hip.hip plans every trained kernel like decode_trained, with ONE_TILE_WAVES_PER_CU = 28: seven wavefronts per SIMD
+    # was planned for (eight accumulator registers on top of the decode's), and seven is what the compiler gave.
+    # fp32: the piece form leaves as 16-byte stores. bf16 / fp16: as 8-byte stores of four elements, and the column form --
+    # any alignment -- as single elements only.
     import isa
-    for name, facts in kernels.items():
-        if 'pool_trained<' in name:
-            assert isa.waves_per_simd(facts['vgpr'], facts['sgpr_count']) == 7, (name, facts)
-            vec4 = name.split('<')[1].split('>')[0].split(', ')[2] == 'true'
+    trained = family_names(family)[0]
+    instances = {name: facts for name, facts in kernels.items() if trained + '<' in name}
+    assert len(instances) == 6 * len(FAMILIES[family][1] or (None,))
+    for name, facts in instances.items():
+        assert isa.waves_per_simd(facts['vgpr'], facts['sgpr_count']) == 7, (name, facts)
+        vec4 = template_arguments(name)[2] == 'true'
+        stores = collections.Counter(re.findall(r'^\s*(?:global|flat|buffer)_store_(\w+)\s', facts['code'], flags=re.M))
+        if family == 'fp32':
             assert (facts['store_x4'] >= 1) == vec4, (name, facts)
+        elif family == 'narrow':
+            assert (stores['dwordx2'] >= 1) == vec4, (name, stores)
+            assert facts['store_x4'] == 0 and stores['dwordx3'] == 0, (name, stores)
+            if not vec4:
+                assert set(stores) == {'short'}, (name, stores)

@@ -2,8 +2,9 @@
 registers, scratch and LDS, read from the device assembly (no GPU needed).
 
     python tools/perf/isa.py [substring of the demangled kernel name] [-- extra hipcc flags]
-    python tools/perf/isa.py --digests     one line per kernel of both translation units, instruction digest and resources: run it
-                                           on two commits and diff the listings to see which kernels a change touched
+    python tools/perf/isa.py --digests     one line per kernel of every translation unit of libmemb_hip.so (SOURCES),
+                                           instruction digest and resources: run it on two commits and diff the listings
+                                           to see which kernels a change touched
 
 tests/test_isa.py uses kernel_table() to pin facts a source-level reading can get wrong: round 2 shipped
 `flag ? *p : __builtin_nontemporal_load(p)`, which LLVM folds into ONE plain load, and reported the
@@ -21,9 +22,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip.hip')
 NARROW_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_narrow.hip')
 POOLED_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_pooled.hip')
-POOLED_NARROW_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_pooled_narrow.hip')
-POOLED_KNOWN_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_pooled_known.hip')
 POOLED_CHUNKED_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_pooled_chunked.hip')
+SOURCES = (SOURCE, NARROW_SOURCE, POOLED_SOURCE, POOLED_CHUNKED_SOURCE)   # every translation unit of build_native.build_hip_library
 # the flags of build_native.build_hip_library
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt',
          '-Wno-unused-value', '-Wno-align-mismatch', '-Wno-pass-failed', '-Wno-unused-command-line-argument']
@@ -45,10 +45,19 @@ def device_assembly(extra_flags=(), source=SOURCE):
             return f.read()
 
 
+def _instructions(code, symbol):
+    """A kernel's instructions and labels as text that does not depend on the translation unit the kernel lives in or on
+    its place there: without the kernel's own symbol, the function number of its labels (.LBB<n>_<m>, .Lfunc_end<n>) and
+    the compiler's comments, which repeat that number (`; in Loop: Header=BB<n>_<m>`) behind padding as wide as the label"""
+    code = re.sub(r'\.(LBB|Lfunc_begin|Lfunc_end)\d+', r'.\1', code.replace(symbol, 'KERNEL'))
+    lines = (re.sub(r'\s*;.*$', '', line) for line in code.split('\n'))
+    return '\n'.join(line for line in lines if line.strip())
+
+
 def kernel_table(extra_flags=(), source=SOURCE):
     """{demangled kernel name: facts} for every kernel of one translation unit of libmemb_hip.so (default memb_hip.hip;
-    NARROW_SOURCE: the bf16 / fp16 kernels; POOLED_SOURCE: the pooled ones; POOLED_NARROW_SOURCE: their bf16 / fp16 forms;
-    POOLED_KNOWN_SOURCE: the pooled kernels that skip missing rows)"""
+    NARROW_SOURCE: the bf16 / fp16 decode kernels; POOLED_SOURCE: every sequential pooled kernel; POOLED_CHUNKED_SOURCE: the
+    chunked order's; or any other path, such as a unit of another checkout)"""
     text = device_assembly(extra_flags, source)
     names = re.findall(r'^\s*\.amdhsa_kernel (\S+)$', text, flags=re.M)
     demangled = subprocess.run([_tool('c++filt')], input='\n'.join(names), stdout=subprocess.PIPE, text=True,
@@ -88,8 +97,8 @@ def kernel_table(extra_flags=(), source=SOURCE):
             'accum_offset': field('amdhsa_accum_offset'),
             'private_segment': field('amdhsa_private_segment_fixed_size'),
             'lds': field('amdhsa_group_segment_fixed_size'),
-            # digest of the instruction text with the function number taken out of its labels (.LBB<n>_<m> -> .LBB_<m>)
-            'digest': hashlib.sha256(re.sub(r'\.LBB\d+_(\d+)', r'.LBB_\1', code).encode()).hexdigest()[:16],
+            'code': code,
+            'digest': hashlib.sha256(_instructions(code, name).encode()).hexdigest()[:16],
             'vgpr_count': field('vgpr_count:', meta) if meta else None,
             # (.sgpr_count of the metadata = next_free_sgpr + VCC / flat scratch / XNACK: what the hardware allocates by)
             'sgpr_count': field('sgpr_count:', meta) if meta else None,
@@ -97,11 +106,12 @@ def kernel_table(extra_flags=(), source=SOURCE):
     return table
 
 
-def kernel_digests():
-    """{demangled kernel name: (digest of its instructions, vgpr, sgpr_count, LDS bytes, scratch bytes)} over both translation
-    units: equal before and after a change that is meant to leave the device code alone"""
+def kernel_digests(sources=SOURCES):
+    """{demangled kernel name: (digest of its instructions, vgpr, sgpr_count, LDS bytes, scratch bytes)} over every
+    translation unit of the library (or the units given): equal before and after a change that is meant to leave the device
+    code alone, wherever it moves a kernel"""
     return {pretty: (facts['digest'], facts['vgpr'], facts['sgpr_count'], facts['lds'], facts['private_segment'])
-            for source in (SOURCE, NARROW_SOURCE) for pretty, facts in kernel_table(source=source).items()}
+            for source in sources for pretty, facts in kernel_table(source=source).items()}
 
 
 def waves_per_simd(vgpr, sgpr_count=None):
@@ -121,8 +131,8 @@ if __name__ == '__main__':
     if '--' in arguments:
         extra = arguments[arguments.index('--') + 1:]
         arguments = arguments[:arguments.index('--')]
-    if arguments[:1] == ['--digests']:   # one line per kernel, to diff against another commit's
-        for pretty, facts in sorted(kernel_digests().items()):
+    if arguments[:1] == ['--digests']:   # one line per kernel, to diff against another commit's; [units of that commit]
+        for pretty, facts in sorted(kernel_digests(arguments[1:] or SOURCES).items()):
             print(pretty.replace('(anonymous namespace)::', '').split('(')[0], *facts)
         sys.exit(0)
     needle = arguments[0] if arguments else ''
