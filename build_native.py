@@ -55,11 +55,11 @@ def _hipcc():
 def build_hip_library(force=False, extra_flags=()):
     sources = [os.path.join(CSRC, name) for name in
                ('memb_hip.hip', 'memb_hip_narrow.hip', 'memb_hip_pooled.hip', 'memb_hip_pooled_chunked.hip',
-                'hip_pooled_chunked.h', 'hip_narrow.h', 'hip_pooled.h', 'hip_pooled_kernels.h', 'hip_device_common.h', 'hip_trained_kernels.h',
+                'memb_hip_pooled_union.hip', 'hip_pooled_union.h', 'hip_pooled_chunked.h', 'hip_narrow.h', 'hip_pooled.h', 'hip_pooled_kernels.h', 'hip_device_common.h', 'hip_trained_kernels.h',
                 'hip_rowwise_kernels.h', 'hip_host_path.h', 'hip_encoder.h', 'hip_encoder_kernels.h', 'hip_words.h',
                 'hip_words_kernels.h', 'worker_pool.h', 'codec.h', 'wire.h')]
     sources += [os.path.join(INCLUDE, name) for name in ('memb_hip.h', 'memb_hip_narrow.h', 'memb_hip_pooled.h', 'memb_hip_pooled_known.h',
-                                                        'memb_hip_pooled_chunked.h')]
+                                                        'memb_hip_pooled_chunked.h', 'memb_hip_pooled_union.h')]
     if force or _newer(HIP_LIBRARY, sources):
         _run([
             _hipcc(), '--offload-arch=' + GPU_ARCH, '-O3', '-std=c++17', '-fPIC', '-shared',
@@ -68,6 +68,7 @@ def build_hip_library(force=False, extra_flags=()):
             '-Wno-unused-value', '-Wno-align-mismatch', '-Wno-pass-failed', *extra_flags,
             '-o', HIP_LIBRARY, os.path.join(CSRC, 'memb_hip.hip'), os.path.join(CSRC, 'memb_hip_narrow.hip'),
             os.path.join(CSRC, 'memb_hip_pooled.hip'), os.path.join(CSRC, 'memb_hip_pooled_chunked.hip'),
+            os.path.join(CSRC, 'memb_hip_pooled_union.hip'),
         ])
     return HIP_LIBRARY
 
@@ -79,7 +80,7 @@ def build_extension(force=False):
     headers = [os.path.join(CSRC, name) for name in
                ('reader.h', 'builder.h', 'compression_strategy.h', 'worker_pool.h', 'codec.h', 'wire.h')]
     headers += [os.path.join(INCLUDE, name) for name in ('memb_hip.h', 'memb_hip_narrow.h', 'memb_hip_pooled.h', 'memb_hip_pooled_known.h',
-                                                        'memb_hip_pooled_chunked.h')]
+                                                        'memb_hip_pooled_chunked.h', 'memb_hip_pooled_union.h')]
     build_hip_library(force)
     if force or _newer(EXTENSION, sources + headers + [HIP_LIBRARY]):
         _run([

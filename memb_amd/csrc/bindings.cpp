@@ -7,6 +7,7 @@
 #include "reader.h"
 #include "compression_strategy.h"
 #include "codec.h"
+#include "../../include/memb_hip_pooled_union.h"
 
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -1095,6 +1096,84 @@ PYBIND11_MODULE(_memb, m) {
         py::arg("ld"),
         py::arg("stream") = 0,
         py::arg("average") = false);
+    // ReadersUnion 'average' pooled in one launch (memb_hip_pool_rows_union_device); false when the readers cannot share
+    // the kernel (the caller then merges the rows and pools them with pool_dense_rows_to_device). Device pointers.
+    m.def(
+        "pool_union_rows_to_device",
+        [](const std::vector<std::shared_ptr<memb::Reader>>& readers,
+           const std::vector<uintptr_t>& rows,
+           size_t n,
+           uintptr_t offsets,
+           size_t bags,
+           uintptr_t out,
+           size_t ld,
+           size_t colOff,
+           int mode,
+           uintptr_t stream,
+           int outType)
+        {
+            if (readers.size() != rows.size() || readers.empty()) {
+                throw std::runtime_error("One row-id array per reader is needed");
+            }
+            std::vector<memb_hip_ctx*> contexts;
+            std::vector<const uint32_t*> rowPointers;
+            for (size_t i = 0; i < readers.size(); ++i) {
+                contexts.push_back(readers[i]->deviceContext());
+                rowPointers.push_back(reinterpret_cast<const uint32_t*>(rows[i]));
+            }
+            const int code = memb_hip_pool_rows_union_device(
+                contexts.data(), rowPointers.data(), readers.size(), n, reinterpret_cast<const uint32_t*>(offsets), bags,
+                reinterpret_cast<void*>(out), outType, ld, colOff, mode, reinterpret_cast<void*>(stream));
+            if (code == MEMB_HIP_UNSUPPORTED) {
+                return false;
+            }
+            if (code != MEMB_HIP_OK) {
+                throw std::runtime_error(std::string("memb_hip_pool_rows_union_device: ") + memb_hip_last_error());
+            }
+            return true;
+        },
+        py::arg("readers"),
+        py::arg("rows_ptrs"),
+        py::arg("n"),
+        py::arg("offsets_ptr"),
+        py::arg("bags"),
+        py::arg("out_ptr"),
+        py::arg("ld"),
+        py::arg("col_off") = 0,
+        py::arg("mode") = MEMB_HIP_POOL_MEAN,
+        py::arg("stream") = 0,
+        py::arg("out_type") = MEMB_HIP_OUT_F32);
+    // what the last pooled union launch with this reader as its first ran ("" before any)
+    m.def("pool_union_kernel_name", [](const std::shared_ptr<memb::Reader>& first) {
+        return std::string(memb_hip_pool_union_kernel_name(first->deviceContext()));
+    });
+    // the kernel pool_dense_rows_to_device launches for an out type
+    m.def("pool_dense_kernel_name", [](int outType) { return std::string(memb_hip_pool_dense_kernel_name(outType)); });
+    // the bags of n rows of a dense fp32 matrix on `device` (memb_hip_pool_dense_rows_device). Device pointers.
+    m.def(
+        "pool_dense_rows_to_device",
+        [](int device, uintptr_t values, size_t n, size_t dim, size_t ldValues, uintptr_t offsets, size_t bags, uintptr_t out,
+           size_t ld, size_t colOff, int mode, uintptr_t stream, int outType)
+        {
+            if (memb_hip_pool_dense_rows_device(
+                    device, reinterpret_cast<const float*>(values), n, dim, ldValues, reinterpret_cast<const uint32_t*>(offsets),
+                    bags, reinterpret_cast<void*>(out), outType, ld, colOff, mode, reinterpret_cast<void*>(stream)) != MEMB_HIP_OK) {
+                throw std::runtime_error(std::string("memb_hip_pool_dense_rows_device: ") + memb_hip_last_error());
+            }
+        },
+        py::arg("device"),
+        py::arg("values_ptr"),
+        py::arg("n"),
+        py::arg("dim"),
+        py::arg("ld_values"),
+        py::arg("offsets_ptr"),
+        py::arg("bags"),
+        py::arg("out_ptr"),
+        py::arg("ld"),
+        py::arg("col_off") = 0,
+        py::arg("mode") = MEMB_HIP_POOL_MEAN,
+        py::arg("stream") = 0,
+        py::arg("out_type") = MEMB_HIP_OUT_F32);
     // one batch of words resolved by several readers of one device (ReadersUnion): packed and copied once
     m.def(
         "union_words_to_rows_device",

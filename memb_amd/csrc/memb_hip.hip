@@ -34,7 +34,8 @@
 // that includes the same device headers and hands its kernels over as addresses
 // (hip_narrow.h), planned and launched here; memb_hip_pooled.hip -- every sequential pooled kernel (sum / mean
 // of each bag of rows or of its known rows, as fp32, bf16 or fp16), handed over the same way through one selector
-// (hip_pooled.h); memb_hip_pooled_chunked.hip -- the chunked order's (hip_pooled_chunked.h); hip_host_path.h -- how rows reach host
+// (hip_pooled.h); memb_hip_pooled_chunked.hip -- the chunked order's (hip_pooled_chunked.h); memb_hip_pooled_union.hip -- the
+// pooled kernels of a ReadersUnion's averaged rows and of dense rows (hip_pooled_union.h); hip_host_path.h -- how rows reach host
 // buffers (pinned ring, copy threads, centroid indices over PCIe).
 #include <hip/hip_runtime.h>
 
@@ -43,10 +44,12 @@
 #include "../../include/memb_hip_pooled.h"
 #include "../../include/memb_hip_pooled_known.h"
 #include "../../include/memb_hip_pooled_chunked.h"
+#include "../../include/memb_hip_pooled_union.h"
 #include "codec.h"
 #include "hip_narrow.h"
 #include "hip_pooled.h"
 #include "hip_pooled_chunked.h"
+#include "hip_pooled_union.h"
 #include "wire.h"
 #include "worker_pool.h"
 
@@ -185,6 +188,7 @@ struct memb_hip_ctx {
     uint32_t fineSymbols = 0;
     uint32_t recordPieces = 0;           // non-zero: row records (TrainedParams::recordPieces); `streams` is that array
     const char* unionKernel = "";        // what the last union launch with this context as its first model ran (kernelTable)
+    const char* pooledUnionKernel = "";  // ... and the last pooled union launch (memb_hip_pool_union_kernel_name)
     uint32_t lanesPerWord = 1;           // G: lanes that share one word
     uint32_t segmentSymbols = 0;         // S: symbols per lane, multiple of 4
     std::vector<uint32_t> streamBytes;   // per row, host side (reporting only)
@@ -976,10 +980,19 @@ int launchTrainedBatches(memb_hip_ctx* ctx, const memb_hip_batch* batches, size_
     return MEMB_HIP_OK;
 }
 
-// See memb_hip_decode_rows_union_device. MEMB_HIP_UNSUPPORTED when the models cannot share the kernel.
-int launchTrainedUnion(
-    memb_hip_ctx* const* ctxs, const uint32_t* const* rows, const size_t* colOffs, size_t count, size_t n, float* out,
-    size_t ld, hipStream_t stream, bool average)
+// What the union kernels share (decode_trained_union, decode_union_split, pool_trained_union): the conditions under which
+// models can share one -- MEMB_HIP_UNSUPPORTED with the reason otherwise -- and their parameters: every model's own tables,
+// streams and row ids, one output (whose elements are elementBytes wide), tables and codebooks laid out in the block's LDS.
+struct UnionPlan {
+    UnionParams params{};
+    bool hasSub = false;
+    bool allFast = true;
+    uint32_t wordsPerWave = 0;
+};
+
+int planUnion(
+    memb_hip_ctx* const* ctxs, const uint32_t* const* rows, const size_t* colOffs, size_t count, size_t n, void* out,
+    size_t elementBytes, size_t ld, UnionPlan* plan)
 {
     // (MEMB_HIP_UNSUPPORTED is not an error, but memb_hip_last_error() says which condition it was)
     if (count < 2 || count > UNION_MAX_MODELS || (ctxs[0] && ctxs[0]->switches.unionFused == 0)) {
@@ -1011,20 +1024,21 @@ int launchTrainedUnion(
     }
     // Nibble keys (<= 16 centroids, codes <= 8 bits) only when every model has them; a mixed union decodes the
     // nibble-key models through their byte-key tables (memb_hip_ctx::table32): the same symbols, one per byte.
-    if (ld % 4 != 0 || reinterpret_cast<uintptr_t>(out) % 16 != 0 || n > (size_t(1) << 37)) {
+    // (a piece of four elements: 16 bytes of fp32, 8 of bf16 / fp16)
+    if (ld % 4 != 0 || reinterpret_cast<uintptr_t>(out) % (4 * elementBytes) != 0 || n > (size_t(1) << 37)) {
         return fail(MEMB_HIP_UNSUPPORTED, "union kernel: the output is not 16-byte aligned in every row");
     }
     const uint32_t wordsPerWave = WAVE / first->lanesPerWord;
-    const size_t tiles = (n + wordsPerWave - 1) / wordsPerWave;
 
-    UnionParams params{};
+    UnionParams& params = plan->params;
+    params = UnionParams{};
     uint32_t sharedDwords = 0;
     for (size_t m = 0; m < count; ++m) {
         memb_hip_ctx* ctx = ctxs[m];
         TrainedParams& p = params.model[m];
         p = baseTrainedParams(ctx);
         p.rows = rows[m];
-        p.out = out;
+        p.out = static_cast<float*>(out);   // (2-byte elements for a narrow type)
         p.n = n;
         p.ld = ld;
         p.colOff = colOffs[m];
@@ -1053,44 +1067,74 @@ int launchTrainedUnion(
     params.codebookOffsetDwords = sharedDwords;
     sharedDwords += static_cast<uint32_t>(count) * 512;
     params.sharedDwords = sharedDwords;
+    plan->hasSub = hasSub;
+    plan->allFast = allFast;
+    plan->wordsPerWave = wordsPerWave;
+    return MEMB_HIP_OK;
+}
+
+// one wavefront's LDS area in decode_trained_union and pool_trained_union: bitstream slots and a symbol tile per model
+void layOutUnionWave(memb_hip_ctx* const* ctxs, size_t count, uint32_t wordsPerWave, UnionParams* params)
+{
+    uint32_t at = 0;
+    for (size_t m = 0; m < count; ++m) {
+        params->slotOffsetDwords[m] = at;
+        at += roundUp4(wordsPerWave * ctxs[m]->slotDwords);
+        params->keyTileOffsetDwords[m] = at;
+        at += roundUp4(params->model[m].keyTileDwords);
+    }
+    params->perWaveDwords = at;
+}
+
+// waves per block of a union kernel: most resident wavefronts per CU -- by LDS and by the kernel's registers --, blocks of
+// four on ties (as chooseGeometry); 0 when no block size fits
+hipError_t chooseUnionWaves(
+    const memb_hip_ctx* first, const void* kernel, uint32_t sharedDwords, uint32_t perWaveDwords, uint32_t* waves, uint32_t* ldsBytes)
+{
+    KernelFacts facts;
+    const hipError_t status = kernelFacts(kernel, &facts);
+    uint32_t bestResident = 0;
+    *waves = 0;
+    // (a forced block size -- option waves_per_block, 1 .. 16 -- is the only candidate, as in chooseGeometry)
+    const uint32_t forced = first->switches.waves;
+    for (uint32_t candidate : {forced ? forced : 4u, 8u, 2u, 1u}) {
+        if (forced && candidate != forced) {
+            continue;
+        }
+        const uint32_t bytes = 4u * (sharedDwords + candidate * perWaveDwords);
+        const uint32_t resident = residentWaves(first->ldsLimit, candidate, bytes, facts.registerWavesPerCu);
+        if (resident > bestResident) {
+            bestResident = resident;
+            *waves = candidate;
+            *ldsBytes = bytes;
+        }
+    }
+    return status;
+}
+
+// See memb_hip_decode_rows_union_device. MEMB_HIP_UNSUPPORTED when the models cannot share the kernel.
+int launchTrainedUnion(
+    memb_hip_ctx* const* ctxs, const uint32_t* const* rows, const size_t* colOffs, size_t count, size_t n, float* out,
+    size_t ld, hipStream_t stream, bool average)
+{
+    UnionPlan plan;
+    const int planned = planUnion(ctxs, rows, colOffs, count, n, out, sizeof(float), ld, &plan);
+    if (planned != MEMB_HIP_OK) {
+        return planned;
+    }
+    const memb_hip_ctx* first = ctxs[0];
+    UnionParams& params = plan.params;
+    const bool hasSub = plan.hasSub;
+    const bool allFast = plan.allFast;
+    const uint32_t wordsPerWave = plan.wordsPerWave;
+    const uint32_t sharedDwords = params.sharedDwords;
+    const size_t tiles = (n + wordsPerWave - 1) / wordsPerWave;
     params.rowPieces = (average ? 1u : static_cast<uint32_t>(count)) * (first->dim / 4);
     params.rowMagic = magicFor(params.rowPieces, uint64_t(wordsPerWave) * params.rowPieces);
-
-    // one wavefront's LDS area in decode_trained_union: bitstream slots and a symbol tile per model
-    auto layOut = [&] {
-        uint32_t at = 0;
-        for (size_t m = 0; m < count; ++m) {
-            params.slotOffsetDwords[m] = at;
-            at += roundUp4(wordsPerWave * ctxs[m]->slotDwords);
-            params.keyTileOffsetDwords[m] = at;
-            at += roundUp4(params.model[m].keyTileDwords);
-        }
-        params.perWaveDwords = at;
-    };
-
-    // waves per block: most resident wavefronts per CU -- by LDS and by the kernel's registers --, blocks of
-    // four on ties (as chooseGeometry); 0 when no block size fits
+    auto layOut = [&] { layOutUnionWave(ctxs, count, wordsPerWave, &params); };
     auto chooseWaves = [&](const KernelInstance<UnionParams>& kernel, uint32_t sharedDwords, uint32_t perWaveDwords,
                            uint32_t* waves, uint32_t* ldsBytes) -> hipError_t {
-        KernelFacts facts;
-        const hipError_t status = kernelFacts(kernel.fn, &facts);
-        uint32_t bestResident = 0;
-        *waves = 0;
-        // (a forced block size -- option waves_per_block, 1 .. 16 -- is the only candidate, as in chooseGeometry)
-        const uint32_t forced = first->switches.waves;
-        for (uint32_t candidate : {forced ? forced : 4u, 8u, 2u, 1u}) {
-            if (forced && candidate != forced) {
-                continue;
-            }
-            const uint32_t bytes = 4u * (sharedDwords + candidate * perWaveDwords);
-            const uint32_t resident = residentWaves(first->ldsLimit, candidate, bytes, facts.registerWavesPerCu);
-            if (resident > bestResident) {
-                bestResident = resident;
-                *waves = candidate;
-                *ldsBytes = bytes;
-            }
-        }
-        return status;
+        return chooseUnionWaves(first, reinterpret_cast<const void*>(kernel.fn), sharedDwords, perWaveDwords, waves, ldsBytes);
     };
     uint32_t waves = 0;
     uint32_t ldsBytes = 0;
@@ -1157,7 +1201,13 @@ int launchTrainedUnion(
         }
         // (does not fit: the forms below lay their areas out afresh)
     }
-    // decode_trained_union, one tile per wavefront: three or four models, pairs without row records
+    // decode_trained_union, one tile per wavefront: three or four models, pairs without row records.
+    // Its outputUnionTile keeps the words a nibble-key model lacks as one bit per (word, model) of a tile in ONE 64-bit mask:
+    // a tile of more than 64 such pairs -- one lane per word (dim < 8), or three and four models at two or three lanes per
+    // word -- does not fit (decode_union_split above has tiles of half as many words of two models: at most 64 pairs)
+    if (allFast && uint64_t(wordsPerWave) * count > WAVE) {
+        return fail(MEMB_HIP_UNSUPPORTED, "union kernel: nibble keys and more than 64 (word, model) pairs in a tile");
+    }
     layOut();
     const KernelInstance<UnionParams>& kernel = kernelTable().unions[hasSub && !allFast][allFast][count][average];
     hipError_t status = chooseWaves(kernel, sharedDwords, params.perWaveDwords, &waves, &ldsBytes);
@@ -1464,6 +1514,92 @@ int launchPooled(
         launchKernelAddress(kernel, dim3(static_cast<uint32_t>(blocks)), dim3(waves * WAVE), ldsBytes, stream, arguments);
     if (status != hipSuccess) {
         return fail(MEMB_HIP_ERR_DEVICE, std::string(name) + " launch: " + hipGetErrorString(status));
+    }
+    return MEMB_HIP_OK;
+}
+
+// A pooled lookup of a union's AVERAGED rows (include/memb_hip_pooled_union.h): pool_trained_union of
+// memb_hip_pooled_union.hip, for the unions launchTrainedUnion takes (planUnion) whose dim fits pool_trained's register
+// form; MEMB_HIP_UNSUPPORTED with the reason otherwise, nothing launched. LDS per wavefront and the shared image are
+// decode_trained_union's, the block size the one with the most resident wavefronts (chooseUnionWaves), the bags of a
+// wavefront launchPooled's.
+int launchPooledUnion(
+    memb_hip_ctx* const* ctxs, const uint32_t* const* rows, size_t count, size_t n, memb_pooled::PoolParams pool, void* out,
+    int outType, size_t ld, size_t colOff, hipStream_t stream)
+{
+    if (n > (size_t(1) << 37) || pool.bags >= (1ull << 37)) {
+        return fail(MEMB_HIP_ERR_INVALID, "batch too large");
+    }
+    size_t colOffs[UNION_MAX_MODELS];
+    for (size_t m = 0; m < UNION_MAX_MODELS; ++m) {
+        colOffs[m] = colOff;
+    }
+    UnionPlan plan;
+    const int planned = planUnion(ctxs, rows, colOffs, count, n, out, outType == MEMB_HIP_OUT_F32 ? 4 : 2, ld, &plan);
+    if (planned != MEMB_HIP_OK) {
+        return planned;
+    }
+    memb_hip_ctx* first = ctxs[0];
+    if (first->dim > memb_pooled::TRAINED_VEC4_MAX_DIM) {
+        return fail(MEMB_HIP_UNSUPPORTED, "pooled union kernel: dim beyond the register form (" + std::to_string(memb_pooled::TRAINED_VEC4_MAX_DIM) + ")");
+    }
+    UnionParams& params = plan.params;
+    params.rowPieces = first->dim / 4;
+    params.rowMagic = magicFor(params.rowPieces, uint64_t(plan.wordsPerWave) * params.rowPieces);
+    layOutUnionWave(ctxs, count, plan.wordsPerWave, &params);
+    const memb_pooled::PoolKernel kernel =
+        memb_pooled::pooledUnionKernel(plan.hasSub && !plan.allFast, plan.allFast, static_cast<int>(count), outType);
+    if (!kernel.address) {
+        return fail(MEMB_HIP_ERR_INVALID, std::string("internal error: no ") + kernel.name + " kernel for this output");
+    }
+    uint32_t waves = 0;
+    uint32_t ldsBytes = 0;
+    hipError_t status = chooseUnionWaves(first, kernel.address, params.sharedDwords, params.perWaveDwords, &waves, &ldsBytes);
+    if (status != hipSuccess) {
+        return fail(MEMB_HIP_ERR_DEVICE, std::string("hipFuncGetAttributes: ") + hipGetErrorString(status));
+    }
+    if (!waves) {
+        return fail(MEMB_HIP_UNSUPPORTED, "pooled union kernel: tables and bitstream slots of the models do not fit into LDS together");
+    }
+    const uint64_t tilesPerWave = first->switches.tilesPerWave ? first->switches.tilesPerWave : POOLED_TILES_PER_WAVE;
+    const uint64_t entriesPerBag = std::max<uint64_t>(1, n / std::max<uint64_t>(pool.bags, 1));
+    const uint64_t fillsTheCus = std::max<uint64_t>(1, pool.bags / (uint64_t(first->cuCount) * ONE_TILE_WAVES_PER_CU));
+    pool.bagsPerWave = static_cast<uint32_t>(std::min<uint64_t>(
+        std::min<uint64_t>(std::max<uint64_t>(1, tilesPerWave * plan.wordsPerWave / entriesPerBag), fillsTheCus), 1u << 16));
+    const uint64_t perBlock = uint64_t(waves) * pool.bagsPerWave;
+    const uint64_t blocks = (pool.bags + perBlock - 1) / perBlock;
+    if (blocks >= 0x7FFFFFFFull) {
+        return fail(MEMB_HIP_ERR_INVALID, "batches too large for one launch");
+    }
+    void* arguments[2] = {&params, &pool};
+    status = launchKernelAddress(kernel.address, dim3(static_cast<uint32_t>(blocks)), dim3(waves * WAVE), ldsBytes, stream, arguments);
+    if (status != hipSuccess) {
+        return fail(MEMB_HIP_ERR_DEVICE, std::string(kernel.name) + " launch: " + hipGetErrorString(status));
+    }
+    first->pooledUnionKernel = kernel.name;
+    return MEMB_HIP_OK;
+}
+
+// memb_hip_pool_dense_rows_device: pool_dense of memb_hip_pooled_union.hip, one wavefront per bag.
+int launchPooledDense(memb_pooled::DenseParams params, memb_pooled::PoolParams pool, int outType, hipStream_t stream)
+{
+    if (params.n > (size_t(1) << 37) || pool.bags >= (1ull << 37)) {
+        return fail(MEMB_HIP_ERR_INVALID, "batch too large");
+    }
+    const memb_pooled::PoolKernel kernel = memb_pooled::pooledDenseKernel(outType);
+    if (!kernel.address) {
+        return fail(MEMB_HIP_ERR_INVALID, std::string("internal error: no ") + kernel.name + " kernel for this output");
+    }
+    pool.bagsPerWave = 1;
+    const uint64_t blocks = (pool.bags + memb_pooled::ROWWISE_WAVES - 1) / memb_pooled::ROWWISE_WAVES;
+    if (blocks >= 0x7FFFFFFFull) {
+        return fail(MEMB_HIP_ERR_INVALID, "batches too large for one launch");
+    }
+    void* arguments[2] = {&params, &pool};
+    const hipError_t status = launchKernelAddress(
+        kernel.address, dim3(static_cast<uint32_t>(blocks)), dim3(memb_pooled::ROWWISE_WAVES * WAVE), 0, stream, arguments);
+    if (status != hipSuccess) {
+        return fail(MEMB_HIP_ERR_DEVICE, std::string(kernel.name) + " launch: " + hipGetErrorString(status));
     }
     return MEMB_HIP_OK;
 }
@@ -2477,6 +2613,88 @@ int pool_rows_device_checked(
         ctx, Lookup{rows, n, out, outType, ld, col_off}, pool, static_cast<hipStream_t>(stream), known ? &counted : nullptr);
 }
 
+// memb_hip_pool_rows_union_device (include/memb_hip_pooled_union.h)
+int pool_rows_union_device_checked(
+    memb_hip_ctx* const* ctxs, const uint32_t* const* rows, size_t count, size_t n, const uint32_t* offsets, size_t bags, void* out,
+    int outType, size_t ld, size_t col_off, int mode, void* stream)
+{
+    if (!knownOutType(outType)) {
+        return fail(MEMB_HIP_ERR_INVALID, "unknown out_type " + std::to_string(outType));
+    }
+    if (mode != MEMB_HIP_POOL_SUM && mode != MEMB_HIP_POOL_MEAN) {
+        return fail(MEMB_HIP_ERR_INVALID, "unknown pooling mode " + std::to_string(mode));
+    }
+    if (!ctxs || !rows || count == 0 || (bags && (!offsets || !out))) {
+        return fail(MEMB_HIP_ERR_INVALID, "null argument");
+    }
+    for (size_t m = 0; m < count; ++m) {
+        if (!ctxs[m] || (n && !rows[m])) {
+            return fail(MEMB_HIP_ERR_INVALID, "null argument");
+        }
+    }
+    const size_t elementBytes = outType == MEMB_HIP_OUT_F32 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(out) % elementBytes != 0) {
+        return fail(MEMB_HIP_ERR_INVALID, "out must be aligned to its element (" + std::to_string(elementBytes) + " bytes)");
+    }
+    if (col_off > ld || ld - col_off < ctxs[0]->dim) {
+        return fail(MEMB_HIP_ERR_INVALID, "ld must be at least col_off + dim");
+    }
+    if (bags == 0) {
+        return MEMB_HIP_OK;
+    }
+    DeviceScope deviceScope(ctxs[0]->device);
+    HIP_TRY(deviceScope.status());
+    memb_pooled::PoolParams pool{};
+    pool.offsets = offsets;
+    pool.bags = bags;
+    pool.mean = mode == MEMB_HIP_POOL_MEAN ? 1u : 0u;
+    return launchPooledUnion(ctxs, rows, count, n, pool, out, outType, ld, col_off, static_cast<hipStream_t>(stream));
+}
+
+// memb_hip_pool_dense_rows_device (include/memb_hip_pooled_union.h)
+int pool_dense_rows_device_checked(
+    int device, const float* values, size_t n, size_t dim, size_t ldValues, const uint32_t* offsets, size_t bags, void* out,
+    int outType, size_t ld, size_t col_off, int mode, void* stream)
+{
+    if (!knownOutType(outType)) {
+        return fail(MEMB_HIP_ERR_INVALID, "unknown out_type " + std::to_string(outType));
+    }
+    if (mode != MEMB_HIP_POOL_SUM && mode != MEMB_HIP_POOL_MEAN) {
+        return fail(MEMB_HIP_ERR_INVALID, "unknown pooling mode " + std::to_string(mode));
+    }
+    if ((n && !values) || (bags && (!offsets || !out))) {
+        return fail(MEMB_HIP_ERR_INVALID, "null argument");
+    }
+    if (dim == 0 || dim > 0xFFFFFFFFull || ldValues < dim || device < 0) {
+        return fail(MEMB_HIP_ERR_INVALID, "dim must be 1 .. 2^32 - 1, ld_values at least dim and device a HIP device");
+    }
+    const size_t elementBytes = outType == MEMB_HIP_OUT_F32 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(out) % elementBytes != 0 || reinterpret_cast<uintptr_t>(values) % 4 != 0) {
+        return fail(MEMB_HIP_ERR_INVALID, "values and out must be aligned to their elements");
+    }
+    if (col_off > ld || ld - col_off < dim) {
+        return fail(MEMB_HIP_ERR_INVALID, "ld must be at least col_off + dim");
+    }
+    if (bags == 0) {
+        return MEMB_HIP_OK;
+    }
+    DeviceScope deviceScope(device);
+    HIP_TRY(deviceScope.status());
+    memb_pooled::DenseParams params{};
+    params.values = values;
+    params.out = static_cast<float*>(out);
+    params.n = n;
+    params.ld = ld;
+    params.colOff = col_off;
+    params.ldValues = ldValues;
+    params.dim = static_cast<uint32_t>(dim);
+    memb_pooled::PoolParams pool{};
+    pool.offsets = offsets;
+    pool.bags = bags;
+    pool.mean = mode == MEMB_HIP_POOL_MEAN ? 1u : 0u;
+    return launchPooledDense(params, pool, outType, static_cast<hipStream_t>(stream));
+}
+
 // memb_hip_pool_rows_chunked_device_typed (include/memb_hip_pooled_chunked.h): the chunk plan, the partial sums of the
 // chunks -- launchPooled with MEMB_HIP_POOL_SUM over the derived offsets, into the caller's workspace -- and the bags' sums
 // of those, all enqueued on `stream`. The host knows no chunk count: every launch is sized by the workspace's bound.
@@ -3051,6 +3269,33 @@ int memb_hip_pool_known_rows_device_typed(
 {
     return guarded([&] {
         return pool_rows_device_checked(ctx, rows, n, offsets, bags, out, out_type, ld, col_off, mode, stream, true, counts);
+    });
+}
+
+int memb_hip_pool_rows_union_device(
+    memb_hip_ctx* const* ctxs, const uint32_t* const* rows, size_t count, size_t n, const uint32_t* offsets, size_t bags, void* out,
+    int out_type, size_t ld, size_t col_off, int mode, void* stream)
+{
+    return guarded([&] { return pool_rows_union_device_checked(ctxs, rows, count, n, offsets, bags, out, out_type, ld, col_off, mode, stream); });
+}
+
+const char* memb_hip_pool_union_kernel_name(const memb_hip_ctx* first)
+{
+    return first ? first->pooledUnionKernel : "";
+}
+
+const char* memb_hip_pool_dense_kernel_name(int out_type)
+{
+    const memb_pooled::PoolKernel kernel = memb_pooled::pooledDenseKernel(out_type);
+    return kernel.address ? kernel.name : "";
+}
+
+int memb_hip_pool_dense_rows_device(
+    int device, const float* values, size_t n, size_t dim, size_t ld_values, const uint32_t* offsets, size_t bags, void* out,
+    int out_type, size_t ld, size_t col_off, int mode, void* stream)
+{
+    return guarded([&] {
+        return pool_dense_rows_device_checked(device, values, n, dim, ld_values, offsets, bags, out, out_type, ld, col_off, mode, stream);
     });
 }
 

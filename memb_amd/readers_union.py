@@ -6,15 +6,17 @@ vectors side by side, mode 'average' takes their float32 mean; a word that one
 reader does not know contributes zeros there. Differences are only in how the
 rows get where they belong: for concatenation every reader decodes straight into
 its column block of the result (the C ABI's `ld` / `col_off`), and
-`batch_embedding_device` does either merge without leaving the GPU.
+`batch_embedding_device` does either merge without leaving the GPU. Pooled lookups -- the sum or mean of each bag of
+merged rows -- are `pooled_rows_device`, `pooled_sentences_device` and `pooled_rows`.
 """
 import numpy as np
 
-from .reader import BaseReader, Reader, WordBatches, tokenizer_word_list
+from .reader import BaseReader, Reader, WordBatches, _current_stream, bag_offsets, pool_mode, tokenizer_word_list
 
 CONCATENATE = 'concatenate'
 AVERAGE = 'average'
 MODES = (AVERAGE, CONCATENATE)
+POOLED_HOST_CHUNK = 1 << 16   # entries pooled_rows of a union of device='cpu' readers decodes and merges at a time
 
 
 def _merge_host(mode, pieces):
@@ -42,6 +44,7 @@ class ReadersUnion(BaseReader):
         self._mode = mode
         self._widths = widths
         self._word_batches = WordBatches()   # of batch_embedding_device (one per call in flight), shared by the readers
+        self._last_pooled_kernel = ''
 
     @property
     def dim(self):
@@ -69,39 +72,50 @@ class ReadersUnion(BaseReader):
             return merged
         return _merge_host(self._mode, [reader.batch_embedding(words) for reader in self._readers])
 
-    def batch_embedding_device(self, words):
-        """batch_embedding merged on the GPU, returned as a torch.Tensor (not in the
-        reference API). Concatenation: column blocks of one (n, dim) tensor. Average:
-        reader 1 stores, readers 2..R add, the last one also divides by R -- the very
-        additions and the one division numpy.mean performs, in its order, so the
-        result has the same bits as batch_embedding. All readers on one device. May be called from several threads
-        at once."""
-        import torch
+    def _device_index(self):
+        """The HIP device every reader is staged on; refuses unions the device methods cannot serve"""
         readers = self._readers
         if not all(isinstance(reader, Reader) for reader in readers):
             raise TypeError('device merge needs memb_amd.Reader instances')
         if len({reader.device for reader in readers}) != 1:
             raise ValueError('all readers of a union must be on one device')
         from . import _memb
-        device = 'cuda:{}'.format(readers[0].device)
+        index = readers[0]._impl.device()
+        if index == _memb.HOST_DEVICE:
+            raise RuntimeError("these readers decode on the host (device 'cpu'): device buffers need readers on a HIP device")
+        return index
+
+    def resolve_rows_device(self, words):
+        """The row ids of `words` in every reader, left on the GPU: a list of R torch.int32 tensors (views of the uint32
+        ids, 0xFFFFFFFF where a reader does not know a word), each equal to that reader's own resolve_rows_device. The
+        words are packed and copied ONCE and resolved by every reader's own hash table: the ids never visit the host.
+        May be called from several threads at once."""
+        import torch
+        from . import _memb
+        readers = self._readers
+        index = self._device_index()
+        device = 'cuda:{}'.format(index)
         stream = torch.cuda.current_stream(torch.device(device)).cuda_stream
-        # the words are packed and copied ONCE and resolved on the GPU by every reader's own hash table
-        # (Reader.resolve_rows_device): the row ids never visit the host
         row_ids = [torch.empty((len(words),), dtype=torch.int32, device=device) for _ in readers]
-        batch = self._word_batches.take(readers[0].device)
+        batch = self._word_batches.take(index)
         try:
             _memb.union_words_to_rows_device(
                 batch, words, [reader._impl for reader in readers], [ids.data_ptr() for ids in row_ids], stream)
         finally:
             self._word_batches.give(batch)
-        merged = torch.empty((len(words), self.dim), dtype=torch.float32, device=device)
-        # one launch that decodes every reader's words of a tile and writes the merged rows once,
-        # where the readers can share a kernel
+        return row_ids
+
+    def _merge_rows_device(self, row_ids, merged, stream):
+        """The merged float32 rows of one row-id tensor per reader into `merged` (n, dim), n > 0: one launch that decodes
+        every reader's words of a tile and writes the merged rows once, where the readers can share a kernel"""
+        from . import _memb
+        readers = self._readers
+        n = merged.shape[0]
         concatenate = self._mode == CONCATENATE
         columns = [sum(self._widths[:i]) if concatenate else 0 for i in range(len(readers))]
-        if len(words) and _memb.union_rows_to_device(
+        if _memb.union_rows_to_device(
                 [reader._impl for reader in readers], [ids.data_ptr() for ids in row_ids], columns,
-                len(words), merged.data_ptr(), merged.stride(0), stream, not concatenate):
+                n, merged.data_ptr(), merged.stride(0), stream, not concatenate):
             return merged
         if concatenate:
             column = 0
@@ -115,11 +129,213 @@ class ReadersUnion(BaseReader):
                 ids, out=merged, accumulate=position > 0, divisor=float(count) if position == count - 1 else 0.0)
         return merged
 
+    def batch_embedding_device(self, words):
+        """batch_embedding merged on the GPU, returned as a torch.Tensor (not in the
+        reference API). Concatenation: column blocks of one (n, dim) tensor. Average:
+        reader 1 stores, readers 2..R add, the last one also divides by R -- the very
+        additions and the one division numpy.mean performs, in its order, so the
+        result has the same bits as batch_embedding. All readers on one device. May be called from several threads
+        at once."""
+        import torch
+        device = 'cuda:{}'.format(self._device_index())
+        stream = torch.cuda.current_stream(torch.device(device)).cuda_stream
+        row_ids = self.resolve_rows_device(words)
+        merged = torch.empty((len(words), self.dim), dtype=torch.float32, device=device)
+        if len(words):
+            self._merge_rows_device(row_ids, merged, stream)
+        return merged
+
     def bags_embedding_device(self, *args, **kwargs):
-        """Pooled lookups exist for a single Reader only (Reader.bags_embedding_device)"""
-        raise NotImplementedError('pooled lookups of a ReadersUnion are not built: pool each Reader and merge the results')
+        """A union's bag is of ENTRIES of one row id per reader, which the one-array signature of
+        Reader.bags_embedding_device has no place for: see pooled_rows_device, pooled_sentences_device and pooled_rows"""
+        raise NotImplementedError(
+            'a ReadersUnion pools entries of one row id per reader: use pooled_rows_device, pooled_sentences_device or pooled_rows')
 
     bags_embedding = sentences_embedding_device = bags_embedding_device
+
+    @property
+    def last_pooled_kernel(self):
+        """The kernel the last 'average' pooled launch of this union ran -- 'pool_trained_union<..>' for the fused kernel,
+        'pool_dense<..>' for the fallback over merged rows, both as the library names them -- or '' before any.
+        Informational, like info()['union_kernel']: with several threads in pooled_rows_device it is the kernel of whichever
+        call recorded it last."""
+        return self._last_pooled_kernel
+
+    def pooled_rows_device(self, rows, offsets, mode='mean', out=None, col_off=0, dtype=None):
+        """Pooled lookup of merged rows that never leaves the GPU: the sum or mean of each bag of the rows
+        batch_embedding_device writes, bit for bit Reader.bags_embedding_device's loop over them.
+        Parameters
+        ----------
+        rows : a sequence of R contiguous int32 / uint32 torch.Tensors of equal length n on the readers' device, one per
+            reader (resolve_rows_device): entry i is (rows[0][i], .., rows[R - 1][i]), a row a reader does not have
+            (0xFFFFFFFF or an id >= len(reader)) is +0.0 there
+        offsets, mode, out, col_off, dtype : as in Reader.bags_embedding_device; out is (bags, >= col_off + union.dim)
+        'concatenate': every reader pools into its own column block, R launches of Reader.bags_embedding_device's kernels.
+        'average': the merged row of an entry is (((v1 + v2) + ..) / R in float32. Trained readers of one dim (a multiple
+        of 4, at most 512) and lane geometry with a 16-byte aligned `out` run ONE kernel that decodes every reader's rows,
+        merges and adds them in registers: neither the readers' rows nor the merged rows are written. Every other averaged
+        union -- uniform or full storage, mixed storages, other dims, more than four readers, an unaligned `out`, option
+        union_fused = 0 on the first reader -- merges the rows into a float32 (n, dim) temporary of this call (4 n dim
+        bytes) and pools that: the same bits. last_pooled_kernel says which ran.
+        No missing='skip', no chunked reduction, no accumulate, weights or 'max'.
+        May be called from several threads at once: nothing is shared between calls but last_pooled_kernel.
+        """
+        import torch
+        from . import _memb
+        code = pool_mode(mode)
+        readers = self._readers
+        index = self._device_index()
+        if not isinstance(rows, (list, tuple)) or len(rows) != len(readers):
+            raise ValueError('rows must be a sequence of one row-id tensor per reader ({})'.format(len(readers)))
+        for ids in rows:
+            if (not isinstance(ids, torch.Tensor) or ids.device.type != 'cuda' or ids.dtype not in (torch.int32, torch.uint32)
+                    or not ids.is_contiguous()):
+                raise TypeError('rows must be contiguous int32/uint32 tensors on the GPU')
+        n = rows[0].numel()
+        if any(ids.numel() != n for ids in rows):
+            raise ValueError('the row-id tensors of a union must be of equal length')
+        device = rows[0].device
+        if (not isinstance(offsets, torch.Tensor) or offsets.device.type != 'cuda' or offsets.dtype not in (torch.int32, torch.uint32)
+                or not offsets.is_contiguous() or offsets.dim() != 1):
+            raise TypeError('offsets must be a contiguous int32/uint32 tensor of bags + 1 entries on the GPU')
+        if offsets.numel() < 1:
+            raise ValueError('offsets needs bags + 1 entries')
+        bags = offsets.numel() - 1
+        if dtype is None:
+            if out is not None and out.dtype != torch.float32:
+                raise TypeError('out is {}: pooled rows are float32 unless dtype asks for bfloat16 / float16'.format(out.dtype))
+            dtype = torch.float32
+        elif dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise TypeError('dtype must be torch.float32, torch.bfloat16 or torch.float16, not {}'.format(dtype))
+        elif out is not None and out.dtype != dtype:
+            raise TypeError('out is {} but dtype is {}'.format(out.dtype, dtype))
+        dim = self.dim
+        if out is None:
+            out = torch.empty((bags, col_off + dim), dtype=dtype, device=device)
+        if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] != bags:
+            raise TypeError('out must be a {} (bags, width) tensor with unit column stride'.format(dtype))
+        if (device.index != index or out.device != device or offsets.device != device
+                or any(ids.device != device for ids in rows)):
+            raise ValueError('rows, offsets and out must be on cuda:{} (the device these readers are staged on), got {}, {} and {}'.format(
+                index, sorted({str(ids.device) for ids in rows}), offsets.device, out.device))
+        if out.shape[1] < col_off + dim:
+            raise ValueError('out is narrower than col_off + dim')
+        if self._mode == CONCATENATE:
+            column = col_off
+            for reader, ids, width in zip(readers, rows, self._widths):
+                reader.bags_embedding_device(ids, offsets, mode=mode, out=out, col_off=column, dtype=dtype)
+                column += width
+            return out
+        if bags == 0:
+            return out
+        out_type = {torch.float32: _memb.OUT_F32, torch.bfloat16: _memb.OUT_BF16, torch.float16: _memb.OUT_F16}[dtype]
+        ld = out.stride(0) if bags > 1 else out.shape[1]
+        stream = _current_stream(torch, index)
+        if _memb.pool_union_rows_to_device(
+                [reader._impl for reader in readers], [ids.data_ptr() for ids in rows], n, offsets.data_ptr(), bags,
+                out.data_ptr(), ld, col_off, code, stream, out_type):
+            self._last_pooled_kernel = _memb.pool_union_kernel_name(readers[0]._impl)
+            return out
+        # this call's own: torch's allocator keeps it alive for the work enqueued on the current stream
+        merged = torch.empty((n, dim), dtype=torch.float32, device=device)
+        if n:
+            self._merge_rows_device(list(rows), merged, stream)
+        _memb.pool_dense_rows_to_device(
+            index, merged.data_ptr(), n, dim, dim, offsets.data_ptr(), bags, out.data_ptr(), ld, col_off, code, stream, out_type)
+        self._last_pooled_kernel = _memb.pool_dense_kernel_name(out_type)
+        return out
+
+    def pooled_sentences_device(self, sentences, mode='mean', dtype=None):
+        """One merged vector per sentence, left on the GPU: `sentences` is a sequence of word sequences; the words are
+        resolved on the device by every reader (resolve_rows_device) and each sentence's merged rows are pooled by
+        pooled_rows_device. A sentence without words is a zero vector. Returns a (len(sentences), dim) tensor of `dtype`."""
+        import torch
+        pool_mode(mode)
+        index = self._device_index()
+        words = []
+        offsets = np.zeros(len(sentences) + 1, dtype=np.int64)
+        for position, sentence in enumerate(sentences):
+            if isinstance(sentence, (str, bytes)):
+                raise TypeError('a sentence is a sequence of words, not one string')
+            words.extend(sentence)
+            offsets[position + 1] = len(words)
+        if len(words) > 0xFFFFFFFF:
+            raise ValueError('more than 0xFFFFFFFF words in one call')
+        offsets = bag_offsets(offsets, len(words))   # (host-made: checked like a caller's)
+        device = 'cuda:{}'.format(index)
+        if words:
+            rows = self.resolve_rows_device(words)
+        else:
+            rows = [torch.empty((0,), dtype=torch.int32, device=device) for _ in self._readers]
+        on_device = torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).to(device)
+        return self.pooled_rows_device(rows, on_device, mode=mode, dtype=dtype)
+
+    def pooled_rows(self, rows, offsets, mode='mean'):
+        """pooled_rows_device for host arrays: a sequence of R numpy row-id arrays of equal length and offsets in, a numpy
+        float32 (bags, dim) matrix out. offsets: bags + 1 integers, ascending, within 0 .. n -- anything else is a
+        ValueError. Readers on a GPU send the ids and offsets up and bring only bags x dim floats back. A union of
+        device='cpu' readers decodes rows_embedding in slices of POOLED_HOST_CHUNK entries, merges them in numpy float32 in
+        pooled_rows_device's order and adds them in entry order: the same bits."""
+        code = pool_mode(mode)
+        readers = self._readers
+        if not all(isinstance(reader, Reader) for reader in readers):
+            raise TypeError('pooled lookups need memb_amd.Reader instances')
+        if isinstance(rows, np.ndarray) and rows.ndim == 1 or len(rows) != len(readers):
+            raise ValueError('rows must be a sequence of one row-id array per reader ({})'.format(len(readers)))
+        rows = [np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1) for ids in rows]
+        n = rows[0].size
+        if any(ids.size != n for ids in rows):
+            raise ValueError('the row-id arrays of a union must be of equal length')
+        offsets = bag_offsets(offsets, n)
+        bags = offsets.size - 1
+        from . import _memb
+        on_host = [reader._impl.device() == _memb.HOST_DEVICE for reader in readers]
+        if not any(on_host):
+            import torch
+            device = 'cuda:{}'.format(self._device_index())
+            result = self.pooled_rows_device(
+                [torch.from_numpy(ids.view(np.int32)).to(device) for ids in rows],
+                torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).to(device), mode=mode)
+            return result.cpu().numpy()
+        if not all(on_host):
+            raise ValueError('all readers of a union must be on one device')
+        out = np.zeros((bags, self.dim), dtype=np.float32)
+        begins, ends = offsets[:-1], offsets[1:]
+        for start in range(0, n, POOLED_HOST_CHUNK):
+            stop = min(n, start + POOLED_HOST_CHUNK)
+            first = int(np.searchsorted(ends, start, side='right'))    # the first bag that ends behind `start`
+            last = int(np.searchsorted(begins, stop, side='left'))     # bags below this one begin before `stop`
+            bag = np.arange(first, last)
+            low = np.maximum(begins[first:last], start)
+            high = np.minimum(ends[first:last], stop)
+            fresh = begins[first:last] >= start                        # the bag's first entry lies in this slice
+            keep = high > low
+            bag, low, high, fresh = bag[keep], low[keep], high[keep], fresh[keep]
+            if not bag.size:
+                continue
+            pieces = [reader.rows_embedding(ids[start:stop]) for reader, ids in zip(readers, rows)]
+            if self._mode == CONCATENATE:
+                values = np.hstack(pieces)
+            else:
+                values = pieces[0]
+                for piece in pieces[1:]:
+                    values = np.add(values, piece, dtype=np.float32)
+                values = np.divide(values, np.float32(len(readers)), dtype=np.float32)
+            for step in range(int((high - low).max())):
+                active = (high - low) > step
+                addend = values[low[active] + step - start]
+                target = bag[active]
+                if step == 0:
+                    begun = fresh[active]
+                    out[target[begun]] = addend[begun]
+                    out[target[~begun]] = np.add(out[target[~begun]], addend[~begun], dtype=np.float32)
+                else:
+                    out[target] = np.add(out[target], addend, dtype=np.float32)
+        if code == _memb.POOL_MEAN:
+            counts = (ends - begins).astype(np.float32)
+            filled = counts > 0
+            out[filled] = np.divide(out[filled], counts[filled][:, None], dtype=np.float32)
+        return out
 
     def tokenizer_embedding(self, tokenizer):
         """Embedding-layer weights for a keras Tokenizer, merged over the readers"""
