@@ -570,6 +570,18 @@ py::dict contextInfo(memb::Reader& reader, uint64_t batchWords)
     return result;
 }
 
+// What every pool_*_to_device method passes on: the sequential lookup over every entry, to which the method adds its own
+memb::PooledLookup pooledLookup(
+    uintptr_t rows, size_t n, uintptr_t offsets, size_t bags, uintptr_t out, int outType, size_t ld, size_t colOff, int mode,
+    uintptr_t stream)
+{
+    memb::PooledLookup lookup{
+        reinterpret_cast<const uint32_t*>(rows), n, reinterpret_cast<const uint32_t*>(offsets), bags, reinterpret_cast<void*>(out),
+        outType, ld, colOff, mode};
+    lookup.stream = reinterpret_cast<void*>(stream);
+    return lookup;
+}
+
 }  // namespace
 
 // The caller's output matrix for the *_into calls, used in place: float32, writeable, two-dimensional,
@@ -928,9 +940,7 @@ PYBIND11_MODULE(_memb, m) {
             [](memb::Reader& reader, uintptr_t rows, size_t n, uintptr_t offsets, size_t bags, uintptr_t out, size_t ld,
                size_t colOff, int mode, uintptr_t stream, int outType)
             {
-                reader.poolRowsDevice(
-                    reinterpret_cast<const uint32_t*>(rows), n, reinterpret_cast<const uint32_t*>(offsets), bags,
-                    reinterpret_cast<void*>(out), outType, ld, colOff, mode, reinterpret_cast<void*>(stream));
+                reader.poolRowsDevice(pooledLookup(rows, n, offsets, bags, out, outType, ld, colOff, mode, stream));
             },
             py::arg("rows_ptr"),
             py::arg("n"),
@@ -947,10 +957,10 @@ PYBIND11_MODULE(_memb, m) {
             [](memb::Reader& reader, uintptr_t rows, size_t n, uintptr_t offsets, size_t bags, uintptr_t out, size_t ld,
                size_t colOff, int mode, uintptr_t stream, int outType, uintptr_t counts)
             {
-                reader.poolKnownRowsDevice(
-                    reinterpret_cast<const uint32_t*>(rows), n, reinterpret_cast<const uint32_t*>(offsets), bags,
-                    reinterpret_cast<void*>(out), outType, ld, colOff, mode, reinterpret_cast<uint32_t*>(counts),
-                    reinterpret_cast<void*>(stream));
+                memb::PooledLookup lookup = pooledLookup(rows, n, offsets, bags, out, outType, ld, colOff, mode, stream);
+                lookup.skip = true;
+                lookup.counts = reinterpret_cast<uint32_t*>(counts);
+                reader.poolRowsDevice(lookup);
             },
             py::arg("rows_ptr"),
             py::arg("n"),
@@ -974,10 +984,13 @@ PYBIND11_MODULE(_memb, m) {
                size_t colOff, int mode, uintptr_t stream, int outType, bool skipMissing, uintptr_t counts, uintptr_t workspace,
                size_t workspaceBytes)
             {
-                reader.poolRowsChunkedDevice(
-                    reinterpret_cast<const uint32_t*>(rows), n, reinterpret_cast<const uint32_t*>(offsets), bags,
-                    reinterpret_cast<void*>(out), outType, ld, colOff, mode, skipMissing, reinterpret_cast<uint32_t*>(counts),
-                    reinterpret_cast<void*>(workspace), workspaceBytes, reinterpret_cast<void*>(stream));
+                memb::PooledLookup lookup = pooledLookup(rows, n, offsets, bags, out, outType, ld, colOff, mode, stream);
+                lookup.skip = skipMissing;
+                lookup.counts = reinterpret_cast<uint32_t*>(counts);
+                lookup.chunked = true;
+                lookup.workspace = reinterpret_cast<void*>(workspace);
+                lookup.workspaceBytes = workspaceBytes;
+                reader.poolRowsDevice(lookup);
             },
             py::arg("rows_ptr"),
             py::arg("n"),

@@ -148,28 +148,25 @@ void CompressedStorage::decodeRowsDeviceTyped(
     }
 }
 
-void CompressedStorage::poolRowsDevice(
-    const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int outType, size_t ld, size_t colOff,
-    int mode, void* stream) const
+void CompressedStorage::poolRowsDevice(const PooledLookup& lookup) const
 {
     if (onHost()) {
         throw std::runtime_error("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device");
     }
-    if (memb_hip_pool_rows_device_typed(deviceContext(), rows, n, offsets, bags, out, outType, ld, colOff, mode, stream) !=
-        MEMB_HIP_OK) {
-        throwDeviceError("HIP pooled lookup failed");
+    const PooledLookup& l = lookup;
+    int code;
+    if (l.chunked) {
+        code = memb_hip_pool_rows_chunked_device_typed(
+            deviceContext(), l.rows, l.n, l.offsets, l.bags, l.out, l.outType, l.ld, l.colOff, l.mode, l.skip ? 1 : 0, l.counts,
+            l.workspace, l.workspaceBytes, l.stream);
+    } else if (l.skip) {
+        code = memb_hip_pool_known_rows_device_typed(
+            deviceContext(), l.rows, l.n, l.offsets, l.bags, l.out, l.outType, l.ld, l.colOff, l.mode, l.counts, l.stream);
+    } else {
+        code = memb_hip_pool_rows_device_typed(
+            deviceContext(), l.rows, l.n, l.offsets, l.bags, l.out, l.outType, l.ld, l.colOff, l.mode, l.stream);
     }
-}
-
-void CompressedStorage::poolKnownRowsDevice(
-    const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int outType, size_t ld, size_t colOff,
-    int mode, uint32_t* counts, void* stream) const
-{
-    if (onHost()) {
-        throw std::runtime_error("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device");
-    }
-    if (memb_hip_pool_known_rows_device_typed(
-            deviceContext(), rows, n, offsets, bags, out, outType, ld, colOff, mode, counts, stream) != MEMB_HIP_OK) {
+    if (code != MEMB_HIP_OK) {
         throwDeviceError("HIP pooled lookup failed");
     }
 }
@@ -180,20 +177,6 @@ size_t CompressedStorage::poolChunkedWorkspaceBytes(size_t n, size_t bags) const
         throw std::runtime_error("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device");
     }
     return memb_hip_pool_chunked_workspace_bytes(deviceContext(), n, bags);
-}
-
-void CompressedStorage::poolRowsChunkedDevice(
-    const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int outType, size_t ld, size_t colOff,
-    int mode, bool skipMissing, uint32_t* counts, void* workspace, size_t workspaceBytes, void* stream) const
-{
-    if (onHost()) {
-        throw std::runtime_error("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device");
-    }
-    if (memb_hip_pool_rows_chunked_device_typed(
-            deviceContext(), rows, n, offsets, bags, out, outType, ld, colOff, mode, skipMissing ? 1 : 0, counts, workspace,
-            workspaceBytes, stream) != MEMB_HIP_OK) {
-        throwDeviceError("HIP pooled lookup failed");
-    }
 }
 
 // ---------------------------------------------------------------------------

@@ -32,6 +32,33 @@ namespace memb {
 
 const size_t THREADED_DECODER_THRESHOLD = 1024;  // reference src/reader.cpp:9
 
+// A pooled device lookup (include/memb_hip_pooled.h): the sum or mean (mode: MEMB_HIP_POOL_*) of each bag
+// rows[offsets[b] .. offsets[b + 1]) goes to out[b * ld + colOff .. + dim), as elements of outType (MEMB_HIP_OUT_*; ld and
+// colOff count elements). rows, offsets, out, counts and workspace are device pointers; enqueued on `stream` (hipStream_t,
+// may be null).
+struct PooledLookup {
+    const uint32_t* rows;
+    size_t n;
+    const uint32_t* offsets;
+    size_t bags;
+    void* out;
+    int outType;
+    size_t ld;
+    size_t colOff;
+    int mode;
+    // skip: over the entries the model knows (include/memb_hip_pooled_known.h) -- an entry that is not in the model is left
+    // out of its bag and of the mean's count; counts: null, or where the bags' known entries are counted
+    bool skip = false;
+    uint32_t* counts = nullptr;
+    // chunked: under the chunked order (include/memb_hip_pooled_chunked.h) -- long bags are cut into chunks of
+    // MEMB_HIP_POOL_CHUNK entries whose sums are added in chunk order. workspace: at least poolChunkedWorkspaceBytes(n, bags)
+    // bytes that the caller keeps until the work on `stream` has ended.
+    bool chunked = false;
+    void* workspace = nullptr;
+    size_t workspaceBytes = 0;
+    void* stream = nullptr;
+};
+
 class CompressedStorage {
 public:
     virtual ~CompressedStorage();
@@ -67,22 +94,10 @@ public:
     // Same with elements of outType (include/memb_hip_narrow.h: MEMB_HIP_OUT_*); ld and colOff count elements.
     void decodeRowsDeviceTyped(
         const uint32_t* rows, size_t n, void* out, int outType, size_t ld, size_t colOff, void* stream) const;
-    // The sum or mean (mode: MEMB_HIP_POOL_*) of each bag of rows, device buffers (include/memb_hip_pooled.h): bag b =
-    // rows[offsets[b] .. offsets[b + 1]) goes to out[b * ld + colOff ..], as elements of outType (MEMB_HIP_OUT_*; ld and
-    // colOff count elements).
-    void poolRowsDevice(
-        const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int outType, size_t ld, size_t colOff,
-        int mode, void* stream) const;
-    // ... over the entries the model knows (include/memb_hip_pooled_known.h); counts: null, or bags entries on the device
-    void poolKnownRowsDevice(
-        const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int outType, size_t ld, size_t colOff,
-        int mode, uint32_t* counts, void* stream) const;
-    // Either of the two under the chunked order (include/memb_hip_pooled_chunked.h): workspace, a device buffer of at least
-    // poolChunkedWorkspaceBytes(n, bags) bytes, is the caller's for the duration of the work on `stream`.
+    // The sum or mean of each bag of rows, device buffers (PooledLookup above).
+    void poolRowsDevice(const PooledLookup& lookup) const;
+    // The bytes of PooledLookup::workspace a chunked lookup of n entries in `bags` bags needs.
     size_t poolChunkedWorkspaceBytes(size_t n, size_t bags) const;
-    void poolRowsChunkedDevice(
-        const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int outType, size_t ld, size_t colOff,
-        int mode, bool skipMissing, uint32_t* counts, void* workspace, size_t workspaceBytes, void* stream) const;
 
     // device == HOST_DEVICE: rows are decoded by extractRowHost on host threads
     static constexpr int HOST_DEVICE = -2;

@@ -22,6 +22,24 @@ struct KnownParams {
 
 constexpr uint32_t TRAINED_VEC4_MAX_DIM = 512;   // two pieces per lane
 constexpr uint32_t ROWWISE_WAVES = 4;
+constexpr uint32_t POOLED_TILES_PER_WAVE = 4;
+
+// PoolParams::bagsPerWave of the trained kernels (this unit's and pool_trained_union), on the host: a wavefront owns a run
+// of consecutive bags sized so that it decodes about POOLED_TILES_PER_WAVE tiles of wordsPerWave entries
+// (tilesPerWaveSwitch, the option tiles_per_wave: that many where it is not 0), fewer while the grid would not fill the
+// cuCount CUs with wavesPerCu wavefronts each, at most 1 << 16. A bag is never split: ONE enormous bag is walked by one
+// wavefront, correct and slow.
+inline uint32_t pooledBagsPerWave(
+    uint32_t tilesPerWaveSwitch, uint32_t wordsPerWave, uint64_t n, uint64_t bags, uint32_t cuCount, uint32_t wavesPerCu)
+{
+    const uint64_t tilesPerWave = tilesPerWaveSwitch ? tilesPerWaveSwitch : POOLED_TILES_PER_WAVE;
+    const uint64_t entriesPerBag = n / (bags ? bags : 1);
+    const uint64_t tilesOfEntries = tilesPerWave * wordsPerWave / (entriesPerBag ? entriesPerBag : 1);
+    const uint64_t fillsTheCus = bags / (uint64_t(cuCount) * wavesPerCu);
+    uint64_t owned = tilesOfEntries < fillsTheCus ? tilesOfEntries : fillsTheCus;
+    owned = owned < (1u << 16) ? owned : (1u << 16);
+    return static_cast<uint32_t>(owned ? owned : 1);
+}
 
 enum class PoolStorage { Trained, Uniform, Full };
 

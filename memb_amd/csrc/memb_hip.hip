@@ -1414,26 +1414,40 @@ int launch(memb_hip_ctx* ctx, const Lookup& lookup, hipStream_t stream)
     }
 }
 
+// The end of every sequential pooled launch: a grid of blocks of `waves` wavefronts that own bagsPerWave bags each -- which
+// the kernel reads from `pool`, its second argument.
+int launchPooledKernel(
+    const memb_pooled::PoolKernel& kernel, uint32_t waves, uint32_t bagsPerWave, uint32_t ldsBytes, memb_pooled::PoolParams* pool,
+    void** arguments, hipStream_t stream)
+{
+    pool->bagsPerWave = bagsPerWave;
+    const uint64_t perBlock = uint64_t(waves) * bagsPerWave;
+    const uint64_t blocks = (pool->bags + perBlock - 1) / perBlock;
+    if (blocks >= 0x7FFFFFFFull) {
+        return fail(MEMB_HIP_ERR_INVALID, "batches too large for one launch");
+    }
+    const hipError_t status =
+        launchKernelAddress(kernel.address, dim3(static_cast<uint32_t>(blocks)), dim3(waves * WAVE), ldsBytes, stream, arguments);
+    if (status != hipSuccess) {
+        return fail(MEMB_HIP_ERR_DEVICE, std::string(kernel.name) + " launch: " + hipGetErrorString(status));
+    }
+    return MEMB_HIP_OK;
+}
+
 // A pooled lookup (include/memb_hip_pooled.h): `lookup` describes the ENTRIES (rows, n) and the bags' rows (out, ld, colOff),
-// `pool` the bags. One kernel of memb_hip_pooled.hip, whatever the storage, the element and `known`
-// (memb_pooled::pooledKernel).
+// `pool` the bags, both checked by the caller (PooledCall::check: at least one bag, neither count beyond a launch). One kernel of
+// memb_hip_pooled.hip, whatever the storage, the element and `known` (memb_pooled::pooledKernel of hip_pooled.h).
 // Trained: planned like a decode of n rows by the one-tile kernel (planTrained, force = 0, usual index) -- pool_trained is
-// that kernel up to the symbol tile -- and a wavefront owns a run of consecutive bags sized so that it decodes about
-// POOLED_TILES_PER_WAVE tiles (option tiles_per_wave: that many), fewer while the grid would not fill the CUs. A bag is
-// never split: ONE enormous bag is walked by one wavefront, correct and slow.
+// that kernel up to the symbol tile -- and a wavefront owns a run of consecutive whole bags (memb_pooled::pooledBagsPerWave).
 // Bags' rows of a narrow outType run the bf16 / fp16 kernels on the same plan: they add fp32 centroids, so LDS is planned
 // for an fp32 codebook whatever the element, and only the choice of the piece form follows it.
+// Uniform, full: one wavefront per bag, blocks of ROWWISE_WAVES.
 // known (include/memb_hip_pooled_known.h): the pool_known_* kernels, which leave a bag's unknown entries out and take the
 // counts as a third parameter -- the same plan, the same geometry.
-constexpr uint32_t POOLED_TILES_PER_WAVE = 4;
-
 int launchPooled(
     memb_hip_ctx* ctx, const Lookup& lookup, memb_pooled::PoolParams pool, hipStream_t stream,
     const memb_pooled::KnownParams* known = nullptr)
 {
-    if (lookup.n > (size_t(1) << 37) || pool.bags >= (1ull << 37)) {
-        return fail(MEMB_HIP_ERR_INVALID, "batch too large");
-    }
     memb_pooled::PoolStorage storage;
     bool vec4 = false;
     memb_pooled::KnownParams counted = known ? *known : memb_pooled::KnownParams{};
@@ -1443,7 +1457,7 @@ int launchPooled(
     FullParams full;
     uint32_t waves = memb_pooled::ROWWISE_WAVES;
     uint32_t ldsBytes = 0;
-    pool.bagsPerWave = 1;
+    uint32_t bagsPerWave = 1;
     switch (ctx->storage) {
         case memb::wire::Storage_Trained: {
             storage = memb_pooled::PoolStorage::Trained;
@@ -1473,11 +1487,8 @@ int launchPooled(
             vec4 = pieces && ctx->dim <= memb_pooled::TRAINED_VEC4_MAX_DIM;
             waves = geometry.waves;
             ldsBytes = geometry.ldsBytes;
-            const uint64_t tilesPerWave = ctx->switches.tilesPerWave ? ctx->switches.tilesPerWave : POOLED_TILES_PER_WAVE;
-            const uint64_t entriesPerBag = std::max<uint64_t>(1, lookup.n / std::max<uint64_t>(pool.bags, 1));
-            const uint64_t fillsTheCus = std::max<uint64_t>(1, pool.bags / (uint64_t(ctx->cuCount) * ONE_TILE_WAVES_PER_CU));
-            pool.bagsPerWave = static_cast<uint32_t>(std::min<uint64_t>(
-                std::min<uint64_t>(std::max<uint64_t>(1, tilesPerWave * trained.wordsPerWave / entriesPerBag), fillsTheCus), 1u << 16));
+            bagsPerWave = memb_pooled::pooledBagsPerWave(
+                ctx->switches.tilesPerWave, trained.wordsPerWave, lookup.n, pool.bags, ctx->cuCount, ONE_TILE_WAVES_PER_CU);
             arguments[0] = &trained;
             break;
         }
@@ -1498,38 +1509,23 @@ int launchPooled(
         default:
             return fail(MEMB_HIP_ERR_INVALID, "context has no storage");
     }
-    const memb_pooled::PoolKernel chosen =
+    const memb_pooled::PoolKernel kernel =
         memb_pooled::pooledKernel(storage, lookupHasSub(ctx), ctx->fast, vec4, lookup.outType, known != nullptr);
-    const void* kernel = chosen.address;
-    const char* name = chosen.name;
-    if (!kernel) {
-        return fail(MEMB_HIP_ERR_INVALID, std::string("internal error: no ") + name + " kernel for this output");
+    if (!kernel.address) {
+        return fail(MEMB_HIP_ERR_INVALID, std::string("internal error: no ") + kernel.name + " kernel for this output");
     }
-    const uint64_t perBlock = uint64_t(waves) * pool.bagsPerWave;
-    const uint64_t blocks = (pool.bags + perBlock - 1) / perBlock;
-    if (blocks >= 0x7FFFFFFFull) {
-        return fail(MEMB_HIP_ERR_INVALID, "batches too large for one launch");
-    }
-    const hipError_t status =
-        launchKernelAddress(kernel, dim3(static_cast<uint32_t>(blocks)), dim3(waves * WAVE), ldsBytes, stream, arguments);
-    if (status != hipSuccess) {
-        return fail(MEMB_HIP_ERR_DEVICE, std::string(name) + " launch: " + hipGetErrorString(status));
-    }
-    return MEMB_HIP_OK;
+    return launchPooledKernel(kernel, waves, bagsPerWave, ldsBytes, &pool, arguments, stream);
 }
 
-// A pooled lookup of a union's AVERAGED rows (include/memb_hip_pooled_union.h): pool_trained_union of
-// memb_hip_pooled_union.hip, for the unions launchTrainedUnion takes (planUnion) whose dim fits pool_trained's register
-// form; MEMB_HIP_UNSUPPORTED with the reason otherwise, nothing launched. LDS per wavefront and the shared image are
-// decode_trained_union's, the block size the one with the most resident wavefronts (chooseUnionWaves), the bags of a
-// wavefront launchPooled's.
+// A pooled lookup of a union's AVERAGED rows (include/memb_hip_pooled_union.h), checked by the caller like launchPooled's:
+// pool_trained_union of memb_hip_pooled_union.hip (memb_pooled::pooledUnionKernel of hip_pooled_union.h), for the unions
+// launchTrainedUnion takes (planUnion) whose dim fits pool_trained's register form; MEMB_HIP_UNSUPPORTED with the reason
+// otherwise, nothing launched. LDS per wavefront and the shared image are decode_trained_union's, the block size the one
+// with the most resident wavefronts (chooseUnionWaves), the bags of a wavefront launchPooled's.
 int launchPooledUnion(
     memb_hip_ctx* const* ctxs, const uint32_t* const* rows, size_t count, size_t n, memb_pooled::PoolParams pool, void* out,
     int outType, size_t ld, size_t colOff, hipStream_t stream)
 {
-    if (n > (size_t(1) << 37) || pool.bags >= (1ull << 37)) {
-        return fail(MEMB_HIP_ERR_INVALID, "batch too large");
-    }
     size_t colOffs[UNION_MAX_MODELS];
     for (size_t m = 0; m < UNION_MAX_MODELS; ++m) {
         colOffs[m] = colOff;
@@ -1554,54 +1550,33 @@ int launchPooledUnion(
     }
     uint32_t waves = 0;
     uint32_t ldsBytes = 0;
-    hipError_t status = chooseUnionWaves(first, kernel.address, params.sharedDwords, params.perWaveDwords, &waves, &ldsBytes);
+    const hipError_t status = chooseUnionWaves(first, kernel.address, params.sharedDwords, params.perWaveDwords, &waves, &ldsBytes);
     if (status != hipSuccess) {
         return fail(MEMB_HIP_ERR_DEVICE, std::string("hipFuncGetAttributes: ") + hipGetErrorString(status));
     }
     if (!waves) {
         return fail(MEMB_HIP_UNSUPPORTED, "pooled union kernel: tables and bitstream slots of the models do not fit into LDS together");
     }
-    const uint64_t tilesPerWave = first->switches.tilesPerWave ? first->switches.tilesPerWave : POOLED_TILES_PER_WAVE;
-    const uint64_t entriesPerBag = std::max<uint64_t>(1, n / std::max<uint64_t>(pool.bags, 1));
-    const uint64_t fillsTheCus = std::max<uint64_t>(1, pool.bags / (uint64_t(first->cuCount) * ONE_TILE_WAVES_PER_CU));
-    pool.bagsPerWave = static_cast<uint32_t>(std::min<uint64_t>(
-        std::min<uint64_t>(std::max<uint64_t>(1, tilesPerWave * plan.wordsPerWave / entriesPerBag), fillsTheCus), 1u << 16));
-    const uint64_t perBlock = uint64_t(waves) * pool.bagsPerWave;
-    const uint64_t blocks = (pool.bags + perBlock - 1) / perBlock;
-    if (blocks >= 0x7FFFFFFFull) {
-        return fail(MEMB_HIP_ERR_INVALID, "batches too large for one launch");
-    }
+    const uint32_t bagsPerWave = memb_pooled::pooledBagsPerWave(
+        first->switches.tilesPerWave, plan.wordsPerWave, n, pool.bags, first->cuCount, ONE_TILE_WAVES_PER_CU);
     void* arguments[2] = {&params, &pool};
-    status = launchKernelAddress(kernel.address, dim3(static_cast<uint32_t>(blocks)), dim3(waves * WAVE), ldsBytes, stream, arguments);
-    if (status != hipSuccess) {
-        return fail(MEMB_HIP_ERR_DEVICE, std::string(kernel.name) + " launch: " + hipGetErrorString(status));
+    const int code = launchPooledKernel(kernel, waves, bagsPerWave, ldsBytes, &pool, arguments, stream);
+    if (code == MEMB_HIP_OK) {
+        first->pooledUnionKernel = kernel.name;
     }
-    first->pooledUnionKernel = kernel.name;
-    return MEMB_HIP_OK;
+    return code;
 }
 
-// memb_hip_pool_dense_rows_device: pool_dense of memb_hip_pooled_union.hip, one wavefront per bag.
+// memb_hip_pool_dense_rows_device, checked by the caller like launchPooled's: pool_dense of memb_hip_pooled_union.hip
+// (memb_pooled::pooledDenseKernel), one wavefront per bag.
 int launchPooledDense(memb_pooled::DenseParams params, memb_pooled::PoolParams pool, int outType, hipStream_t stream)
 {
-    if (params.n > (size_t(1) << 37) || pool.bags >= (1ull << 37)) {
-        return fail(MEMB_HIP_ERR_INVALID, "batch too large");
-    }
     const memb_pooled::PoolKernel kernel = memb_pooled::pooledDenseKernel(outType);
     if (!kernel.address) {
         return fail(MEMB_HIP_ERR_INVALID, std::string("internal error: no ") + kernel.name + " kernel for this output");
     }
-    pool.bagsPerWave = 1;
-    const uint64_t blocks = (pool.bags + memb_pooled::ROWWISE_WAVES - 1) / memb_pooled::ROWWISE_WAVES;
-    if (blocks >= 0x7FFFFFFFull) {
-        return fail(MEMB_HIP_ERR_INVALID, "batches too large for one launch");
-    }
     void* arguments[2] = {&params, &pool};
-    const hipError_t status = launchKernelAddress(
-        kernel.address, dim3(static_cast<uint32_t>(blocks)), dim3(memb_pooled::ROWWISE_WAVES * WAVE), 0, stream, arguments);
-    if (status != hipSuccess) {
-        return fail(MEMB_HIP_ERR_DEVICE, std::string(kernel.name) + " launch: " + hipGetErrorString(status));
-    }
-    return MEMB_HIP_OK;
+    return launchPooledKernel(kernel, memb_pooled::ROWWISE_WAVES, 1, 0, &pool, arguments, stream);
 }
 
 template <typename T>
@@ -2578,39 +2553,83 @@ bool knownOutType(int outType)
     return outType == MEMB_HIP_OUT_F32 || outType == MEMB_HIP_OUT_BF16 || outType == MEMB_HIP_OUT_F16;
 }
 
+// The arguments every pooled entry point takes, and the check they share. The entry point's own go in beside them:
+// sourceMissing, its test of what the entries come from (a context and rows, a union's contexts and their rows, dense
+// values), and ownRefusal, what it refuses beyond the shared checks (null: nothing).
+struct PooledCall {
+    bool sourceMissing;
+    size_t n;
+    const uint32_t* offsets;
+    size_t bags;
+    void* out;
+    int outType;
+    size_t ld;
+    size_t colOff;
+    int mode;
+    const char* ownRefusal = nullptr;   // chunked: counts without skip_missing; dense: its dim, ld_values and device
+    bool dense = false;                 // ownRefusal comes before the alignment, which is that of `values` too
+    const void* values = nullptr;
+
+    struct Checked {
+        int code;
+        bool launch;                    // false with MEMB_HIP_OK: bags == 0, nothing to do
+        memb_pooled::PoolParams pool;   // offsets, bags, mean
+    };
+    // ONE order: out_type, mode, null arguments, [dense's own,] alignment, ld, [chunked's own,] no bags, a batch beyond one
+    // launch. dim() is called once the null check has passed, never before: what it reads need not exist until then.
+    template <typename Dim>
+    Checked check(Dim dim) const
+    {
+        const auto refuse = [](const std::string& message) { return Checked{fail(MEMB_HIP_ERR_INVALID, message), false, {}}; };
+        if (!knownOutType(outType)) {
+            return refuse("unknown out_type " + std::to_string(outType));
+        }
+        if (mode != MEMB_HIP_POOL_SUM && mode != MEMB_HIP_POOL_MEAN) {
+            return refuse("unknown pooling mode " + std::to_string(mode));
+        }
+        if (sourceMissing || (bags && (!offsets || !out))) {
+            return refuse("null argument");
+        }
+        if (dense && ownRefusal) {
+            return refuse(ownRefusal);
+        }
+        const size_t elementBytes = outType == MEMB_HIP_OUT_F32 ? 4 : 2;
+        if (reinterpret_cast<uintptr_t>(out) % elementBytes != 0 || reinterpret_cast<uintptr_t>(values) % 4 != 0) {
+            return refuse(
+                dense ? "values and out must be aligned to their elements"
+                      : "out must be aligned to its element (" + std::to_string(elementBytes) + " bytes)");
+        }
+        if (colOff > ld || ld - colOff < dim()) {
+            return refuse("ld must be at least col_off + dim");
+        }
+        if (ownRefusal) {
+            return refuse(ownRefusal);
+        }
+        if (bags == 0) {
+            return Checked{MEMB_HIP_OK, false, {}};
+        }
+        if (n > (size_t(1) << 37) || bags >= (1ull << 37)) {
+            return refuse("batch too large");
+        }
+        return Checked{MEMB_HIP_OK, true, {offsets, bags, 0, mode == MEMB_HIP_POOL_MEAN ? 1u : 0u}};
+    }
+};
+
 // known: memb_hip_pool_known_rows_device_typed -- the same checks, the kernels that skip unknown entries, counts or null
 int pool_rows_device_checked(
     memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int outType, size_t ld,
     size_t col_off, int mode, void* stream, bool known = false, uint32_t* counts = nullptr)
 {
-    if (!knownOutType(outType)) {
-        return fail(MEMB_HIP_ERR_INVALID, "unknown out_type " + std::to_string(outType));
-    }
-    if (mode != MEMB_HIP_POOL_SUM && mode != MEMB_HIP_POOL_MEAN) {
-        return fail(MEMB_HIP_ERR_INVALID, "unknown pooling mode " + std::to_string(mode));
-    }
-    if (!ctx || (n && !rows) || (bags && (!offsets || !out))) {
-        return fail(MEMB_HIP_ERR_INVALID, "null argument");
-    }
-    const size_t elementBytes = outType == MEMB_HIP_OUT_F32 ? 4 : 2;
-    if (reinterpret_cast<uintptr_t>(out) % elementBytes != 0) {
-        return fail(MEMB_HIP_ERR_INVALID, "out must be aligned to its element (" + std::to_string(elementBytes) + " bytes)");
-    }
-    if (col_off > ld || ld - col_off < ctx->dim) {
-        return fail(MEMB_HIP_ERR_INVALID, "ld must be at least col_off + dim");
-    }
-    if (bags == 0) {
-        return MEMB_HIP_OK;
+    const PooledCall::Checked checked = PooledCall{!ctx || (n && !rows), n, offsets, bags, out, outType, ld, col_off, mode}.check(
+        [&] { return size_t(ctx->dim); });
+    if (!checked.launch) {
+        return checked.code;
     }
     DeviceScope deviceScope(ctx->device);
     HIP_TRY(deviceScope.status());
-    memb_pooled::PoolParams pool{};
-    pool.offsets = offsets;
-    pool.bags = bags;
-    pool.mean = mode == MEMB_HIP_POOL_MEAN ? 1u : 0u;
     const memb_pooled::KnownParams counted{counts};
     return launchPooled(
-        ctx, Lookup{rows, n, out, outType, ld, col_off}, pool, static_cast<hipStream_t>(stream), known ? &counted : nullptr);
+        ctx, Lookup{rows, n, out, outType, ld, col_off}, checked.pool, static_cast<hipStream_t>(stream), known ? &counted : nullptr);
 }
 
 // memb_hip_pool_rows_union_device (include/memb_hip_pooled_union.h)
@@ -2618,37 +2637,18 @@ int pool_rows_union_device_checked(
     memb_hip_ctx* const* ctxs, const uint32_t* const* rows, size_t count, size_t n, const uint32_t* offsets, size_t bags, void* out,
     int outType, size_t ld, size_t col_off, int mode, void* stream)
 {
-    if (!knownOutType(outType)) {
-        return fail(MEMB_HIP_ERR_INVALID, "unknown out_type " + std::to_string(outType));
+    bool sourceMissing = !ctxs || !rows || count == 0;
+    for (size_t m = 0; !sourceMissing && m < count; ++m) {
+        sourceMissing = !ctxs[m] || (n && !rows[m]);
     }
-    if (mode != MEMB_HIP_POOL_SUM && mode != MEMB_HIP_POOL_MEAN) {
-        return fail(MEMB_HIP_ERR_INVALID, "unknown pooling mode " + std::to_string(mode));
-    }
-    if (!ctxs || !rows || count == 0 || (bags && (!offsets || !out))) {
-        return fail(MEMB_HIP_ERR_INVALID, "null argument");
-    }
-    for (size_t m = 0; m < count; ++m) {
-        if (!ctxs[m] || (n && !rows[m])) {
-            return fail(MEMB_HIP_ERR_INVALID, "null argument");
-        }
-    }
-    const size_t elementBytes = outType == MEMB_HIP_OUT_F32 ? 4 : 2;
-    if (reinterpret_cast<uintptr_t>(out) % elementBytes != 0) {
-        return fail(MEMB_HIP_ERR_INVALID, "out must be aligned to its element (" + std::to_string(elementBytes) + " bytes)");
-    }
-    if (col_off > ld || ld - col_off < ctxs[0]->dim) {
-        return fail(MEMB_HIP_ERR_INVALID, "ld must be at least col_off + dim");
-    }
-    if (bags == 0) {
-        return MEMB_HIP_OK;
+    const PooledCall::Checked checked = PooledCall{sourceMissing, n, offsets, bags, out, outType, ld, col_off, mode}.check(
+        [&] { return size_t(ctxs[0]->dim); });
+    if (!checked.launch) {
+        return checked.code;
     }
     DeviceScope deviceScope(ctxs[0]->device);
     HIP_TRY(deviceScope.status());
-    memb_pooled::PoolParams pool{};
-    pool.offsets = offsets;
-    pool.bags = bags;
-    pool.mean = mode == MEMB_HIP_POOL_MEAN ? 1u : 0u;
-    return launchPooledUnion(ctxs, rows, count, n, pool, out, outType, ld, col_off, static_cast<hipStream_t>(stream));
+    return launchPooledUnion(ctxs, rows, count, n, checked.pool, out, outType, ld, col_off, static_cast<hipStream_t>(stream));
 }
 
 // memb_hip_pool_dense_rows_device (include/memb_hip_pooled_union.h)
@@ -2656,27 +2656,15 @@ int pool_dense_rows_device_checked(
     int device, const float* values, size_t n, size_t dim, size_t ldValues, const uint32_t* offsets, size_t bags, void* out,
     int outType, size_t ld, size_t col_off, int mode, void* stream)
 {
-    if (!knownOutType(outType)) {
-        return fail(MEMB_HIP_ERR_INVALID, "unknown out_type " + std::to_string(outType));
-    }
-    if (mode != MEMB_HIP_POOL_SUM && mode != MEMB_HIP_POOL_MEAN) {
-        return fail(MEMB_HIP_ERR_INVALID, "unknown pooling mode " + std::to_string(mode));
-    }
-    if ((n && !values) || (bags && (!offsets || !out))) {
-        return fail(MEMB_HIP_ERR_INVALID, "null argument");
-    }
+    PooledCall call{n && !values, n, offsets, bags, out, outType, ld, col_off, mode};
     if (dim == 0 || dim > 0xFFFFFFFFull || ldValues < dim || device < 0) {
-        return fail(MEMB_HIP_ERR_INVALID, "dim must be 1 .. 2^32 - 1, ld_values at least dim and device a HIP device");
+        call.ownRefusal = "dim must be 1 .. 2^32 - 1, ld_values at least dim and device a HIP device";
     }
-    const size_t elementBytes = outType == MEMB_HIP_OUT_F32 ? 4 : 2;
-    if (reinterpret_cast<uintptr_t>(out) % elementBytes != 0 || reinterpret_cast<uintptr_t>(values) % 4 != 0) {
-        return fail(MEMB_HIP_ERR_INVALID, "values and out must be aligned to their elements");
-    }
-    if (col_off > ld || ld - col_off < dim) {
-        return fail(MEMB_HIP_ERR_INVALID, "ld must be at least col_off + dim");
-    }
-    if (bags == 0) {
-        return MEMB_HIP_OK;
+    call.dense = true;
+    call.values = values;
+    const PooledCall::Checked checked = call.check([&] { return dim; });
+    if (!checked.launch) {
+        return checked.code;
     }
     DeviceScope deviceScope(device);
     HIP_TRY(deviceScope.status());
@@ -2688,11 +2676,7 @@ int pool_dense_rows_device_checked(
     params.colOff = col_off;
     params.ldValues = ldValues;
     params.dim = static_cast<uint32_t>(dim);
-    memb_pooled::PoolParams pool{};
-    pool.offsets = offsets;
-    pool.bags = bags;
-    pool.mean = mode == MEMB_HIP_POOL_MEAN ? 1u : 0u;
-    return launchPooledDense(params, pool, outType, static_cast<hipStream_t>(stream));
+    return launchPooledDense(params, checked.pool, outType, static_cast<hipStream_t>(stream));
 }
 
 // memb_hip_pool_rows_chunked_device_typed (include/memb_hip_pooled_chunked.h): the chunk plan, the partial sums of the
@@ -2702,30 +2686,13 @@ int pool_rows_chunked_checked(
     memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* out, int outType, size_t ld,
     size_t col_off, int mode, bool skip, uint32_t* counts, void* workspace, size_t workspaceBytes, void* stream)
 {
-    if (!knownOutType(outType)) {
-        return fail(MEMB_HIP_ERR_INVALID, "unknown out_type " + std::to_string(outType));
-    }
-    if (mode != MEMB_HIP_POOL_SUM && mode != MEMB_HIP_POOL_MEAN) {
-        return fail(MEMB_HIP_ERR_INVALID, "unknown pooling mode " + std::to_string(mode));
-    }
-    if (!ctx || (n && !rows) || (bags && (!offsets || !out))) {
-        return fail(MEMB_HIP_ERR_INVALID, "null argument");
-    }
-    const size_t elementBytes = outType == MEMB_HIP_OUT_F32 ? 4 : 2;
-    if (reinterpret_cast<uintptr_t>(out) % elementBytes != 0) {
-        return fail(MEMB_HIP_ERR_INVALID, "out must be aligned to its element (" + std::to_string(elementBytes) + " bytes)");
-    }
-    if (col_off > ld || ld - col_off < ctx->dim) {
-        return fail(MEMB_HIP_ERR_INVALID, "ld must be at least col_off + dim");
-    }
+    PooledCall call{!ctx || (n && !rows), n, offsets, bags, out, outType, ld, col_off, mode};
     if (counts && !skip) {
-        return fail(MEMB_HIP_ERR_INVALID, "counts need skip_missing: they are of the entries the model knows");
+        call.ownRefusal = "counts need skip_missing: they are of the entries the model knows";
     }
-    if (bags == 0) {
-        return MEMB_HIP_OK;
-    }
-    if (n > (size_t(1) << 37) || bags >= (1ull << 37)) {
-        return fail(MEMB_HIP_ERR_INVALID, "batch too large");
+    const PooledCall::Checked checked = call.check([&] { return size_t(ctx->dim); });
+    if (!checked.launch) {
+        return checked.code;
     }
     const memb_pooled::ChunkWorkspace layout = memb_pooled::chunkWorkspace(n, bags, ctx->dim);
     if (layout.maxChunks >= 0xFFFFFFFFull) {
@@ -2808,7 +2775,7 @@ int pool_rows_chunked_checked(
     sums.ld = ld;
     sums.colOff = col_off;
     sums.dim = ctx->dim;
-    sums.mean = mode == MEMB_HIP_POOL_MEAN ? 1u : 0u;
+    sums.mean = checked.pool.mean;
     const uint64_t waves = uint64_t(bags) * ((ctx->dim + WAVE - 1) / WAVE);
     const uint64_t blocks = (waves + memb_pooled::PLAN_THREADS / WAVE - 1) / (memb_pooled::PLAN_THREADS / WAVE);
     if (blocks >= 0x7FFFFFFFull) {

@@ -456,31 +456,14 @@ void Reader::rowsToDeviceBufferTyped(
     compressedStorage_->decodeRowsDeviceTyped(rows, n, buffer, outType, ld, colOff, stream);
 }
 
-void Reader::poolRowsDevice(
-    const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* buffer, int outType, size_t ld, size_t colOff,
-    int mode, void* stream) const
+void Reader::poolRowsDevice(const PooledLookup& lookup) const
 {
-    compressedStorage_->poolRowsDevice(rows, n, offsets, bags, buffer, outType, ld, colOff, mode, stream);
-}
-
-void Reader::poolKnownRowsDevice(
-    const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* buffer, int outType, size_t ld, size_t colOff,
-    int mode, uint32_t* counts, void* stream) const
-{
-    compressedStorage_->poolKnownRowsDevice(rows, n, offsets, bags, buffer, outType, ld, colOff, mode, counts, stream);
+    compressedStorage_->poolRowsDevice(lookup);
 }
 
 size_t Reader::poolChunkedWorkspaceBytes(size_t n, size_t bags) const
 {
     return compressedStorage_->poolChunkedWorkspaceBytes(n, bags);
-}
-
-void Reader::poolRowsChunkedDevice(
-    const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* buffer, int outType, size_t ld, size_t colOff,
-    int mode, bool skipMissing, uint32_t* counts, void* workspace, size_t workspaceBytes, void* stream) const
-{
-    compressedStorage_->poolRowsChunkedDevice(
-        rows, n, offsets, bags, buffer, outType, ld, colOff, mode, skipMissing, counts, workspace, workspaceBytes, stream);
 }
 
 std::vector<float> Reader::wordEmbedding(const std::string& word) const

@@ -114,24 +114,9 @@ public:
     // Device rows of bf16 / fp16 / fp32 (include/memb_hip_narrow.h); ld and colOff count elements of outType.
     void rowsToDeviceBufferTyped(
         const uint32_t* rows, size_t n, void* buffer, int outType, size_t ld, size_t colOff, void* stream) const;
-    // Pooled device lookup (include/memb_hip_pooled.h): the sum or mean (mode: MEMB_HIP_POOL_*) of each bag
-    // rows[offsets[b] .. offsets[b + 1]) goes to buffer[b * ld + colOff .. + dim), as elements of outType (MEMB_HIP_OUT_*;
-    // ld and colOff count elements); all three are device pointers.
-    void poolRowsDevice(
-        const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* buffer, int outType, size_t ld,
-        size_t colOff, int mode, void* stream) const;
-    // The same over the entries the model knows (include/memb_hip_pooled_known.h): an entry that is not in the model is
-    // left out of its bag and of the mean's count; counts: null, or where the bags' known entries are counted (device).
-    void poolKnownRowsDevice(
-        const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* buffer, int outType, size_t ld,
-        size_t colOff, int mode, uint32_t* counts, void* stream) const;
-    // Either of the two under the chunked order (include/memb_hip_pooled_chunked.h): long bags are cut into chunks of
-    // MEMB_HIP_POOL_CHUNK entries whose sums are added in chunk order. workspace: a device buffer of at least
-    // poolChunkedWorkspaceBytes(n, bags) bytes that the caller keeps until the work on `stream` has ended.
+    // Pooled device lookup: the sum or mean of each bag of rows (compression_strategy.h: PooledLookup).
+    void poolRowsDevice(const PooledLookup& lookup) const;
     size_t poolChunkedWorkspaceBytes(size_t n, size_t bags) const;
-    void poolRowsChunkedDevice(
-        const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, void* buffer, int outType, size_t ld,
-        size_t colOff, int mode, bool skipMissing, uint32_t* counts, void* workspace, size_t workspaceBytes, void* stream) const;
 
     // Several device-buffer lookups in one kernel launch (include/memb_hip.h: memb_hip_decode_batches_device).
     void batchesToDeviceBuffers(const memb_hip_batch* batches, size_t count, void* stream) const;

@@ -173,6 +173,110 @@ def bag_offsets(offsets, n):
     return array
 
 
+def pooled_output(torch, offsets, out, dtype, col_off, dim, device, check_devices):
+    """What Reader.bags_embedding_device and ReadersUnion.pooled_rows_device check alike once their rows are in order: the
+    offsets, the dtype and the out of a pooled device lookup of rows on `device` into columns [col_off, col_off + dim).
+    check_devices(out) raises the caller's own ValueError unless rows, offsets and out are where its kernel runs. Returns
+    (bags, out, out_type, ld): out made where it was None, out_type the _memb.OUT_* of its dtype, ld its leading dimension
+    in elements."""
+    if (not isinstance(offsets, torch.Tensor) or offsets.device.type != 'cuda' or offsets.dtype not in (torch.int32, torch.uint32)
+            or not offsets.is_contiguous() or offsets.dim() != 1):
+        raise TypeError('offsets must be a contiguous int32/uint32 tensor of bags + 1 entries on the GPU')
+    if offsets.numel() < 1:
+        raise ValueError('offsets needs bags + 1 entries')
+    bags = offsets.numel() - 1
+    if dtype is None:
+        if out is not None and out.dtype != torch.float32:
+            raise TypeError('out is {}: pooled rows are float32 unless dtype asks for bfloat16 / float16'.format(out.dtype))
+        dtype = torch.float32
+    elif dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise TypeError('dtype must be torch.float32, torch.bfloat16 or torch.float16, not {}'.format(dtype))
+    elif out is not None and out.dtype != dtype:
+        raise TypeError('out is {} but dtype is {}'.format(out.dtype, dtype))
+    if out is None:
+        out = torch.empty((bags, col_off + dim), dtype=dtype, device=device)
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] != bags:
+        raise TypeError('out must be a {} (bags, width) tensor with unit column stride'.format(dtype))
+    check_devices(out)
+    if out.shape[1] < col_off + dim:
+        raise ValueError('out is narrower than col_off + dim')
+    out_type = {torch.float32: _memb.OUT_F32, torch.bfloat16: _memb.OUT_BF16, torch.float16: _memb.OUT_F16}[dtype]
+    ld = out.stride(0) if bags > 1 else out.shape[1]
+    return bags, out, out_type, ld
+
+
+def flatten_sentences(sentences):
+    """(words, offsets) of a sequence of word sequences: the sentences' words side by side and, as numpy.int64, where each
+    sentence begins among them (len(sentences) + 1 entries)"""
+    words = []
+    offsets = np.zeros(len(sentences) + 1, dtype=np.int64)
+    for position, sentence in enumerate(sentences):
+        if isinstance(sentence, (str, bytes)):
+            raise TypeError('a sentence is a sequence of words, not one string')
+        words.extend(sentence)
+        offsets[position + 1] = len(words)
+    if len(words) > 0xFFFFFFFF:
+        raise ValueError('more than 0xFFFFFFFF words in one call')
+    return words, bag_offsets(offsets, len(words))   # (host-made: checked like a caller's)
+
+
+def pool_slices_host(offsets, n, dim, slice_entries, mean, skip, slice_values):
+    """The pooled lookup of include/memb_hip_pooled.h in numpy, for readers that decode on the host: the float32 sum or
+    `mean` of each bag of n entries (offsets: bag_offsets), added in entry order, over slices of slice_entries entries so
+    that no more than a slice of rows is ever decoded. slice_values(start, stop) is a generator that yields the float32
+    (stop - start, dim) rows of the entries [start, stop). With `skip` (missing='skip': an unknown entry is left out of its
+    bag and of the mean's count) it first yields the slice's boolean mask of known entries, then the rows of those entries
+    alone; it is not asked for rows that no bag would use. Returns (out, known_counts): the (bags, dim) result and, with
+    `skip`, the known entries of each bag as numpy.int64 (zeros without)."""
+    bags = offsets.size - 1
+    out = np.zeros((bags, dim), dtype=np.float32)
+    begins, ends = offsets[:-1], offsets[1:]
+    known_counts = np.zeros(bags, dtype=np.int64)   # skip: the bags' known entries in the slices so far
+    for start in range(0, n, slice_entries):
+        stop = min(n, start + slice_entries)
+        first = int(np.searchsorted(ends, start, side='right'))    # the first bag that ends behind `start`
+        last = int(np.searchsorted(begins, stop, side='left'))     # bags below this one begin before `stop`
+        bag = np.arange(first, last)
+        low = np.maximum(begins[first:last], start)
+        high = np.minimum(ends[first:last], stop)
+        fresh = begins[first:last] >= start                        # the bag's first entry lies in this slice
+        keep = high > low
+        bag, low, high, fresh = bag[keep], low[keep], high[keep], fresh[keep]
+        if not bag.size:
+            continue
+        produced = slice_values(start, stop)
+        if skip:
+            # the slice's known entries side by side: a bag's range among them, and whether its sum starts here; only
+            # they are decoded, and a slice without one is not decoded at all
+            known = next(produced)
+            if not known.any():
+                continue
+            before = np.concatenate(([0], np.cumsum(known)))
+            low, high = before[low - start] + start, before[high - start] + start
+            fresh = known_counts[bag] == 0
+            known_counts[bag] += high - low
+            keep = high > low
+            bag, low, high, fresh = bag[keep], low[keep], high[keep], fresh[keep]
+            if not bag.size:
+                continue
+        values = next(produced)
+        for step in range(int((high - low).max())):
+            active = (high - low) > step
+            addend = values[low[active] + step - start]
+            target = bag[active]
+            if step == 0:
+                begun = fresh[active]
+                out[target[begun]] = addend[begun]
+                out[target[~begun]] = out[target[~begun]] + addend[~begun]
+            else:
+                out[target] = out[target] + addend
+    if mean:
+        counts = (known_counts if skip else ends - begins).astype(np.float32)
+        filled = counts > 0
+        out[filled] = out[filled] / counts[filled][:, None]
+    return out, known_counts
+
+
 def tokenizer_word_list(tokenizer):
     """The words of a keras Tokenizer placed at their indices, '' where an index
     has no word (index 0 never has one). With `num_words` set only indices below
@@ -398,31 +502,13 @@ class Reader(BaseReader):
         device = rows.device
         if device.type != 'cuda' or rows.dtype not in (torch.int32, torch.uint32) or not rows.is_contiguous():
             raise TypeError('rows must be a contiguous int32/uint32 tensor on the GPU')
-        if (not isinstance(offsets, torch.Tensor) or offsets.device.type != 'cuda' or offsets.dtype not in (torch.int32, torch.uint32)
-                or not offsets.is_contiguous() or offsets.dim() != 1):
-            raise TypeError('offsets must be a contiguous int32/uint32 tensor of bags + 1 entries on the GPU')
-        if offsets.numel() < 1:
-            raise ValueError('offsets needs bags + 1 entries')
-        bags = offsets.numel() - 1
-        if dtype is None:
-            if out is not None and out.dtype != torch.float32:
-                raise TypeError('out is {}: pooled rows are float32 unless dtype asks for bfloat16 / float16'.format(out.dtype))
-            dtype = torch.float32
-        elif dtype not in (torch.float32, torch.bfloat16, torch.float16):
-            raise TypeError('dtype must be torch.float32, torch.bfloat16 or torch.float16, not {}'.format(dtype))
-        elif out is not None and out.dtype != dtype:
-            raise TypeError('out is {} but dtype is {}'.format(out.dtype, dtype))
-        if out is None:
-            out = torch.empty((bags, col_off + self.dim), dtype=dtype, device=device)
-        if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] != bags:
-            raise TypeError('out must be a {} (bags, width) tensor with unit column stride'.format(dtype))
-        if device.index != index or out.device != device or offsets.device != device:
-            raise ValueError('rows, offsets and out must be on cuda:{} (the device this reader is staged on), got {}, {} and {}'.format(
-                self.device, device, offsets.device, out.device))
-        if out.shape[1] < col_off + self.dim:
-            raise ValueError('out is narrower than col_off + dim')
-        out_type = {torch.float32: _memb.OUT_F32, torch.bfloat16: _memb.OUT_BF16, torch.float16: _memb.OUT_F16}[dtype]
-        ld = out.stride(0) if bags > 1 else out.shape[1]
+
+        def check_devices(out):
+            if device.index != index or out.device != device or offsets.device != device:
+                raise ValueError('rows, offsets and out must be on cuda:{} (the device this reader is staged on), got {}, {} and {}'.format(
+                    self.device, device, offsets.device, out.device))
+
+        bags, out, out_type, ld = pooled_output(torch, offsets, out, dtype, col_off, self.dim, device, check_devices)
         if chunked:
             counts = torch.empty((bags,), dtype=torch.int32, device=device) if return_counts else None
             workspace_bytes = self._impl.pool_chunked_workspace_bytes(rows.numel(), bags)
@@ -461,16 +547,7 @@ class Reader(BaseReader):
         index = self._impl.device()
         if index == _memb.HOST_DEVICE:
             raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
-        words = []
-        offsets = np.zeros(len(sentences) + 1, dtype=np.int64)
-        for position, sentence in enumerate(sentences):
-            if isinstance(sentence, (str, bytes)):
-                raise TypeError('a sentence is a sequence of words, not one string')
-            words.extend(sentence)
-            offsets[position + 1] = len(words)
-        if len(words) > 0xFFFFFFFF:
-            raise ValueError('more than 0xFFFFFFFF words in one call')
-        offsets = bag_offsets(offsets, len(words))   # (host-made: checked like a caller's)
+        words, offsets = flatten_sentences(sentences)
         device = 'cuda:{}'.format(index)
         rows = self.resolve_rows_device(words) if words else torch.empty((0,), dtype=torch.int32, device=device)
         on_device = torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).to(device)
@@ -490,7 +567,6 @@ class Reader(BaseReader):
         chunked = pool_reduction(reduction)
         rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
         offsets = bag_offsets(offsets, rows.size)
-        bags = offsets.size - 1
         if self._impl.device() != _memb.HOST_DEVICE:
             import torch
             device = 'cuda:{}'.format(self._impl.device())
@@ -503,52 +579,17 @@ class Reader(BaseReader):
             return result.cpu().numpy()
         if chunked:
             return self._bags_embedding_chunked(rows, offsets, code, skip, return_counts)
-        out = np.zeros((bags, self.dim), dtype=np.float32)
-        begins, ends = offsets[:-1], offsets[1:]
-        known_counts = np.zeros(bags, dtype=np.int64)   # missing='skip': the bags' known entries in the chunks so far
-        for start in range(0, rows.size, BAGS_HOST_CHUNK):
-            stop = min(rows.size, start + BAGS_HOST_CHUNK)
-            first = int(np.searchsorted(ends, start, side='right'))    # the first bag that ends behind `start`
-            last = int(np.searchsorted(begins, stop, side='left'))     # bags below this one begin before `stop`
-            bag = np.arange(first, last)
-            low = np.maximum(begins[first:last], start)
-            high = np.minimum(ends[first:last], stop)
-            fresh = begins[first:last] >= start                        # the bag's first entry lies in this chunk
-            keep = high > low
-            bag, low, high, fresh = bag[keep], low[keep], high[keep], fresh[keep]
-            if not bag.size:
-                continue
+
+        def slice_values(start, stop):
             if skip:
-                # the chunk's known entries side by side: a bag's range among them, and whether its sum starts here; only
-                # they are decoded, and a chunk without one is not decoded at all
                 known = rows[start:stop] < len(self)
-                if not known.any():
-                    continue
-                before = np.concatenate(([0], np.cumsum(known)))
-                low, high = before[low - start] + start, before[high - start] + start
-                fresh = known_counts[bag] == 0
-                known_counts[bag] += high - low
-                keep = high > low
-                bag, low, high, fresh = bag[keep], low[keep], high[keep], fresh[keep]
-                if not bag.size:
-                    continue
-                values = self.rows_embedding(rows[start:stop][known])
+                yield known
+                yield self.rows_embedding(rows[start:stop][known])
             else:
-                values = self.rows_embedding(rows[start:stop])
-            for step in range(int((high - low).max())):
-                active = (high - low) > step
-                addend = values[low[active] + step - start]
-                target = bag[active]
-                if step == 0:
-                    begun = fresh[active]
-                    out[target[begun]] = addend[begun]
-                    out[target[~begun]] = out[target[~begun]] + addend[~begun]
-                else:
-                    out[target] = out[target] + addend
-        if code == _memb.POOL_MEAN:
-            counts = (known_counts if skip else ends - begins).astype(np.float32)
-            filled = counts > 0
-            out[filled] = out[filled] / counts[filled][:, None]
+                yield self.rows_embedding(rows[start:stop])
+
+        out, known_counts = pool_slices_host(
+            offsets, rows.size, self.dim, BAGS_HOST_CHUNK, code == _memb.POOL_MEAN, skip, slice_values)
         if return_counts:
             return out, known_counts.astype(np.uint32)
         return out

@@ -11,7 +11,8 @@ merged rows -- are `pooled_rows_device`, `pooled_sentences_device` and `pooled_r
 """
 import numpy as np
 
-from .reader import BaseReader, Reader, WordBatches, _current_stream, bag_offsets, pool_mode, tokenizer_word_list
+from .reader import (BaseReader, Reader, WordBatches, _current_stream, bag_offsets, flatten_sentences, pool_mode, pool_slices_host,
+                     pooled_output, tokenizer_word_list)
 
 CONCATENATE = 'concatenate'
 AVERAGE = 'average'
@@ -195,31 +196,15 @@ class ReadersUnion(BaseReader):
         if any(ids.numel() != n for ids in rows):
             raise ValueError('the row-id tensors of a union must be of equal length')
         device = rows[0].device
-        if (not isinstance(offsets, torch.Tensor) or offsets.device.type != 'cuda' or offsets.dtype not in (torch.int32, torch.uint32)
-                or not offsets.is_contiguous() or offsets.dim() != 1):
-            raise TypeError('offsets must be a contiguous int32/uint32 tensor of bags + 1 entries on the GPU')
-        if offsets.numel() < 1:
-            raise ValueError('offsets needs bags + 1 entries')
-        bags = offsets.numel() - 1
-        if dtype is None:
-            if out is not None and out.dtype != torch.float32:
-                raise TypeError('out is {}: pooled rows are float32 unless dtype asks for bfloat16 / float16'.format(out.dtype))
-            dtype = torch.float32
-        elif dtype not in (torch.float32, torch.bfloat16, torch.float16):
-            raise TypeError('dtype must be torch.float32, torch.bfloat16 or torch.float16, not {}'.format(dtype))
-        elif out is not None and out.dtype != dtype:
-            raise TypeError('out is {} but dtype is {}'.format(out.dtype, dtype))
+
+        def check_devices(out):
+            if (device.index != index or out.device != device or offsets.device != device
+                    or any(ids.device != device for ids in rows)):
+                raise ValueError('rows, offsets and out must be on cuda:{} (the device these readers are staged on), got {}, {} and {}'.format(
+                    index, sorted({str(ids.device) for ids in rows}), offsets.device, out.device))
+
         dim = self.dim
-        if out is None:
-            out = torch.empty((bags, col_off + dim), dtype=dtype, device=device)
-        if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] != bags:
-            raise TypeError('out must be a {} (bags, width) tensor with unit column stride'.format(dtype))
-        if (device.index != index or out.device != device or offsets.device != device
-                or any(ids.device != device for ids in rows)):
-            raise ValueError('rows, offsets and out must be on cuda:{} (the device these readers are staged on), got {}, {} and {}'.format(
-                index, sorted({str(ids.device) for ids in rows}), offsets.device, out.device))
-        if out.shape[1] < col_off + dim:
-            raise ValueError('out is narrower than col_off + dim')
+        bags, out, out_type, ld = pooled_output(torch, offsets, out, dtype, col_off, dim, device, check_devices)
         if self._mode == CONCATENATE:
             column = col_off
             for reader, ids, width in zip(readers, rows, self._widths):
@@ -228,8 +213,6 @@ class ReadersUnion(BaseReader):
             return out
         if bags == 0:
             return out
-        out_type = {torch.float32: _memb.OUT_F32, torch.bfloat16: _memb.OUT_BF16, torch.float16: _memb.OUT_F16}[dtype]
-        ld = out.stride(0) if bags > 1 else out.shape[1]
         stream = _current_stream(torch, index)
         if _memb.pool_union_rows_to_device(
                 [reader._impl for reader in readers], [ids.data_ptr() for ids in rows], n, offsets.data_ptr(), bags,
@@ -252,16 +235,7 @@ class ReadersUnion(BaseReader):
         import torch
         pool_mode(mode)
         index = self._device_index()
-        words = []
-        offsets = np.zeros(len(sentences) + 1, dtype=np.int64)
-        for position, sentence in enumerate(sentences):
-            if isinstance(sentence, (str, bytes)):
-                raise TypeError('a sentence is a sequence of words, not one string')
-            words.extend(sentence)
-            offsets[position + 1] = len(words)
-        if len(words) > 0xFFFFFFFF:
-            raise ValueError('more than 0xFFFFFFFF words in one call')
-        offsets = bag_offsets(offsets, len(words))   # (host-made: checked like a caller's)
+        words, offsets = flatten_sentences(sentences)
         device = 'cuda:{}'.format(index)
         if words:
             rows = self.resolve_rows_device(words)
@@ -287,7 +261,6 @@ class ReadersUnion(BaseReader):
         if any(ids.size != n for ids in rows):
             raise ValueError('the row-id arrays of a union must be of equal length')
         offsets = bag_offsets(offsets, n)
-        bags = offsets.size - 1
         from . import _memb
         on_host = [reader._impl.device() == _memb.HOST_DEVICE for reader in readers]
         if not any(on_host):
@@ -299,20 +272,8 @@ class ReadersUnion(BaseReader):
             return result.cpu().numpy()
         if not all(on_host):
             raise ValueError('all readers of a union must be on one device')
-        out = np.zeros((bags, self.dim), dtype=np.float32)
-        begins, ends = offsets[:-1], offsets[1:]
-        for start in range(0, n, POOLED_HOST_CHUNK):
-            stop = min(n, start + POOLED_HOST_CHUNK)
-            first = int(np.searchsorted(ends, start, side='right'))    # the first bag that ends behind `start`
-            last = int(np.searchsorted(begins, stop, side='left'))     # bags below this one begin before `stop`
-            bag = np.arange(first, last)
-            low = np.maximum(begins[first:last], start)
-            high = np.minimum(ends[first:last], stop)
-            fresh = begins[first:last] >= start                        # the bag's first entry lies in this slice
-            keep = high > low
-            bag, low, high, fresh = bag[keep], low[keep], high[keep], fresh[keep]
-            if not bag.size:
-                continue
+
+        def slice_values(start, stop):
             pieces = [reader.rows_embedding(ids[start:stop]) for reader, ids in zip(readers, rows)]
             if self._mode == CONCATENATE:
                 values = np.hstack(pieces)
@@ -321,21 +282,9 @@ class ReadersUnion(BaseReader):
                 for piece in pieces[1:]:
                     values = np.add(values, piece, dtype=np.float32)
                 values = np.divide(values, np.float32(len(readers)), dtype=np.float32)
-            for step in range(int((high - low).max())):
-                active = (high - low) > step
-                addend = values[low[active] + step - start]
-                target = bag[active]
-                if step == 0:
-                    begun = fresh[active]
-                    out[target[begun]] = addend[begun]
-                    out[target[~begun]] = np.add(out[target[~begun]], addend[~begun], dtype=np.float32)
-                else:
-                    out[target] = np.add(out[target], addend, dtype=np.float32)
-        if code == _memb.POOL_MEAN:
-            counts = (ends - begins).astype(np.float32)
-            filled = counts > 0
-            out[filled] = np.divide(out[filled], counts[filled][:, None], dtype=np.float32)
-        return out
+            yield values
+
+        return pool_slices_host(offsets, n, self.dim, POOLED_HOST_CHUNK, code == _memb.POOL_MEAN, False, slice_values)[0]
 
     def tokenizer_embedding(self, tokenizer):
         """Embedding-layer weights for a keras Tokenizer, merged over the readers"""
