@@ -1,8 +1,12 @@
-"""The chunked order of include/memb_hip_pooled_chunked.h restated in numpy, for tests/test_pooled_chunked_host.py and
-tests/test_gpu_pooled_chunked.py. Every function takes the chunk length C from the caller, who reads memb_amd.POOL_CHUNK.
+"""The pooling contracts restated in numpy, for every tests/test_*pooled*.py: the sequential order of
+include/memb_hip_pooled.h / memb_hip_pooled_known.h, the chunked order of include/memb_hip_pooled_chunked.h (every function
+of it takes the chunk length C from the caller, who reads memb_amd.POOL_CHUNK), the merge of a ReadersUnion's rows
+(include/memb_hip_pooled_union.h), and the id and batch builders those tests share. Pure numpy: no torch, no GPU.
 
-Offsets are read as the kernels read them: uint32, clamped to n, a backwards range empty."""
+Offsets are read as the kernels read them: uint32, clamped to n, a backwards range empty -- so bags may overlap."""
 import numpy as np
+
+from conftest import bits_equal
 
 UNKNOWN = 0xFFFFFFFF
 
@@ -10,6 +14,103 @@ UNKNOWN = 0xFFFFFFFF
 def offsets_of(lengths, first=0):
     return (first + np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64))])).astype(np.int64)
 
+
+def clamped(offsets, n):
+    return np.minimum(np.asarray(offsets).astype(np.int64) & 0xFFFFFFFF, n)
+
+
+# ---- the sequential order ----
+
+def compacted(rows, offsets, n_rows):
+    """The batch without its unknown entries (row id >= n_rows): (rows, offsets, positions of the kept entries in `rows`).
+    Bags may overlap: each is gathered."""
+    rows = np.asarray(rows, dtype=np.uint32)
+    bounds = clamped(offsets, len(rows))
+    kept = []
+    lengths = []
+    for begin, end in zip(bounds[:-1], bounds[1:]):
+        positions = np.arange(begin, max(begin, end))
+        positions = positions[rows[positions] < n_rows]
+        kept.append(positions)
+        lengths.append(len(positions))
+    positions = np.concatenate(kept).astype(np.int64) if kept else np.zeros(0, dtype=np.int64)
+    return rows[positions], offsets_of(lengths), positions
+
+
+def sequential_by_the_contract(values, rows, offsets, n_rows, mode, skip):
+    """THE loop of include/memb_hip_pooled.h and, with skip, of memb_hip_pooled_known.h. values: the (n, dim) float32 rows of
+    the entries (zeros for an unknown one). Per bag, over its entries in entry order -- with skip over K, its KNOWN entries
+    (rows[i] < n_rows) only, an unknown one adding nothing, not even +0.0 --: acc = v_first, then acc = acc + v_i, one
+    float32 addition each; 'mean': one float32 division by float32(count) at the end; +0.0 for a bag without an entry
+    (with skip: without a known one). Returns (vectors, counts): counts the bags' known entries with skip, their entries
+    without. `rows` and `n_rows` are read with skip only.
+
+    The loop runs for all bags side by side: step j adds entry j of every bag that has one."""
+    n, dim = values.shape
+    if skip:
+        _, dense, positions = compacted(rows, offsets, n_rows)
+        begin, length = dense[:-1], dense[1:] - dense[:-1]
+    else:
+        bounds = clamped(offsets, n)
+        begin, length = bounds[:-1], np.maximum(bounds[1:] - bounds[:-1], 0)
+    out = np.zeros((len(begin), dim), dtype=np.float32)
+    for step in range(int(length.max()) if len(length) else 0):
+        active = np.nonzero(length > step)[0]
+        entries = begin[active] + step
+        addend = values[positions[entries] if skip else entries]
+        out[active] = addend if step == 0 else np.add(out[active], addend, dtype=np.float32)
+    if mode == 'mean':
+        filled = length > 0
+        out[filled] = np.divide(out[filled], length[filled].astype(np.float32)[:, None], dtype=np.float32)
+    return out, length.astype(np.uint32)
+
+
+def pooled_by_the_contract(values, offsets, mode):
+    """The plain case: every entry counts (a missing row is its +0.0 row), vectors only."""
+    return sequential_by_the_contract(values, None, offsets, None, mode, False)[0]
+
+
+def ids_with_misses(count, n_rows, seed):
+    rng = np.random.default_rng(seed)
+    rows = rng.integers(0, n_rows, size=count, dtype=np.int64)
+    if count:
+        rows[::7] = 0xFFFFFFFF
+        rows[3::11] = n_rows + 5
+        rows[0] = n_rows
+        rows[-1] = 0xFFFFFFFF
+    return rows.astype(np.uint32)
+
+
+def ids_with_unknowns(count, n_rows, seed, share=0.3):
+    rng = np.random.default_rng(seed)
+    rows = rng.integers(0, n_rows, size=count, dtype=np.int64)
+    unknown = rng.random(count) < share
+    rows[unknown] = rng.choice([UNKNOWN, n_rows, n_rows + 5, 0xFFFFFFFE], size=int(unknown.sum()))
+    return rows.astype(np.uint32)
+
+
+# ---- a ReadersUnion's rows ----
+
+def merged_rows(mode, pieces):
+    """The union's rows by the explicit order: (((v1 + v2) + v3) ..) / R, or the readers' rows side by side"""
+    if mode == 'concatenate':
+        return np.hstack(pieces)
+    total = pieces[0]
+    for piece in pieces[1:]:
+        total = np.add(total, piece, dtype=np.float32)
+    return np.divide(total, np.float32(len(pieces)), dtype=np.float32)
+
+
+def union_ids(count, readers, seed, n_rows):
+    """Row ids drawn independently per reader -- an entry is missing in one reader, in another, in all or in none -- and a
+    stretch of entries that no reader has"""
+    rows = [ids_with_misses(count, n_rows, seed + 100 * position) for position in range(readers)]
+    for ids in rows:
+        ids[count // 2:count // 2 + 9] = 0xFFFFFFFF
+    return rows
+
+
+# ---- the chunked order ----
 
 def contract_lengths(chunk):
     return [0, 1, chunk - 1, chunk, chunk + 1, 2 * chunk, 2 * chunk + 1, 0, 5 * chunk + 3, 3, 40 * chunk + 5, 1]
@@ -46,10 +147,6 @@ def inner_batches(chunk, n_rows, seed):
         rows[-1] = 1   # (known entries behind the last bag: they must not be counted)
         batches.append((name, rows, offsets))
     return batches
-
-
-def clamped(offsets, n):
-    return np.minimum(np.asarray(offsets).astype(np.int64) & 0xFFFFFFFF, n)
 
 
 def derived_offsets(offsets, n, chunk):
@@ -100,11 +197,6 @@ def chunked_by_the_contract(values, rows, offsets, n_rows, mode, skip, chunk):
                 partial.append(in_order(values[positions]))   # a chunk without a known entry contributes nothing
         out[bag] = finish(in_order(partial), counts[bag], mode, dim)
     return out, counts
-
-
-def sequential_by_the_contract(values, rows, offsets, n_rows, mode, skip):
-    """The order of include/memb_hip_pooled.h / memb_hip_pooled_known.h: a bag's entries one after the other."""
-    return chunked_by_the_contract(values, rows, offsets, n_rows, mode, skip, 1 << 40)
 
 
 def from_partial_sums(partial, chunk_counts, first, mode, counts, dim):
@@ -265,3 +357,69 @@ def reversed_batch(rows, offsets):
     another plan, other chunk counts per slot of the workspace."""
     lengths = (np.asarray(offsets[1:]) - np.asarray(offsets[:-1]))[::-1]
     return np.ascontiguousarray(np.asarray(rows, dtype=np.uint32)[::-1]), offsets_of(lengths, first=int(offsets[0]))
+
+
+# ---- signed zeros under the chunked order: a model, its batches and what they must show ----
+
+def signed_zero_model(native, directory):
+    """A `full` model whose row 0 is all -0.0 and whose rows 1 and 2 are subnormal with mixed signs, -0.0 in their first
+    columns."""
+    rng = np.random.default_rng(41)
+    count, dim = 40, 300
+    vectors = rng.integers(-70000, 70000, size=(count, dim)).astype(np.float32) * np.float32(1.4e-45)
+    vectors[0] = -0.0
+    vectors[1, :50] = -0.0
+    vectors[2, :30] = -0.0
+    assert (np.abs(vectors) < 1.1754944e-38).all() and (vectors[1] > 0).any() and (vectors[1] < 0).any()
+    builder = native.Builder(dim, 'full', 8)
+    builder.add_words(['s{:04d}'.format(i) for i in range(count)], vectors)
+    path = str(directory / 'signed_zero.bin')
+    builder.save(path)
+    return path, count
+
+
+def skip_cases(chunk, count):
+    """(rows, offsets): a bag of 3 C entries -- first chunk: one known row of -0.0 among unknown entries, middle chunk all
+    0xFFFFFFFF, last chunk rows 0, 1, 2 and then row 0 again and again -- a bag of 2 C + 3 unknown entries, and a bag of
+    3 C + 1 subnormal rows."""
+    first = np.full(chunk, UNKNOWN, dtype=np.uint32)
+    first[chunk // 2] = 0
+    middle = np.full(chunk, UNKNOWN, dtype=np.uint32)
+    last = np.zeros(chunk, dtype=np.uint32)
+    last[:3] = [0, 1, 2]
+    unknown = np.full(2 * chunk + 3, UNKNOWN, dtype=np.uint32)
+    unknown[5] = count   # (an id that is not in the model is unknown too)
+    subnormal = (np.arange(3 * chunk + 1) % (count - 1) + 1).astype(np.uint32)
+    rows = np.concatenate([first, middle, last, unknown, subnormal])
+    return rows, offsets_of([3 * chunk, len(unknown), len(subnormal)])
+
+
+def check_skip_cases(result, counts, values, rows, offsets, count, chunk):
+    """result, counts: mode='sum', missing='skip' of skip_cases; values: the entries' rows."""
+    want, want_counts = chunked_by_the_contract(values, rows, offsets, count, 'sum', True, chunk)
+    assert bits_equal(result, want) and np.array_equal(counts, want_counts)
+    assert counts[0] == 1 + chunk and counts[1] == 0 and counts[2] == 3 * chunk + 1
+    last = in_order(values[2 * chunk:3 * chunk])   # the last chunk's sum: -0.0 where rows 0, 1 and 2 all are
+    negative_zero = (last == 0) & np.signbit(last)
+    assert negative_zero[:30].all() and not negative_zero.all()
+    # -0.0 (the first chunk) + nothing (the middle one) + last = last, -0.0 included; a +0.0 from the middle chunk or from
+    # the first chunk's unknown entries would have turned those columns into +0.0
+    assert bits_equal(result[0], last)
+    assert not result[1].any() and not np.signbit(result[1]).any()   # no known entry: +0.0
+    assert (result[2] != 0).any() and (np.abs(result[2]) < 1.1754944e-38).all()   # subnormal partial sums are kept
+
+
+def signed_zero_rows(rows):
+    """The known entries of `rows` as rows 0, 1 and 2 of signed_zero_model, whose first 30 columns are -0.0."""
+    return np.where(rows == UNKNOWN, rows, rows % np.uint32(3)).astype(np.uint32)
+
+
+def check_negative_zeros_survive(signed, holes, offsets, chunk):
+    """(a reader of signed_zero_model, a batch of signed_zero_rows) by the contract, the first 30 columns of every bag with a
+    known entry are -0.0, whichever chunks are unknown: one +0.0 added for an unknown chunk or entry would make them +0.0,
+    and the reference would notice. Returns the contract's (sums, counts) with missing='skip'."""
+    want, counts = chunked_by_the_contract(signed.rows_embedding(holes), holes, offsets, len(signed), 'sum', True, chunk)
+    filled = counts > 0
+    assert not want[:, :30].any() and np.signbit(want[filled, :30]).all() and not np.signbit(want[~filled]).any()
+    assert not filled.any() or (want[filled, 50:] != 0).any()
+    return want, counts

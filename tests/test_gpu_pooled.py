@@ -4,12 +4,12 @@ The oracle everywhere: the reader's own fp32 rows from rows_embedding_device -- 
 to the CPU checker -- copied to the host and pooled by the explicit float32 loop of the contract
 (include/memb_hip_pooled.h): acc = v_begin, acc = acc + v_i in entry order, one division for the mean, +0.0 for an empty
 bag. Compared with bits_equal: the tolerance is zero."""
-import threading
-
 import numpy as np
 import pytest
 
 from conftest import bits_equal
+from pooled_device import for_every_key_form, into_a_frame, run_on_two_streams, sweep_options, to_device
+from pooled_reference import ids_with_misses, offsets_of, pooled_by_the_contract
 
 pytestmark = pytest.mark.gpu
 
@@ -18,63 +18,18 @@ STORAGES = [('trained', 2), ('trained', 4), ('trained', 6), ('trained', 8), ('un
 N_ROWS = 20000
 
 
-def pooled_by_the_contract(values, offsets, mode):
-    """values: (n, dim) float32 rows of the entries; offsets: any integers, read as the kernel reads them (clamped to n).
-    The contract's loop, run for all bags side by side: step k adds entry begin + k of every bag that has one."""
-    n, dim = values.shape
-    clamped = np.minimum(np.asarray(offsets).astype(np.int64) & 0xFFFFFFFF, n)
-    begin, end = clamped[:-1], clamped[1:]
-    length = np.maximum(end - begin, 0)
-    out = np.zeros((len(begin), dim), dtype=np.float32)
-    for step in range(int(length.max()) if len(length) else 0):
-        active = np.nonzero(length > step)[0]
-        addend = values[begin[active] + step]
-        out[active] = addend if step == 0 else np.add(out[active], addend, dtype=np.float32)
-    if mode == 'mean':
-        filled = length > 0
-        out[filled] = np.divide(out[filled], length[filled].astype(np.float32)[:, None], dtype=np.float32)
-    return out
-
-
-def offsets_of(lengths):
-    return np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64))]).astype(np.int64)
-
-
-def ids_with_misses(count, n_rows, seed):
-    rng = np.random.default_rng(seed)
-    rows = rng.integers(0, n_rows, size=count, dtype=np.int64)
-    if count:
-        rows[::7] = 0xFFFFFFFF
-        rows[3::11] = n_rows + 5
-        rows[0] = n_rows
-        rows[-1] = 0xFFFFFFFF
-    return rows.astype(np.uint32)
-
-
-def to_device(array, kind=np.int32):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(array).astype(np.uint32).view(kind)).cuda()
-
-
 def check_pooled(reader, rows, offsets, context, modes=('sum', 'mean'), col_off=0, spare=0):
     """Both modes against the contract over the reader's own rows; the columns around the bags keep their sentinel.
     Returns the 'sum' result."""
-    import torch
     dim = reader.dim
     device_rows, device_offsets = to_device(rows), to_device(offsets)
     values = reader.rows_embedding_device(device_rows).cpu().numpy() if len(rows) else np.zeros((0, dim), dtype=np.float32)
     bags = len(offsets) - 1
     results = {}
     for mode in modes:
-        width = col_off + dim + spare
-        out = torch.full((bags, width), float(SENTINEL), dtype=torch.float32, device='cuda')
-        returned = reader.bags_embedding_device(device_rows, device_offsets, mode=mode, out=out, col_off=col_off)
-        torch.cuda.synchronize()
-        assert returned.data_ptr() == out.data_ptr()
-        host = out.cpu().numpy()
-        assert (host[:, :col_off] == SENTINEL).all() and (host[:, col_off + dim:] == SENTINEL).all(), context
+        got = into_a_frame(lambda out: reader.bags_embedding_device(device_rows, device_offsets, mode=mode, out=out, col_off=col_off),
+                           bags, dim, context, col_off, spare, sentinel=SENTINEL).numpy()
         want = pooled_by_the_contract(values, offsets, mode)
-        got = host[:, col_off:col_off + dim]
         if not bits_equal(got, want):
             bad = np.nonzero((got.view(np.uint32) != want.view(np.uint32)).any(axis=1))[0]
             raise AssertionError('{} {}: {} of {} bags differ, first {}'.format(context, mode, len(bad), bags, bad[:8]))
@@ -154,19 +109,6 @@ def test_very_wide_rowwise_rows(native, make_model, storage):
     check_pooled(native.Reader(path), ids_with_misses(sum(lengths), 40, 5), offsets_of(lengths), (storage, 5001), col_off=1, spare=2)
 
 
-def set_environment(monkeypatch, **values):
-    for key in ('MEMB_HIP_LANES', 'MEMB_HIP_WAVES', 'MEMB_HIP_ROOT_BITS', 'MEMB_HIP_NO_FAST', 'MEMB_HIP_ROW_RECORDS', 'MEMB_HIP_ROW_META'):
-        monkeypatch.delenv(key, raising=False)
-    for key, value in values.items():
-        monkeypatch.setenv(key, str(value))
-
-
-def kernel_form(reader):
-    name = reader.info(1)['kernel']
-    has_sub, _, fast = [argument.strip() for argument in name[len('decode_trained<'):-1].split(',')]
-    return has_sub == 'true', fast == 'true'
-
-
 def test_key_forms_tables_and_row_layouts(native, make_model, monkeypatch):
     """Nibble keys, byte keys with a one-level table (MEMB_HIP_NO_FAST), two-level tables through
     max_direct_decode_bits=1; row records, compact streams with rowMeta records and with the two index arrays; lanes per
@@ -174,19 +116,12 @@ def test_key_forms_tables_and_row_layouts(native, make_model, monkeypatch):
     lengths = np.random.default_rng(1).geometric(1 / 12.0, size=600)
     rows = ids_with_misses(int(lengths.sum()), N_ROWS, 9)
     offsets = offsets_of(lengths)
-    forms = set()
-    for bits, distribution in ((4, 'normal'), (6, 'student'), (8, 'student')):
-        path, _ = make_model(N_ROWS, 300, 'trained', bits, distribution=distribution)
-        cases = [({}, 0), ({}, 1), ({'MEMB_HIP_ROW_RECORDS': '0'}, 0), ({'MEMB_HIP_ROW_META': '0'}, 1),
-                 ({'MEMB_HIP_NO_FAST': 1}, 0), ({'MEMB_HIP_LANES': 1, 'MEMB_HIP_WAVES': 1}, 0), ({'MEMB_HIP_LANES': 3, 'MEMB_HIP_WAVES': 2}, 0),
-                 ({'MEMB_HIP_LANES': 5, 'MEMB_HIP_WAVES': 8}, 1), ({'MEMB_HIP_LANES': 25}, 0), ({'MEMB_HIP_LANES': 64}, 0)]
-        for environment, max_direct_bits in cases:
-            set_environment(monkeypatch, **environment)
-            reader = native.Reader(path, max_direct_decode_bits=max_direct_bits)
-            forms.add(kernel_form(reader))
-            check_pooled(reader, rows, offsets, (bits, environment, max_direct_bits))
-            check_pooled(reader, rows, offsets, (bits, environment, max_direct_bits, 'col_off 1'), modes=('mean',), col_off=1, spare=1)
-    assert forms == {(False, True), (False, False), (True, False)}, forms
+
+    def check(reader, context):
+        check_pooled(reader, rows, offsets, context)
+        check_pooled(reader, rows, offsets, context + ('col_off 1',), modes=('mean',), col_off=1, spare=1)
+
+    for_every_key_form(native, make_model, monkeypatch, N_ROWS, check)
 
 
 # ---- 3. the mean is the sum and one division ----
@@ -264,21 +199,16 @@ def test_results_do_not_depend_on_options(native, make_model, bits):
     lengths = np.random.default_rng(bits).geometric(1 / 16.0, size=3000)
     device_rows, device_offsets = to_device(ids_with_misses(int(lengths.sum()), N_ROWS, 3)), to_device(offsets_of(lengths))
     reference = {mode: reader.bags_embedding_device(device_rows, device_offsets, mode=mode).cpu().numpy() for mode in ('sum', 'mean')}
-    try:
-        for waves in (1, 2, 4, 7, 8):
-            for tiles in (1, 2, 5, 64):
-                reader.set_option('waves_per_block', waves)
-                reader.set_option('tiles_per_wave', tiles)
-                for mode in ('sum', 'mean'):
-                    got = reader.bags_embedding_device(device_rows, device_offsets, mode=mode).cpu().numpy()
-                    assert bits_equal(got, reference[mode]), (waves, tiles, mode)
-    finally:
-        reader.set_option('waves_per_block', 0)
-        reader.set_option('tiles_per_wave', 0)
+
+    def run(waves, tiles):
+        for mode in ('sum', 'mean'):
+            got = reader.bags_embedding_device(device_rows, device_offsets, mode=mode).cpu().numpy()
+            assert bits_equal(got, reference[mode]), (waves, tiles, mode)
+
+    sweep_options(reader, run)
 
 
 def test_two_threads_on_two_streams(native, make_model):
-    import torch
     path, _ = make_model(N_ROWS, 300, 'trained', 4)
     reader = native.Reader(path)
     jobs = []
@@ -288,30 +218,13 @@ def test_two_threads_on_two_streams(native, make_model):
         offsets = offsets_of(lengths)
         values = reader.rows_embedding_device(to_device(rows)).cpu().numpy()
         jobs.append((to_device(rows), to_device(offsets), {mode: pooled_by_the_contract(values, offsets, mode) for mode in ('sum', 'mean')}))
-    torch.cuda.synchronize()
-    barrier = threading.Barrier(2)
-    failures = []
 
-    def run(thread):
-        try:
-            stream = torch.cuda.Stream()
-            barrier.wait()
-            with torch.cuda.stream(stream):
-                for repeat in range(20):
-                    mode = ('sum', 'mean')[repeat % 2]
-                    got = reader.bags_embedding_device(jobs[thread][0], jobs[thread][1], mode=mode)
-                    stream.synchronize()
-                    if not bits_equal(got.cpu().numpy(), jobs[thread][2][mode]):
-                        failures.append((thread, repeat, mode))
-        except Exception as error:   # (a thread's exception is a failure of the test, not a line on stderr)
-            failures.append((thread, repr(error)))
+    def call(thread, repeat):
+        mode = ('sum', 'mean')[repeat % 2]
+        got = reader.bags_embedding_device(jobs[thread][0], jobs[thread][1], mode=mode)
+        return (got,), (jobs[thread][2][mode],), mode
 
-    threads = [threading.Thread(target=run, args=(thread,)) for thread in range(2)]
-    for thread in threads:
-        thread.start()
-    for thread in threads:
-        thread.join()
-    assert not failures, failures
+    run_on_two_streams(jobs, call)
 
 
 # ---- 7. the Python surface ----

@@ -2,82 +2,25 @@
 bags_embedding_device / sentences_embedding_device / bags_embedding with reduction='chunked'.
 
 Two references, both compared bit for bit (the tolerance is zero):
-  R1  the contract's explicit float32 loop over reader.rows_embedding(rows) (tests/pooled_chunked_reference.py);
+  R1  the contract's explicit float32 loop over reader.rows_embedding(rows) (tests/pooled_reference.py);
   R2  the SEQUENTIAL call (reduction left out) with mode='sum' over the derived offsets, one bag per chunk, then the
       in-order numpy loop over those partial sums.
 A bf16 / fp16 result is R1 .to(dtype) on the CPU. Lengths around a chunk are named by C = memb_amd.POOL_CHUNK."""
 import ctypes
-import threading
 
 import numpy as np
 import pytest
 
 from conftest import bits_equal
-from pooled_chunked_reference import (LONGEST, UNKNOWN, chunked_by_the_contract, contract_batch, derived_offsets, from_partial_sums,
-                                      inner_batches, offsets_of, sequential_by_the_contract)
-from test_pooled_chunked_host import check_skip_cases, signed_zero_model, skip_cases
+from pooled_device import check_chunked, narrow_bits, pooled, run_on_two_streams, to_device
+from pooled_reference import (LONGEST, UNKNOWN, check_skip_cases, chunked_by_the_contract, contract_batch, inner_batches, offsets_of,
+                              sequential_by_the_contract, signed_zero_model, skip_cases)
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -1234.5
 N_ROWS = 3000
 SEED = 11   # of contract_batch: tests/test_pooled_chunked_host.py shows on the host that the two orders differ for it
-
-
-def to_device(array):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(array).astype(np.uint32).view(np.int32)).cuda()
-
-
-def narrow_bits(tensor):
-    import torch
-    if tensor.dtype == torch.float32:
-        return tensor.contiguous().numpy().view(np.uint32)
-    return tensor.contiguous().view(torch.int16).numpy().view(np.uint16)
-
-
-def pooled(reader, rows, offsets, mode, skip, col_off=0, spare=0, dtype=None, reduction='chunked'):
-    """(vectors on the host, counts or None): the call into a canaried `out`, whose other columns keep their sentinel"""
-    import torch
-    kind = dtype or torch.float32
-    bags = len(offsets) - 1
-    out = torch.full((bags, col_off + reader.dim + spare), SENTINEL, dtype=kind, device='cuda')
-    result = reader.bags_embedding_device(
-        to_device(rows), to_device(offsets), mode=mode, out=out, col_off=col_off, dtype=dtype, missing='skip' if skip else 'zero',
-        return_counts=skip, reduction=reduction)
-    torch.cuda.synchronize()
-    returned, counts = result if skip else (result, None)
-    assert returned.data_ptr() == out.data_ptr()
-    host = out.cpu()
-    sentinel = torch.tensor(SENTINEL, dtype=kind)
-    assert (host[:, :col_off] == sentinel).all() and (host[:, col_off + reader.dim:] == sentinel).all()
-    if skip:
-        assert counts.dtype == torch.int32 and tuple(counts.shape) == (bags,) and counts.is_cuda
-        counts = counts.cpu().numpy().view(np.uint32)
-    return host[:, col_off:col_off + reader.dim], counts
-
-
-def check_chunked(reader, rows, offsets, chunk, context, modes=('sum', 'mean'), col_off=0, spare=0, second=True):
-    """Both modes, missing='zero' and 'skip', against R1 and (second) R2."""
-    n_rows, dim = len(reader), reader.dim
-    rows = np.asarray(rows, dtype=np.uint32)
-    values = reader.rows_embedding(rows) if len(rows) else np.zeros((0, dim), dtype=np.float32)
-    derived, first = derived_offsets(offsets, len(rows), chunk)
-    for skip in (False, True):
-        if second:   # today's sums of the chunks as bags
-            partial, chunk_counts = pooled(reader, rows, derived, 'sum', skip, reduction='sequential')
-            partial = partial.numpy()
-            if not skip:
-                chunk_counts = derived[1:] - derived[:-1]
-        for mode in modes:
-            got, counts = pooled(reader, rows, offsets, mode, skip, col_off, spare)
-            want, want_counts = chunked_by_the_contract(values, rows, offsets, n_rows, mode, skip, chunk)
-            assert bits_equal(got.numpy(), want), (context, mode, skip, 'R1')
-            if skip:
-                assert np.array_equal(counts, want_counts), (context, mode, 'counts')
-            if second:
-                again = from_partial_sums(partial, chunk_counts, first, mode, want_counts, dim)
-                assert bits_equal(got.numpy(), again), (context, mode, skip, 'R2')
 
 
 # ---- 1. the contract, both references ----
@@ -213,7 +156,6 @@ def test_results_do_not_depend_on_geometry(native, make_model, monkeypatch):
 # ---- 7. two threads, two streams, two workspaces ----
 
 def test_two_threads_on_two_streams(native, make_model):
-    import torch
     chunk = native.POOL_CHUNK
     path, _ = make_model(N_ROWS, 300, 'trained', 4)
     reader = native.Reader(path)
@@ -225,32 +167,14 @@ def test_two_threads_on_two_streams(native, make_model):
         values = reader.rows_embedding(rows)
         jobs.append((to_device(rows), to_device(offsets),
                      {mode: chunked_by_the_contract(values, rows, offsets, N_ROWS, mode, True, chunk) for mode in ('sum', 'mean')}))
-    torch.cuda.synchronize()
-    barrier = threading.Barrier(2)
-    failures = []
 
-    def run(thread):
-        try:
-            stream = torch.cuda.Stream()
-            barrier.wait()
-            with torch.cuda.stream(stream):
-                for repeat in range(10):
-                    mode = ('sum', 'mean')[repeat % 2]
-                    got, counts = reader.bags_embedding_device(
-                        jobs[thread][0], jobs[thread][1], mode=mode, missing='skip', return_counts=True, reduction='chunked')
-                    stream.synchronize()
-                    want, want_counts = jobs[thread][2][mode]
-                    if not bits_equal(got.cpu().numpy(), want) or not np.array_equal(counts.cpu().numpy().view(np.uint32), want_counts):
-                        failures.append((thread, repeat, mode))
-        except Exception as error:   # (a thread's exception is a failure of the test, not a line on stderr)
-            failures.append((thread, repr(error)))
+    def call(thread, repeat):
+        mode = ('sum', 'mean')[repeat % 2]
+        got = reader.bags_embedding_device(jobs[thread][0], jobs[thread][1], mode=mode, missing='skip', return_counts=True,
+                                           reduction='chunked')
+        return got, jobs[thread][2][mode], mode
 
-    threads = [threading.Thread(target=run, args=(thread,)) for thread in range(2)]
-    for thread in threads:
-        thread.start()
-    for thread in threads:
-        thread.join()
-    assert not failures, failures
+    run_on_two_streams(jobs, call, repeats=10)
 
 
 # ---- 8. one long bag; empty batches; offsets beyond n ----

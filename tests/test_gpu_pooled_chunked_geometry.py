@@ -19,17 +19,17 @@ import numpy as np
 import pytest
 
 from conftest import bits_equal
-from pooled_chunked_reference import (COLUMN_DIMS, COLUMN_ROWS, COLUMN_STORAGES, EDGE_CHUNK_COUNTS, PLAN_BAG_COUNTS,
-                                      PLAN_BAGS_PER_BLOCK, PLAN_THREADS, UNKNOWN, UNKNOWN_CHUNKS, WIDE_MODELS,
-                                      chunked_by_the_contract, chunked_side_by_side, column_batch, contract_batch,
-                                      derived_offsets, edge_batch, from_partial_sums, offsets_of, plan_batch, reversed_batch,
-                                      second_round_batch, sequential_by_the_contract, sub_batch, wide_batch,
-                                      with_unknown_chunks)
-from test_gpu_pooled_chunked import SENTINEL, check_chunked, narrow_bits, pooled, to_device
-from test_pooled_chunked_host import check_negative_zeros_survive, signed_zero_model, signed_zero_rows
+from pooled_device import check_chunked, for_every_key_form, narrow_bits, pooled, sweep_options, to_device
+from pooled_reference import (COLUMN_DIMS, COLUMN_ROWS, COLUMN_STORAGES, EDGE_CHUNK_COUNTS, PLAN_BAG_COUNTS, PLAN_BAGS_PER_BLOCK,
+                              PLAN_THREADS, UNKNOWN, UNKNOWN_CHUNKS, WIDE_MODELS, check_negative_zeros_survive,
+                              chunked_by_the_contract, chunked_side_by_side, column_batch, contract_batch, derived_offsets,
+                              edge_batch, from_partial_sums, offsets_of, plan_batch, reversed_batch, second_round_batch,
+                              sequential_by_the_contract, signed_zero_model, signed_zero_rows, sub_batch, wide_batch,
+                              with_unknown_chunks)
 
 pytestmark = pytest.mark.gpu
 
+SENTINEL = -1234.5
 N_ROWS = 3000
 BOTH = (False, True)   # missing='zero', missing='skip'
 
@@ -194,23 +194,7 @@ def test_very_wide_rows(native, make_model, storage, bits, dim, count):
 
 # ---- D. the geometry of the partial sums ----
 
-def set_environment(monkeypatch, **values):
-    for key in ('MEMB_HIP_LANES', 'MEMB_HIP_WAVES', 'MEMB_HIP_ROOT_BITS', 'MEMB_HIP_NO_FAST', 'MEMB_HIP_ROW_RECORDS', 'MEMB_HIP_ROW_META'):
-        monkeypatch.delenv(key, raising=False)
-    for key, value in values.items():
-        monkeypatch.setenv(key, str(value))
-
-
-def kernel_form(reader):
-    name = reader.info(1)['kernel']
-    has_sub, _, fast = [argument.strip() for argument in name[len('decode_trained<'):-1].split(',')]
-    return has_sub == 'true', fast == 'true'
-
-
 GEOMETRY_ROWS = 20000   # the models of test_key_forms_tables_and_row_layouts in tests/test_gpu_pooled_known.py
-GEOMETRIES = [({}, 0), ({}, 1), ({'MEMB_HIP_ROW_RECORDS': '0'}, 0), ({'MEMB_HIP_ROW_META': '0'}, 1), ({'MEMB_HIP_NO_FAST': 1}, 0),
-              ({'MEMB_HIP_LANES': 1, 'MEMB_HIP_WAVES': 1}, 0), ({'MEMB_HIP_LANES': 3, 'MEMB_HIP_WAVES': 2}, 0),
-              ({'MEMB_HIP_LANES': 5, 'MEMB_HIP_WAVES': 8}, 1), ({'MEMB_HIP_LANES': 25}, 0), ({'MEMB_HIP_LANES': 64}, 0)]
 
 
 def test_key_forms_tables_and_row_layouts(native, make_model, monkeypatch):
@@ -220,19 +204,16 @@ def test_key_forms_tables_and_row_layouts(native, make_model, monkeypatch):
     import torch
     chunk = native.POOL_CHUNK
     rows, offsets = contract_batch(chunk, GEOMETRY_ROWS, 11)
-    forms = set()
-    for bits, distribution in ((4, 'normal'), (6, 'student'), (8, 'student'), (2, 'normal')):
-        path, _ = make_model(GEOMETRY_ROWS, 300, 'trained', bits, distribution=distribution)
-        want = None
-        for environment, max_direct_bits in GEOMETRIES if bits != 2 else GEOMETRIES[:1]:
-            set_environment(monkeypatch, **environment)
-            reader = native.Reader(path, max_direct_decode_bits=max_direct_bits)
-            if bits != 2:   # (the forms of the sequential tests' three models)
-                forms.add(kernel_form(reader))
-            check_chunked(reader, rows, offsets, chunk, (bits, environment, max_direct_bits))
-            want = want or contract_of(reader, rows, offsets, chunk, modes=('mean',))   # (the model's rows: one R1 per model)
-            check_first(reader, rows, offsets, want, (bits, environment, max_direct_bits, 'fp16'), col_off=1, dtype=torch.float16)
-    assert forms == {(False, True), (False, False), (True, False)}, forms
+    want = {}
+
+    def check(reader, context):
+        check_chunked(reader, rows, offsets, chunk, context)
+        if context[0] not in want:   # (the model's rows: one R1 per model)
+            want[context[0]] = contract_of(reader, rows, offsets, chunk, modes=('mean',))
+        check_first(reader, rows, offsets, want[context[0]], context + ('fp16',), col_off=1, dtype=torch.float16)
+
+    for_every_key_form(native, make_model, monkeypatch, GEOMETRY_ROWS, check)   # (the forms of the sequential tests' three models)
+    for_every_key_form(native, make_model, monkeypatch, GEOMETRY_ROWS, check, [(2, 'normal')], [({}, 0)], all_forms=False)
 
 
 def test_results_do_not_depend_on_options(native, make_model):
@@ -241,15 +222,7 @@ def test_results_do_not_depend_on_options(native, make_model):
     reader = native.Reader(path)
     rows, offsets = contract_batch(chunk, N_ROWS, 11)
     want = contract_of(reader, rows, offsets, chunk)
-    try:
-        for waves in (1, 2, 4, 7, 8):
-            for tiles in (1, 2, 5, 64):
-                reader.set_option('waves_per_block', waves)
-                reader.set_option('tiles_per_wave', tiles)
-                check_first(reader, rows, offsets, want, (waves, tiles))
-    finally:
-        reader.set_option('waves_per_block', 0)
-        reader.set_option('tiles_per_wave', 0)
+    sweep_options(reader, lambda waves, tiles: check_first(reader, rows, offsets, want, (waves, tiles)))
 
 
 # ---- E. a caller-owned workspace, whatever it held before ----

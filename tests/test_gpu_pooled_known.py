@@ -7,68 +7,20 @@ Two references, both compared with bits_equal (the tolerance is zero):
   R2  what the EXISTING pooled call (missing='zero', the kernels of memb_hip_pooled.hip / memb_hip_pooled_narrow.hip) returns
       for the compacted batch: unknown entries taken out, offsets recomputed on the host.
 A bf16 / fp16 result is R1 .to(dtype) on the CPU, and R2 with that dtype."""
-import threading
+import itertools
 
 import numpy as np
 import pytest
 
 from conftest import bits_equal
+from pooled_device import (WAVES_PER_BLOCK, for_every_key_form, into_a_frame, narrow_bits, run_on_two_streams, sweep_options,
+                           to_device)
+from pooled_reference import UNKNOWN, compacted, ids_with_unknowns, offsets_of, sequential_by_the_contract
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -1234.5
-UNKNOWN = 0xFFFFFFFF
 N_ROWS = 20000
-
-
-def to_device(array, kind=np.int32):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(array).astype(np.uint32).view(kind)).cuda()
-
-
-def offsets_of(lengths):
-    return np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64))]).astype(np.int64)
-
-
-def compacted(rows, offsets, n_rows):
-    """The batch without its unknown entries: (rows, offsets, positions of the kept entries in `rows`). Offsets are read as
-    the kernel reads them -- uint32, clamped to n, a backwards range empty -- so bags may overlap: each is gathered."""
-    rows = np.asarray(rows, dtype=np.uint32)
-    clamped = np.minimum(np.asarray(offsets).astype(np.int64) & 0xFFFFFFFF, len(rows))
-    kept = []
-    lengths = []
-    for begin, end in zip(clamped[:-1], clamped[1:]):
-        positions = np.arange(begin, max(begin, end))
-        positions = positions[rows[positions] < n_rows]
-        kept.append(positions)
-        lengths.append(len(positions))
-    positions = np.concatenate(kept).astype(np.int64) if kept else np.zeros(0, dtype=np.int64)
-    return rows[positions], offsets_of(lengths), positions
-
-
-def known_by_the_contract(values, rows, offsets, n_rows, mode):
-    """R1: values = the (n, dim) float32 rows of the entries. Returns (vectors, counts). The loop runs for all bags side by
-    side: step j adds known entry j of every bag that has one."""
-    _, dense, positions = compacted(rows, offsets, n_rows)
-    begin = dense[:-1]
-    length = dense[1:] - dense[:-1]
-    out = np.zeros((len(begin), values.shape[1]), dtype=np.float32)
-    for step in range(int(length.max()) if len(length) else 0):
-        active = np.nonzero(length > step)[0]
-        addend = values[positions[begin[active] + step]]
-        out[active] = addend if step == 0 else np.add(out[active], addend, dtype=np.float32)
-    if mode == 'mean':
-        filled = length > 0
-        out[filled] = np.divide(out[filled], length[filled].astype(np.float32)[:, None], dtype=np.float32)
-    return out, length.astype(np.uint32)
-
-
-def narrow_bits(tensor):
-    """the bits of a CPU tensor of any of the three types, as a numpy array"""
-    import torch
-    if tensor.dtype == torch.float32:
-        return tensor.contiguous().numpy().view(np.uint32)
-    return tensor.contiguous().view(torch.int16).numpy().view(np.uint16)
 
 
 def check_known(reader, rows, offsets, context, modes=('sum', 'mean'), col_off=0, spare=0, dtype=None):
@@ -85,17 +37,18 @@ def check_known(reader, rows, offsets, context, modes=('sum', 'mean'), col_off=0
     bags = len(offsets) - 1
     results = {}
     for mode in modes:
-        out = torch.full((bags, col_off + dim + spare), SENTINEL, dtype=kind, device='cuda')
-        returned, counts = reader.bags_embedding_device(
-            device_rows, device_offsets, mode=mode, out=out, col_off=col_off, dtype=dtype, missing='skip', return_counts=True)
-        torch.cuda.synchronize()
-        assert returned.data_ptr() == out.data_ptr()
+        counted = []
+
+        def run(out):
+            returned, counts = reader.bags_embedding_device(
+                device_rows, device_offsets, mode=mode, out=out, col_off=col_off, dtype=dtype, missing='skip', return_counts=True)
+            counted.append(counts)
+            return returned
+
+        got = into_a_frame(run, bags, dim, context, col_off, spare, dtype, sentinel=SENTINEL)
+        counts = counted[0]
         assert counts.dtype == torch.int32 and tuple(counts.shape) == (bags,) and counts.is_cuda
-        host = out.cpu()
-        sentinel = torch.tensor(SENTINEL, dtype=kind)
-        assert (host[:, :col_off] == sentinel).all() and (host[:, col_off + dim:] == sentinel).all(), context
-        got = host[:, col_off:col_off + dim]
-        want, want_counts = known_by_the_contract(values, rows, offsets, n_rows, mode)
+        want, want_counts = sequential_by_the_contract(values, rows, offsets, n_rows, mode, True)
         assert np.array_equal(counts.cpu().numpy().view(np.uint32), want_counts), (context, mode, 'counts')
         first = torch.from_numpy(want).to(kind)                                                    # R1
         second = reader.bags_embedding_device(to_device(dense_rows), to_device(dense_offsets), mode=mode, dtype=dtype).cpu()   # R2
@@ -105,14 +58,6 @@ def check_known(reader, rows, offsets, context, modes=('sum', 'mean'), col_off=0
                 raise AssertionError('{} {} {}: {} of {} bags differ, first {}'.format(context, mode, name, len(bad), bags, bad[:8]))
         results[mode] = got.to(torch.float32).numpy()
     return results[modes[0]], want_counts
-
-
-def ids_with_unknowns(count, n_rows, seed, share=0.3):
-    rng = np.random.default_rng(seed)
-    rows = rng.integers(0, n_rows, size=count, dtype=np.int64)
-    unknown = rng.random(count) < share
-    rows[unknown] = rng.choice([UNKNOWN, n_rows, n_rows + 5, 0xFFFFFFFE], size=int(unknown.sum()))
-    return rows.astype(np.uint32)
 
 
 def shaped_bags(n_rows, seed):
@@ -220,38 +165,18 @@ def test_dims_and_strided_outputs(native, make_model, storage, bits, dim):
                         dtype=dtype)
 
 
-def set_environment(monkeypatch, **values):
-    for key in ('MEMB_HIP_LANES', 'MEMB_HIP_WAVES', 'MEMB_HIP_ROOT_BITS', 'MEMB_HIP_NO_FAST', 'MEMB_HIP_ROW_RECORDS', 'MEMB_HIP_ROW_META'):
-        monkeypatch.delenv(key, raising=False)
-    for key, value in values.items():
-        monkeypatch.setenv(key, str(value))
-
-
-def kernel_form(reader):
-    name = reader.info(1)['kernel']
-    has_sub, _, fast = [argument.strip() for argument in name[len('decode_trained<'):-1].split(',')]
-    return has_sub == 'true', fast == 'true'
-
-
 def test_key_forms_tables_and_row_layouts(native, make_model, monkeypatch):
     """Nibble keys, byte keys with a one-level table (MEMB_HIP_NO_FAST) and with two-level tables (max_direct_decode_bits=1);
     row records, compact streams with rowMeta records and with the two index arrays; 1 to 64 lanes per word."""
     import torch
     rows, offsets = shaped_bags(N_ROWS, 9)
-    forms = set()
-    for bits, distribution in ((4, 'normal'), (6, 'student'), (8, 'student')):
-        path, _ = make_model(N_ROWS, 300, 'trained', bits, distribution=distribution)
-        cases = [({}, 0), ({}, 1), ({'MEMB_HIP_ROW_RECORDS': '0'}, 0), ({'MEMB_HIP_ROW_META': '0'}, 1),
-                 ({'MEMB_HIP_NO_FAST': 1}, 0), ({'MEMB_HIP_LANES': 1, 'MEMB_HIP_WAVES': 1}, 0), ({'MEMB_HIP_LANES': 3, 'MEMB_HIP_WAVES': 2}, 0),
-                 ({'MEMB_HIP_LANES': 5, 'MEMB_HIP_WAVES': 8}, 1), ({'MEMB_HIP_LANES': 25}, 0), ({'MEMB_HIP_LANES': 64}, 0)]
-        for environment, max_direct_bits in cases:
-            set_environment(monkeypatch, **environment)
-            reader = native.Reader(path, max_direct_decode_bits=max_direct_bits)
-            forms.add(kernel_form(reader))
-            check_known(reader, rows, offsets, (bits, environment, max_direct_bits))
-            check_known(reader, rows, offsets, (bits, environment, max_direct_bits, 'col_off 1'), modes=('mean',), col_off=1, spare=1)
-            check_known(reader, rows, offsets, (bits, environment, max_direct_bits, 'fp16'), modes=('mean',), col_off=1, dtype=torch.float16)
-    assert forms == {(False, True), (False, False), (True, False)}, forms
+
+    def check(reader, context):
+        check_known(reader, rows, offsets, context)
+        check_known(reader, rows, offsets, context + ('col_off 1',), modes=('mean',), col_off=1, spare=1)
+        check_known(reader, rows, offsets, context + ('fp16',), modes=('mean',), col_off=1, dtype=torch.float16)
+
+    for_every_key_form(native, make_model, monkeypatch, N_ROWS, check)
 
 
 # ---- 2. offsets a host would have refused: the defined, clamped result ----
@@ -386,21 +311,16 @@ def test_results_do_not_depend_on_options(native, make_model, bits):
         return np.concatenate([vectors.cpu().numpy(), narrow.to(torch.float32).cpu().numpy()]), counts.cpu().numpy()
 
     reference = {mode: both(mode) for mode in ('sum', 'mean')}
-    try:
-        for waves in (1, 2, 4, 7, 8):
-            for tiles in (1, 2, 5, 8, 64):
-                reader.set_option('waves_per_block', waves)
-                reader.set_option('tiles_per_wave', tiles)
-                for mode in ('sum', 'mean'):
-                    vectors, counts = both(mode)
-                    assert bits_equal(vectors, reference[mode][0]) and np.array_equal(counts, reference[mode][1]), (waves, tiles, mode)
-    finally:
-        reader.set_option('waves_per_block', 0)
-        reader.set_option('tiles_per_wave', 0)
+
+    def run(waves, tiles):
+        for mode in ('sum', 'mean'):
+            vectors, counts = both(mode)
+            assert bits_equal(vectors, reference[mode][0]) and np.array_equal(counts, reference[mode][1]), (waves, tiles, mode)
+
+    sweep_options(reader, run, itertools.product(WAVES_PER_BLOCK, (1, 2, 5, 8, 64)))
 
 
 def test_two_threads_on_two_streams(native, make_model):
-    import torch
     path, _ = make_model(N_ROWS, 300, 'trained', 4)
     reader = native.Reader(path)
     jobs = []
@@ -410,33 +330,14 @@ def test_two_threads_on_two_streams(native, make_model):
         offsets = offsets_of(lengths)
         values = reader.rows_embedding(rows)
         jobs.append((to_device(rows), to_device(offsets),
-                     {mode: known_by_the_contract(values, rows, offsets, N_ROWS, mode) for mode in ('sum', 'mean')}))
-    torch.cuda.synchronize()
-    barrier = threading.Barrier(2)
-    failures = []
+                     {mode: sequential_by_the_contract(values, rows, offsets, N_ROWS, mode, True) for mode in ('sum', 'mean')}))
 
-    def run(thread):
-        try:
-            stream = torch.cuda.Stream()
-            barrier.wait()
-            with torch.cuda.stream(stream):
-                for repeat in range(20):
-                    mode = ('sum', 'mean')[repeat % 2]
-                    got, counts = reader.bags_embedding_device(
-                        jobs[thread][0], jobs[thread][1], mode=mode, missing='skip', return_counts=True)
-                    stream.synchronize()
-                    want, want_counts = jobs[thread][2][mode]
-                    if not bits_equal(got.cpu().numpy(), want) or not np.array_equal(counts.cpu().numpy().view(np.uint32), want_counts):
-                        failures.append((thread, repeat, mode))
-        except Exception as error:   # (a thread's exception is a failure of the test, not a line on stderr)
-            failures.append((thread, repr(error)))
+    def call(thread, repeat):
+        mode = ('sum', 'mean')[repeat % 2]
+        got = reader.bags_embedding_device(jobs[thread][0], jobs[thread][1], mode=mode, missing='skip', return_counts=True)
+        return got, jobs[thread][2][mode], mode
 
-    threads = [threading.Thread(target=run, args=(thread,)) for thread in range(2)]
-    for thread in threads:
-        thread.start()
-    for thread in threads:
-        thread.join()
-    assert not failures, failures
+    run_on_two_streams(jobs, call)
 
 
 # ---- 7. the Python surface ----
@@ -454,7 +355,7 @@ def test_python_entry_points_and_their_errors(native, make_model):
     values = reader.rows_embedding(rows)
     host_reader = native.Reader(path, device='cpu')
     for mode in ('sum', 'mean'):
-        want, want_counts = known_by_the_contract(values, rows, offsets, N_ROWS, mode)
+        want, want_counts = sequential_by_the_contract(values, rows, offsets, N_ROWS, mode, True)
         assert list(want_counts) == [5, 0, 0, 17, 1, 1]
         vectors, counts = reader.sentences_embedding_device(sentences, mode=mode, missing='skip', return_counts=True)
         assert bits_equal(vectors.cpu().numpy(), want) and list(counts.cpu().numpy()) == list(want_counts)
@@ -519,6 +420,6 @@ def test_headline_model_in_bags_of_sixteen_with_every_tenth_id_unknown(native):
         want = reader.bags_embedding_device(dense_rows, dense_offsets, mode=mode)
         assert torch.equal(got.view(torch.int32), want.view(torch.int32)), mode                       # R2
         assert torch.equal(counts, dense_offsets[1:] - dense_offsets[:-1])
-        first, first_counts = known_by_the_contract(values, sample_rows, sample_offsets, count, mode)    # R1 on the sample
+        first, first_counts = sequential_by_the_contract(values, sample_rows, sample_offsets, count, mode, True)    # R1 on the sample
         assert bits_equal(got[torch.from_numpy(sample).cuda()].cpu().numpy(), first), mode
         assert np.array_equal(counts.cpu().numpy()[sample].view(np.uint32), first_counts)

@@ -4,16 +4,16 @@ pool_full_narrow; memb_hip.hip: launchPooled with a narrow outType).
 The contract (include/memb_hip_pooled.h): a narrow value is the float32 pooled value rounded ONCE to nearest even. Two
 oracles, which must agree with each other before the device is asked:
   (a) the reader's own float32 bags_embedding_device result (pinned by test_gpu_pooled.py), .cpu().to(dtype)
-  (b) the contract's explicit float32 loop over rows_embedding_device(rows) (test_gpu_pooled.pooled_by_the_contract),
+  (b) the contract's explicit float32 loop over rows_embedding_device(rows) (pooled_reference.pooled_by_the_contract),
       then the same cast
-Compared as the bits of .view(torch.int16): the tolerance is zero."""
-import threading
-
+Compared as 16-bit patterns (narrow_bits): the tolerance is zero."""
 import numpy as np
 import pytest
 
 from conftest import bits_equal
-from test_gpu_pooled import ids_with_misses, offsets_of, pooled_by_the_contract, set_environment, to_device
+from pooled_device import (KEY_FORM_CASES, for_every_key_form, into_a_frame, narrow_bits, run_on_two_streams, set_environment,
+                           sweep_options, to_device)
+from pooled_reference import ids_with_misses, offsets_of, pooled_by_the_contract
 
 pytestmark = pytest.mark.gpu
 
@@ -25,11 +25,6 @@ MODES = ('sum', 'mean')
 def narrow_dtypes():
     import torch
     return (torch.bfloat16, torch.float16)
-
-
-def bits(tensor):
-    import torch
-    return tensor.contiguous().view(torch.int16)
 
 
 def expected(reader, rows, offsets):
@@ -48,29 +43,19 @@ def expected(reader, rows, offsets):
 def check_narrow(reader, rows, offsets, context, want=None, col_off=0, spare=0, shifted=False):
     """Both dtypes and both modes against the oracles; the columns around the bags keep their sentinel. shifted: `out` is
     a view that starts one element into a larger buffer (2-byte aligned only). Returns {(mode, dtype): CPU tensor}."""
-    import torch
     dim = reader.dim
     device_rows, device_offsets = to_device(rows), to_device(offsets)
     want = want or expected(reader, rows, offsets)
     bags = len(offsets) - 1
-    width = col_off + dim + spare
     results = {}
     for mode in MODES:
         for dtype in narrow_dtypes():
-            buffer = torch.full((bags * width + 1,), SENTINEL, dtype=dtype, device='cuda')
-            out = buffer[1:].view(bags, width) if shifted else buffer[:bags * width].view(bags, width)
-            assert out.data_ptr() % 4 == (2 if shifted else 0)
-            returned = reader.bags_embedding_device(device_rows, device_offsets, mode=mode, out=out, col_off=col_off, dtype=dtype)
-            torch.cuda.synchronize()
-            assert returned.data_ptr() == out.data_ptr() and returned.dtype == dtype
-            host = out.cpu()
-            guard = bits(torch.tensor([SENTINEL], dtype=dtype))[0]
-            assert (bits(host[:, :col_off]) == guard).all() and (bits(host[:, col_off + dim:]) == guard).all(), (context, mode, dtype)
-            assert bits(buffer[:1] if shifted else buffer[-1:]).cpu()[0] == guard, (context, mode, dtype)   # (outside the view)
-            got = host[:, col_off:col_off + dim]
-            same = bits(got) == bits(want[mode].to(dtype))
-            if not bool(same.all()):
-                bad = np.nonzero(~same.numpy().all(axis=1))[0]
+            got = into_a_frame(
+                lambda out: reader.bags_embedding_device(device_rows, device_offsets, mode=mode, out=out, col_off=col_off, dtype=dtype),
+                bags, dim, (context, mode, dtype), col_off, spare, dtype, SENTINEL, shifted)
+            same = narrow_bits(got) == narrow_bits(want[mode].to(dtype))
+            if not same.all():
+                bad = np.nonzero(~same.all(axis=1))[0]
                 raise AssertionError('{} {} {}: {} of {} bags differ, first {}'.format(context, mode, dtype, len(bad), bags, bad[:8]))
             results[mode, dtype] = got
     return results
@@ -91,12 +76,12 @@ def test_bag_shapes(native, make_model, storage, bits_per_value):
     for dtype in narrow_dtypes():
         decoded = reader.rows_embedding_device(to_device(rows), dtype=dtype).cpu()
         for mode in MODES:
-            assert bool((bits(ones[mode, dtype]) == bits(decoded)).all()), (context, mode, dtype)
+            assert (narrow_bits(ones[mode, dtype]) == narrow_bits(decoded)).all(), (context, mode, dtype)
     # empty bags at the start, in the middle and at the end
     lengths = [0, 0, 0, 5, 1, 0, 12, 0, 0, 3, 64, 0, 9, 0, 0]
     empties = check_narrow(reader, ids_with_misses(sum(lengths), N_ROWS, 2), offsets_of(lengths), context + ('empties',))
     for result in empties.values():
-        assert not bits(result[[0, 1, 2, 5, 7, 8, 11, 13, 14]]).any()   # +0.0
+        assert not narrow_bits(result[[0, 1, 2, 5, 7, 8, 11, 13, 14]]).any()   # +0.0
     # fixed lengths that straddle the 8-word tile
     for length in (7, 8, 9, 17):
         count = 2000 // length
@@ -113,7 +98,7 @@ def test_bag_shapes(native, make_model, storage, bits_per_value):
     missing = check_narrow(reader, np.array([0xFFFFFFFF, N_ROWS, N_ROWS + 5, 0xFFFFFFFF, 0xFFFFFFFE], dtype=np.uint32), [0, 2, 5],
                            context + ('all missing',))
     for result in missing.values():
-        assert not bits(result).any()
+        assert not narrow_bits(result).any()
     for dtype in narrow_dtypes():
         # bags = 0: nothing is launched, an empty result
         empty = reader.bags_embedding_device(to_device(rows), to_device([len(rows)]), dtype=dtype)
@@ -121,7 +106,7 @@ def test_bag_shapes(native, make_model, storage, bits_per_value):
     # n = 0: +0.0 for every bag
     zero = check_narrow(reader, np.zeros(0, dtype=np.uint32), [0, 0, 0, 0], context + ('n = 0',))
     for result in zero.values():
-        assert tuple(result.shape) == (3, 300) and not bits(result).any()
+        assert tuple(result.shape) == (3, 300) and not narrow_bits(result).any()
     torch.cuda.synchronize()
 
 
@@ -200,15 +185,15 @@ def test_the_value_is_rounded_once(native, tmp_path):
             for dtype in narrow_dtypes():
                 name = str(dtype).split('.')[1]
                 if name in pinned:
-                    value = np.int16(np.uint16(pinned[name]))
+                    value = np.uint16(pinned[name])
                     # the oracle says so, and the device (check_narrow: equal to the oracle) with it
-                    assert bool((bits(want[mode][index].to(dtype)) == value).all()), (bag, mode, name, 'oracle')
-                    assert bool((bits(results[mode, dtype][index]) == value).all()), (bag, mode, name)
+                    assert (narrow_bits(want[mode][index].to(dtype)) == value).all(), (bag, mode, name, 'oracle')
+                    assert (narrow_bits(results[mode, dtype][index]) == value).all(), (bag, mode, name)
     # the traps are traps: per-entry narrowing gives other bits for the first bag
     stepwise = torch.tensor(1.0, dtype=torch.bfloat16)
     for _ in range(2):
         stepwise = (stepwise.float() + 2.0 ** -8).to(torch.bfloat16)
-    assert int(bits(stepwise.reshape(1))[0]) == 0x3F80
+    assert int(narrow_bits(stepwise.reshape(1))[0]) == 0x3F80
 
 
 # ---- 4. launch geometry and key forms never change a result ----
@@ -220,37 +205,36 @@ def test_results_do_not_depend_on_options(native, make_model, bits_per_value):
     lengths = np.random.default_rng(bits_per_value).geometric(1 / 16.0, size=500)
     rows, offsets = ids_with_misses(int(lengths.sum()), N_ROWS, 3), offsets_of(lengths)
     want = expected(reader, rows, offsets)
-    try:
-        for waves, tiles in ((1, 1), (2, 64), (4, 2), (7, 5), (8, 1)):
-            reader.set_option('waves_per_block', waves)
-            reader.set_option('tiles_per_wave', tiles)
-            check_narrow(reader, rows, offsets, (bits_per_value, waves, tiles), want=want)
-            check_narrow(reader, rows, offsets, (bits_per_value, waves, tiles, 'columns'), want=want, col_off=1, spare=1)
-    finally:
-        reader.set_option('waves_per_block', 0)
-        reader.set_option('tiles_per_wave', 0)
+
+    def run(waves, tiles):
+        check_narrow(reader, rows, offsets, (bits_per_value, waves, tiles), want=want)
+        check_narrow(reader, rows, offsets, (bits_per_value, waves, tiles, 'columns'), want=want, col_off=1, spare=1)
+
+    sweep_options(reader, run, ((1, 1), (2, 64), (4, 2), (7, 5), (8, 1)))
 
 
 def test_key_forms_tables_and_row_layouts(native, make_model, monkeypatch):
     lengths = np.random.default_rng(1).geometric(1 / 12.0, size=300)
     rows, offsets = ids_with_misses(int(lengths.sum()), N_ROWS, 9), offsets_of(lengths)
-    for bits_per_value, distribution in ((4, 'normal'), (6, 'student')):
-        path, _ = make_model(N_ROWS, 300, 'trained', bits_per_value, distribution=distribution)
-        set_environment(monkeypatch)
-        want = expected(native.Reader(path), rows, offsets)
-        cases = [({}, 1), ({'MEMB_HIP_ROW_RECORDS': '0'}, 0), ({'MEMB_HIP_ROW_META': '0'}, 1), ({'MEMB_HIP_NO_FAST': 1}, 0),
-                 ({'MEMB_HIP_LANES': 3, 'MEMB_HIP_WAVES': 2}, 0), ({'MEMB_HIP_LANES': 25}, 0), ({'MEMB_HIP_LANES': 64}, 0)]
-        for environment, max_direct_bits in cases:
-            set_environment(monkeypatch, **environment)
-            reader = native.Reader(path, max_direct_decode_bits=max_direct_bits)
-            check_narrow(reader, rows, offsets, (bits_per_value, environment, max_direct_bits), want=want)
-            check_narrow(reader, rows, offsets, (bits_per_value, environment, max_direct_bits, 'columns'), want=want, col_off=1, spare=1)
+    models = [(4, 'normal'), (6, 'student')]
+    set_environment(monkeypatch)
+    want = {bits_per_value: expected(native.Reader(make_model(N_ROWS, 300, 'trained', bits_per_value, distribution=distribution)[0]),
+                                     rows, offsets)
+            for bits_per_value, distribution in models}
+
+    def check(reader, context):
+        check_narrow(reader, rows, offsets, context, want=want[context[0]])
+        check_narrow(reader, rows, offsets, context + ('columns',), want=want[context[0]], col_off=1, spare=1)
+
+    # (seven of the ten cases: what the key forms themselves do is pinned in fp32, by test_gpu_pooled.py)
+    cases = [case for case in KEY_FORM_CASES
+             if case not in (({}, 0), ({'MEMB_HIP_LANES': 1, 'MEMB_HIP_WAVES': 1}, 0), ({'MEMB_HIP_LANES': 5, 'MEMB_HIP_WAVES': 8}, 1))]
+    for_every_key_form(native, make_model, monkeypatch, N_ROWS, check, models, cases, all_forms=False)
 
 
 # ---- 5. two callers at once ----
 
 def test_two_threads_on_two_streams(native, make_model):
-    import torch
     path, _ = make_model(N_ROWS, 300, 'trained', 4)
     reader = native.Reader(path)
     jobs = []
@@ -258,32 +242,15 @@ def test_two_threads_on_two_streams(native, make_model):
         lengths = np.random.default_rng(thread).geometric(1 / 16.0, size=2000)
         rows, offsets = ids_with_misses(int(lengths.sum()), N_ROWS, thread), offsets_of(lengths)
         want = expected(reader, rows, offsets)
-        jobs.append((to_device(rows), to_device(offsets), dtype, {mode: bits(want[mode].to(dtype)) for mode in MODES}))
-    torch.cuda.synchronize()
-    barrier = threading.Barrier(2)
-    failures = []
+        jobs.append((to_device(rows), to_device(offsets), dtype, {mode: narrow_bits(want[mode].to(dtype)) for mode in MODES}))
 
-    def run(thread):
-        try:
-            device_rows, device_offsets, dtype, want = jobs[thread]
-            stream = torch.cuda.Stream()
-            barrier.wait()
-            with torch.cuda.stream(stream):
-                for repeat in range(10):
-                    mode = MODES[repeat % 2]
-                    got = reader.bags_embedding_device(device_rows, device_offsets, mode=mode, dtype=dtype)
-                    stream.synchronize()
-                    if not bool((bits(got.cpu()) == want[mode]).all()):
-                        failures.append((thread, repeat, mode))
-        except Exception as error:   # (a thread's exception is a failure of the test, not a line on stderr)
-            failures.append((thread, repr(error)))
+    def call(thread, repeat):
+        device_rows, device_offsets, dtype, want = jobs[thread]
+        mode = MODES[repeat % 2]
+        got = reader.bags_embedding_device(device_rows, device_offsets, mode=mode, dtype=dtype)
+        return (got,), (want[mode],), mode
 
-    threads = [threading.Thread(target=run, args=(thread,)) for thread in range(2)]
-    for thread in threads:
-        thread.start()
-    for thread in threads:
-        thread.join()
-    assert not failures, failures
+    run_on_two_streams(jobs, call, repeats=10)
 
 
 # ---- 6. the Python surface ----
@@ -305,7 +272,7 @@ def test_python_entry_points_and_their_errors(native, make_model):
         for dtype in narrow_dtypes():
             got = reader.sentences_embedding_device(sentences, mode=mode, dtype=dtype)
             assert got.dtype == dtype and tuple(got.shape) == (5, 300)
-            assert bool((bits(got.cpu()) == bits(fp32.cpu().to(dtype))).all()), (mode, dtype)
+            assert (narrow_bits(got.cpu()) == narrow_bits(fp32.cpu().to(dtype))).all(), (mode, dtype)
     for dtype in narrow_dtypes():
         assert reader.sentences_embedding_device([], dtype=dtype).dtype == dtype
         out = torch.empty((5, 300), dtype=dtype, device='cuda')

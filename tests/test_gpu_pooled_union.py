@@ -11,38 +11,14 @@ import numpy as np
 import pytest
 
 from conftest import bits_equal
-from test_gpu_pooled import ids_with_misses, offsets_of, pooled_by_the_contract, to_device
+from pooled_device import into_a_frame, to_device, union_values
+from pooled_reference import ids_with_misses, merged_rows, offsets_of, pooled_by_the_contract, union_ids
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = np.float32(-1234.5)
 N_ROWS = 3000
 FUSED, DENSE = 'pool_trained_union<', 'pool_dense<'
-
-
-def merged_rows(mode, pieces):
-    if mode == 'concatenate':
-        return np.hstack(pieces)
-    total = pieces[0]
-    for piece in pieces[1:]:
-        total = np.add(total, piece, dtype=np.float32)
-    return np.divide(total, np.float32(len(pieces)), dtype=np.float32)
-
-
-def union_ids(count, readers, seed, n_rows=N_ROWS):
-    """Row ids drawn independently per reader -- an entry is missing in one reader, in another, in all or in none -- and a
-    stretch of entries that no reader has"""
-    rows = [ids_with_misses(count, n_rows, seed + 100 * position) for position in range(readers)]
-    for ids in rows:
-        ids[count // 2:count // 2 + 9] = 0xFFFFFFFF
-    return rows
-
-
-def union_values(union_mode, readers, rows):
-    n = len(rows[0])
-    if not n:
-        return np.zeros((0, sum(reader.dim for reader in readers) if union_mode == 'concatenate' else readers[0].dim), dtype=np.float32)
-    return merged_rows(union_mode, [reader.rows_embedding_device(to_device(ids)).cpu().numpy() for reader, ids in zip(readers, rows)])
 
 
 def template_arguments(name):
@@ -53,7 +29,6 @@ def check_union(union, readers, rows, offsets, context, modes=('sum', 'mean'), c
                 values=None):
     """Both pooling modes against the contract over the merged rows; the columns around the bags keep their sentinel;
     kernel: what last_pooled_kernel must start with. Returns the result of the first mode."""
-    import torch
     dim = union.dim
     device_rows = [to_device(ids) for ids in rows]
     device_offsets = to_device(offsets)
@@ -62,16 +37,11 @@ def check_union(union, readers, rows, offsets, context, modes=('sum', 'mean'), c
     bags = len(offsets) - 1
     results = {}
     for mode in modes:
-        out = torch.full((bags, col_off + dim + spare), float(SENTINEL), dtype=torch.float32, device='cuda')
-        returned = union.pooled_rows_device(device_rows, device_offsets, mode=mode, out=out, col_off=col_off)
-        torch.cuda.synchronize()
-        assert returned.data_ptr() == out.data_ptr()
+        got = into_a_frame(lambda out: union.pooled_rows_device(device_rows, device_offsets, mode=mode, out=out, col_off=col_off),
+                           bags, dim, context, col_off, spare, sentinel=SENTINEL).numpy()
         if kernel and bags:
             assert union.last_pooled_kernel.startswith(kernel), (context, union.last_pooled_kernel)
-        host = out.cpu().numpy()
-        assert (host[:, :col_off] == SENTINEL).all() and (host[:, col_off + dim:] == SENTINEL).all(), context
         want = pooled_by_the_contract(values, offsets, mode)
-        got = host[:, col_off:col_off + dim]
         if not bits_equal(got, want):
             bad = np.nonzero((got.view(np.uint32) != want.view(np.uint32)).any(axis=1))[0]
             raise AssertionError('{} {}: {} of {} bags differ, first {}'.format(context, mode, len(bad), bags, bad[:8]))
@@ -126,7 +96,7 @@ def test_fused_average_bag_shapes(native, make_model, bits, nibbles):
         return check_union(union, readers, rows, offsets, (bits, what), kernel=FUSED)
 
     # all bags of one entry: the merged rows themselves, bit for bit
-    rows = union_ids(3001, 2, 1)
+    rows = union_ids(3001, 2, 1, N_ROWS)
     ones = check(rows, np.arange(3002), 'ones')
     assert bits_equal(ones, union_values('average', readers, rows))
     has_sub, fast, count, out_type = template_arguments(union.last_pooled_kernel)
@@ -137,17 +107,17 @@ def test_fused_average_bag_shapes(native, make_model, bits, nibbles):
     assert has_sub == {(6, 8): 'true', (4, 6): own_has_sub[1]}.get(bits, 'false'), union.last_pooled_kernel
     # empty bags at the start, in the middle and at the end
     lengths = [0, 0, 0, 5, 1, 0, 12, 0, 0, 3, 64, 0, 9, 0, 0]
-    check(union_ids(sum(lengths), 2, 2), offsets_of(lengths), 'empties')
+    check(union_ids(sum(lengths), 2, 2, N_ROWS), offsets_of(lengths), 'empties')
     # fixed lengths that straddle the 8-word tile
     for length in (7, 8, 9, 17):
-        check(union_ids(length * 400, 2, length), np.arange(0, length * 400 + 1, length), ('fixed', length))
+        check(union_ids(length * 400, 2, length, N_ROWS), np.arange(0, length * 400 + 1, length), ('fixed', length))
     # seeded geometric lengths
     for mean_length in (3, 16):
         lengths = rng.geometric(1.0 / mean_length, size=500) - (rng.random(500) < 0.05)
-        check(union_ids(int(lengths.sum()), 2, mean_length), offsets_of(lengths), ('geometric', mean_length))
+        check(union_ids(int(lengths.sum()), 2, mean_length, N_ROWS), offsets_of(lengths), ('geometric', mean_length))
     # one bag that carries across hundreds of tiles, alone and between small ones
-    check(union_ids(5000, 2, 5), [0, 5000], 'one long bag')
-    check(union_ids(5020, 2, 6), offsets_of([3, 0, 7, 5000, 1, 9]), 'long bag among small')
+    check(union_ids(5000, 2, 5, N_ROWS), [0, 5000], 'one long bag')
+    check(union_ids(5020, 2, 6, N_ROWS), offsets_of([3, 0, 7, 5000, 1, 9]), 'long bag among small')
     # every entry missing in every reader
     missing = [np.array([0xFFFFFFFF, N_ROWS, N_ROWS + 1, 0xFFFFFFFF, 0xFFFFFFFE], dtype=np.uint32),
                np.array([N_ROWS, 0xFFFFFFFF, 0xFFFFFFFF, N_ROWS + 7, N_ROWS], dtype=np.uint32)]
@@ -160,7 +130,7 @@ def test_fused_average_bag_shapes(native, make_model, bits, nibbles):
     empty = union.pooled_rows_device([to_device(ids) for ids in rows], to_device([len(rows[0])]))
     assert tuple(empty.shape) == (0, 300)
     # offsets that run past n are clamped
-    rows = union_ids(1000, 2, 8)
+    rows = union_ids(1000, 2, 8, N_ROWS)
     check(rows, np.array([0, 10, 25, 40, 5000, 0xFFFFFFFF], dtype=np.int64), 'offsets past n')
     torch.cuda.synchronize()
 
@@ -172,10 +142,10 @@ def test_three_and_four_readers(native, make_model, count):
     readers = trained_readers(native, make_model, (4,) * count)
     union = native.ReadersUnion(readers, 'average')
     lengths = np.random.default_rng(count).geometric(1 / 9.0, size=500)
-    check_union(union, readers, union_ids(int(lengths.sum()), count, count), offsets_of(lengths), ('readers', count), kernel=FUSED)
+    check_union(union, readers, union_ids(int(lengths.sum()), count, count, N_ROWS), offsets_of(lengths), ('readers', count), kernel=FUSED)
     fast = 'true' if all(nibble_keys(reader) for reader in readers) else 'false'
     assert template_arguments(union.last_pooled_kernel)[1:] == [fast, str(count), '0']
-    ones = union_ids(700, count, 40 + count)
+    ones = union_ids(700, count, 40 + count, N_ROWS)
     check_union(union, readers, ones, np.arange(701), ('readers', count, 'ones'), kernel=FUSED)
 
 
@@ -188,7 +158,7 @@ def test_dims_and_strided_outputs(native, make_model, dim, fused):
     readers = trained_readers(native, make_model, (2, 2) if dim == 4 else (4, 4), dim=dim, count=700)
     union = native.ReadersUnion(readers, 'average')
     lengths = np.random.default_rng(dim).geometric(1 / 9.0, size=300)
-    rows = union_ids(int(lengths.sum()), 2, dim, n_rows=700)
+    rows = union_ids(int(lengths.sum()), 2, dim, 700)
     values = union_values('average', readers, rows)
     for col_off, spare in ((0, 0), (4, 4), (2, 1)):
         # a destination that is not aligned to a piece takes the fallback whatever the dim
@@ -204,7 +174,7 @@ def test_fallback_storages(native, make_model):
     full = native.Reader(make_model(N_ROWS, 300, 'full', 8, seed=53)[0])
     trained = trained_readers(native, make_model, (4, 4))
     lengths = np.random.default_rng(4).geometric(1 / 7.0, size=400)
-    rows = union_ids(int(lengths.sum()), 2, 4)
+    rows = union_ids(int(lengths.sum()), 2, 4, N_ROWS)
     for readers, what in ((uniform, 'uniform / uniform'), ([full, trained[0]], 'full / trained')):
         union = native.ReadersUnion(readers, 'average')
         check_union(union, readers, rows, offsets_of(lengths), what, kernel=DENSE)
@@ -290,7 +260,7 @@ def test_narrow_results(native, make_model, tmp_path):
     for readers, n_rows, kernel in ((scaled, 600, FUSED), (trained_readers(native, make_model, (4, 6)), N_ROWS, FUSED),
                                     (uniform, N_ROWS, DENSE)):
         union = native.ReadersUnion(readers, 'average')
-        rows = [to_device(ids) for ids in union_ids(int(lengths.sum()), 2, 6, n_rows=n_rows)]
+        rows = [to_device(ids) for ids in union_ids(int(lengths.sum()), 2, 6, n_rows)]
         offsets = to_device(offsets_of(lengths))
         for mode in ('sum', 'mean'):
             wide = union.pooled_rows_device(rows, offsets, mode=mode)
@@ -320,7 +290,7 @@ def test_concatenate(native, make_model):
     union = native.ReadersUnion(readers, 'concatenate')
     assert union.dim == 371
     lengths = np.random.default_rng(7).geometric(1 / 6.0, size=300) - 1
-    rows = union_ids(int(lengths.sum()), 3, 7)
+    rows = union_ids(int(lengths.sum()), 3, 7, N_ROWS)
     values = union_values('concatenate', readers, rows)
     for col_off in (0, 3):
         check_union(union, readers, rows, offsets_of(lengths), ('concatenate', col_off), col_off=col_off, spare=col_off,
@@ -400,7 +370,7 @@ def test_refusals(native, make_model):
     readers = trained_readers(native, make_model, (4, 4))
     union = native.ReadersUnion(readers, 'average')
     lengths = [3, 0, 5, 9]
-    rows = union_ids(sum(lengths), 2, 9)
+    rows = union_ids(sum(lengths), 2, 9, N_ROWS)
     device_rows, offsets = [to_device(ids) for ids in rows], to_device(offsets_of(lengths))
     sentinel = torch.full((4, 300), float(SENTINEL), dtype=torch.float32, device='cuda')
 

@@ -1,5 +1,5 @@
 """reduction='chunked' of a device='cpu' reader (Reader.bags_embedding): the contract of include/memb_hip_pooled_chunked.h
-on the host, against the explicit numpy loop of tests/pooled_chunked_reference.py. Bit for bit; no GPU. Also what
+on the host, against the explicit numpy loop of tests/pooled_reference.py. Bit for bit; no GPU. Also what
 tests/test_gpu_pooled_chunked_geometry.py relies on before it runs: its batch builders, and that the side-by-side reference
 it uses for very many bags has the bits of the per-bag loop."""
 import os
@@ -8,12 +8,13 @@ import re
 import numpy as np
 import pytest
 
-import pooled_chunked_reference as reference
+import pooled_reference as reference
 from conftest import REPO, bits_equal
-from pooled_chunked_reference import (COLUMN_DIMS, COLUMN_ROWS, COLUMN_STORAGES, EDGE_CHUNK_COUNTS, LONGEST, PLAN_BAG_COUNTS,
-                                      UNKNOWN, UNKNOWN_CHUNKS, WIDE_MODELS, chunked_by_the_contract, chunked_side_by_side,
-                                      column_batch, contract_batch, contract_lengths, edge_batch, in_order, inner_batches,
-                                      offsets_of, plan_batch, sequential_by_the_contract, wide_batch, with_unknown_chunks)
+from pooled_reference import (COLUMN_DIMS, COLUMN_ROWS, COLUMN_STORAGES, EDGE_CHUNK_COUNTS, LONGEST, PLAN_BAG_COUNTS, UNKNOWN,
+                              UNKNOWN_CHUNKS, WIDE_MODELS, check_negative_zeros_survive, check_skip_cases, chunked_by_the_contract,
+                              chunked_side_by_side, column_batch, contract_batch, contract_lengths, edge_batch, inner_batches,
+                              offsets_of, plan_batch, sequential_by_the_contract, signed_zero_model, signed_zero_rows, skip_cases,
+                              wide_batch, with_unknown_chunks)
 
 N_ROWS = 3000
 
@@ -86,54 +87,6 @@ def test_entries_outside_the_bags_belong_to_no_bag(native, reader):
                 short = np.nonzero(offsets[1:] - offsets[:-1] <= chunk)[0]   # at most one chunk: the sequential bits
                 sequential = reader.bags_embedding(rows, offsets, mode=mode, missing='skip' if skip else 'zero')
                 assert bits_equal(got[short], sequential[short]), (name, mode, skip)
-
-
-def signed_zero_model(native, directory):
-    """A `full` model whose row 0 is all -0.0 and whose rows 1 and 2 are subnormal with mixed signs, -0.0 in their first
-    columns."""
-    rng = np.random.default_rng(41)
-    count, dim = 40, 300
-    vectors = rng.integers(-70000, 70000, size=(count, dim)).astype(np.float32) * np.float32(1.4e-45)
-    vectors[0] = -0.0
-    vectors[1, :50] = -0.0
-    vectors[2, :30] = -0.0
-    assert (np.abs(vectors) < 1.1754944e-38).all() and (vectors[1] > 0).any() and (vectors[1] < 0).any()
-    builder = native.Builder(dim, 'full', 8)
-    builder.add_words(['s{:04d}'.format(i) for i in range(count)], vectors)
-    path = str(directory / 'signed_zero.bin')
-    builder.save(path)
-    return path, count
-
-
-def skip_cases(chunk, count):
-    """(rows, offsets): a bag of 3 C entries -- first chunk: one known row of -0.0 among unknown entries, middle chunk all
-    0xFFFFFFFF, last chunk rows 0, 1, 2 and then row 0 again and again -- a bag of 2 C + 3 unknown entries, and a bag of
-    3 C + 1 subnormal rows."""
-    first = np.full(chunk, UNKNOWN, dtype=np.uint32)
-    first[chunk // 2] = 0
-    middle = np.full(chunk, UNKNOWN, dtype=np.uint32)
-    last = np.zeros(chunk, dtype=np.uint32)
-    last[:3] = [0, 1, 2]
-    unknown = np.full(2 * chunk + 3, UNKNOWN, dtype=np.uint32)
-    unknown[5] = count   # (an id that is not in the model is unknown too)
-    subnormal = (np.arange(3 * chunk + 1) % (count - 1) + 1).astype(np.uint32)
-    rows = np.concatenate([first, middle, last, unknown, subnormal])
-    return rows, offsets_of([3 * chunk, len(unknown), len(subnormal)])
-
-
-def check_skip_cases(result, counts, values, rows, offsets, count, chunk):
-    """result, counts: mode='sum', missing='skip' of skip_cases; values: the entries' rows."""
-    want, want_counts = chunked_by_the_contract(values, rows, offsets, count, 'sum', True, chunk)
-    assert bits_equal(result, want) and np.array_equal(counts, want_counts)
-    assert counts[0] == 1 + chunk and counts[1] == 0 and counts[2] == 3 * chunk + 1
-    last = in_order(values[2 * chunk:3 * chunk])   # the last chunk's sum: -0.0 where rows 0, 1 and 2 all are
-    negative_zero = (last == 0) & np.signbit(last)
-    assert negative_zero[:30].all() and not negative_zero.all()
-    # -0.0 (the first chunk) + nothing (the middle one) + last = last, -0.0 included; a +0.0 from the middle chunk or from
-    # the first chunk's unknown entries would have turned those columns into +0.0
-    assert bits_equal(result[0], last)
-    assert not result[1].any() and not np.signbit(result[1]).any()   # no known entry: +0.0
-    assert (result[2] != 0).any() and (np.abs(result[2]) < 1.1754944e-38).all()   # subnormal partial sums are kept
 
 
 def test_skipped_chunks_add_nothing(native, tmp_path):
@@ -240,22 +193,6 @@ def test_the_batch_edges_of_pool_chunks_on_the_host(native, reader, tmp_path):
         holes = signed_zero_rows(with_unknown_chunks(rows, offsets, chunk, which))
         check_negative_zeros_survive(signed, holes, offsets, chunk)
         host_check(signed, holes, offsets, chunk, ('signed zeros', which), modes=('sum',))
-
-
-def signed_zero_rows(rows):
-    """The known entries of `rows` as rows 0, 1 and 2 of signed_zero_model, whose first 30 columns are -0.0."""
-    return np.where(rows == UNKNOWN, rows, rows % np.uint32(3)).astype(np.uint32)
-
-
-def check_negative_zeros_survive(signed, holes, offsets, chunk):
-    """(a reader of signed_zero_model, a batch of signed_zero_rows) by the contract, the first 30 columns of every bag with a
-    known entry are -0.0, whichever chunks are unknown: one +0.0 added for an unknown chunk or entry would make them +0.0,
-    and the reference would notice. Returns the contract's (sums, counts) with missing='skip'."""
-    want, counts = chunked_by_the_contract(signed.rows_embedding(holes), holes, offsets, len(signed), 'sum', True, chunk)
-    filled = counts > 0
-    assert not want[:, :30].any() and np.signbit(want[filled, :30]).all() and not np.signbit(want[~filled]).any()
-    assert not filled.any() or (want[filled, 50:] != 0).any()
-    return want, counts
 
 
 @pytest.mark.parametrize('storage,bits', COLUMN_STORAGES)

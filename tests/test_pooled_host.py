@@ -1,32 +1,10 @@
 """bags_embedding on a device='cpu' reader: the contract of include/memb_hip_pooled.h executed without a GPU, bit for bit
-against an explicit loop over reader.rows_embedding(rows) -- a second, independent statement of that contract."""
+against the contract's explicit loop (tests/pooled_reference.py) over reader.rows_embedding(rows)."""
 import numpy as np
 import pytest
 
 from conftest import bits_equal
-
-
-def pooled_by_the_contract(values, offsets, mode):
-    """values: the fp32 rows of the entries. acc = v_begin, then acc = acc + v_i in entry order, one float32 addition
-    each; 'mean': one float32 division by float32(count); an empty bag is +0.0"""
-    n, dim = values.shape
-    bags = len(offsets) - 1
-    out = np.zeros((bags, dim), dtype=np.float32)
-    for bag in range(bags):
-        begin, end = min(int(offsets[bag]), n), min(int(offsets[bag + 1]), n)
-        if end <= begin:
-            continue
-        acc = values[begin].copy()
-        for i in range(begin + 1, end):
-            acc = np.add(acc, values[i], dtype=np.float32)
-        if mode == 'mean':
-            acc = np.divide(acc, np.float32(end - begin), dtype=np.float32)
-        out[bag] = acc
-    return out
-
-
-def offsets_of(lengths):
-    return np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+from pooled_reference import offsets_of, pooled_by_the_contract
 
 
 def mixed_bags(count, seed):

@@ -11,10 +11,10 @@ import numpy as np
 import pytest
 
 from conftest import REPO, bits_equal
+from pooled_reference import UNKNOWN, compacted, offsets_of, sequential_by_the_contract
 
 HEADER = os.path.join(REPO, 'include', 'memb_hip_pooled_known.h')
 POOLED_HEADER = os.path.join(REPO, 'include', 'memb_hip_pooled.h')
-UNKNOWN = 0xFFFFFFFF
 
 
 def test_header_is_plain_c_and_cxx_and_leaves_the_pooled_header_alone():
@@ -56,38 +56,12 @@ def test_entry_point_is_exported_and_refuses_bad_arguments(native):
         assert parameters['missing'].default == 'zero' and parameters['return_counts'].default is False
 
 
-def known_by_the_contract(values, rows, offsets, n_rows, mode):
-    """R1. K = the bag's entries with rows[i] < n_rows, in entry order: acc = v_K[0], acc = acc + v_K[j], one float32
-    addition each; 'mean': one float32 division by float32(|K|); +0.0 where K is empty. Returns (vectors, counts)."""
-    bags = len(offsets) - 1
-    out = np.zeros((bags, values.shape[1]), dtype=np.float32)
-    counts = np.zeros(bags, dtype=np.uint32)
-    for bag in range(bags):
-        known = [i for i in range(int(offsets[bag]), int(offsets[bag + 1])) if rows[i] < n_rows]
-        counts[bag] = len(known)
-        if not known:
-            continue
-        acc = values[known[0]].copy()
-        for i in known[1:]:
-            acc = np.add(acc, values[i], dtype=np.float32)
-        if mode == 'mean':
-            acc = np.divide(acc, np.float32(len(known)), dtype=np.float32)
-        out[bag] = acc
-    return out, counts
-
-
-def compacted(rows, offsets, n_rows):
-    keep = rows < n_rows
-    before = np.concatenate([[0], np.cumsum(keep)])
-    return rows[keep], before[np.asarray(offsets, dtype=np.int64)]
-
-
 def check_host(reader, rows, offsets, context):
     n_rows = len(reader)
     values = reader.rows_embedding(rows) if len(rows) else np.zeros((0, reader.dim), dtype=np.float32)
-    dense_rows, dense_offsets = compacted(rows, offsets, n_rows)
+    dense_rows, dense_offsets, _ = compacted(rows, offsets, n_rows)
     for mode in ('sum', 'mean'):
-        want, want_counts = known_by_the_contract(values, rows, offsets, n_rows, mode)
+        want, want_counts = sequential_by_the_contract(values, rows, offsets, n_rows, mode, True)
         got, counts = reader.bags_embedding(rows, offsets, mode=mode, missing='skip', return_counts=True)
         assert got.dtype == np.float32 and counts.dtype == np.uint32 and counts.shape == (len(offsets) - 1,)
         assert bits_equal(got, want), (context, mode, 'R1')
@@ -95,10 +69,6 @@ def check_host(reader, rows, offsets, context):
         assert bits_equal(got, reader.bags_embedding(dense_rows, dense_offsets, mode=mode)), (context, mode, 'R2')
         assert bits_equal(reader.bags_embedding(rows, offsets, mode=mode, missing='skip'), want)
         assert bits_equal(reader.bags_embedding(rows, offsets, mode=mode, missing='zero'), reader.bags_embedding(rows, offsets, mode=mode))
-
-
-def offsets_of(lengths):
-    return np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
 
 
 def rows_with_unknowns(count, n_rows, seed):

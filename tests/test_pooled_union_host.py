@@ -5,28 +5,9 @@ import numpy as np
 import pytest
 
 from conftest import bits_equal
-from test_gpu_pooled import ids_with_misses, offsets_of, pooled_by_the_contract
+from pooled_reference import merged_rows, offsets_of, pooled_by_the_contract, union_ids
 
 N_ROWS = 3000
-
-
-def merged_rows(mode, pieces):
-    """The union's rows by the explicit order: (((v1 + v2) + v3) ..) / R, or the readers' rows side by side"""
-    if mode == 'concatenate':
-        return np.hstack(pieces)
-    total = pieces[0]
-    for piece in pieces[1:]:
-        total = np.add(total, piece, dtype=np.float32)
-    return np.divide(total, np.float32(len(pieces)), dtype=np.float32)
-
-
-def union_ids(count, readers, seed):
-    """Row ids drawn independently per reader -- missing in one, the other, both or neither -- with a stretch of entries
-    that no reader has"""
-    rows = [ids_with_misses(count, N_ROWS, seed + 100 * position) for position in range(readers)]
-    for ids in rows:
-        ids[count // 2:count // 2 + 9] = 0xFFFFFFFF
-    return rows
 
 
 @pytest.fixture(scope='module')
@@ -45,7 +26,7 @@ def test_host_union_pools_by_the_contract(native, host_readers, monkeypatch, uni
     readers = host_readers if union_mode == 'concatenate' else host_readers[:2]
     union = native.ReadersUnion(readers, union_mode)
     lengths = [0, 0, 5, 1, 0, 12, 100, 0, 3, 64, 41, 0, 9, 0]
-    rows = union_ids(sum(lengths), len(readers), 3)
+    rows = union_ids(sum(lengths), len(readers), 3, N_ROWS)
     values = merged_rows(union_mode, [reader.rows_embedding(ids) for reader, ids in zip(readers, rows)])
     for mode in ('sum', 'mean'):
         got = union.pooled_rows(rows, offsets_of(lengths), mode=mode)
@@ -61,14 +42,14 @@ def test_three_host_readers_average_in_reader_order(native, make_model):
     readers = [native.Reader(make_model(N_ROWS, 300, 'trained', 4, seed=20 + position)[0], device='cpu') for position in range(3)]
     union = native.ReadersUnion(readers, 'average')
     lengths = np.random.default_rng(5).geometric(1 / 6.0, size=60)
-    rows = union_ids(int(lengths.sum()), 3, 9)
+    rows = union_ids(int(lengths.sum()), 3, 9, N_ROWS)
     values = merged_rows('average', [reader.rows_embedding(ids) for reader, ids in zip(readers, rows)])
     assert bits_equal(union.pooled_rows(rows, offsets_of(lengths), mode='mean'), pooled_by_the_contract(values, offsets_of(lengths), 'mean'))
 
 
 def test_argument_checks(native, host_readers):
     union = native.ReadersUnion(host_readers[:2], 'average')
-    rows = union_ids(20, 2, 1)
+    rows = union_ids(20, 2, 1, N_ROWS)
     with pytest.raises(ValueError, match='sum'):
         union.pooled_rows(rows, [0, 20], mode='max')
     with pytest.raises(ValueError, match='one row-id array per reader'):
