@@ -7,6 +7,7 @@
 Everything is built next to its sources so the binaries travel with the tree.
 `python build_native.py` builds whatever is out of date (`--force`: everything).
 """
+import glob
 import os
 import shutil
 import subprocess
@@ -53,13 +54,10 @@ def _hipcc():
 
 
 def build_hip_library(force=False, extra_flags=()):
-    sources = [os.path.join(CSRC, name) for name in
-               ('memb_hip.hip', 'memb_hip_narrow.hip', 'memb_hip_pooled.hip', 'memb_hip_pooled_chunked.hip',
-                'memb_hip_pooled_union.hip', 'hip_pooled_union.h', 'hip_pooled_chunked.h', 'hip_narrow.h', 'hip_pooled.h', 'hip_pooled_kernels.h', 'hip_device_common.h', 'hip_trained_kernels.h',
-                'hip_rowwise_kernels.h', 'hip_host_path.h', 'hip_encoder.h', 'hip_encoder_kernels.h', 'hip_words.h',
-                'hip_words_kernels.h', 'worker_pool.h', 'codec.h', 'wire.h')]
-    sources += [os.path.join(INCLUDE, name) for name in ('memb_hip.h', 'memb_hip_narrow.h', 'memb_hip_pooled.h', 'memb_hip_pooled_known.h',
-                                                        'memb_hip_pooled_chunked.h', 'memb_hip_pooled_union.h')]
+    # every translation unit and every section or device header of it: a new hip_*.h is a dependency as soon as it exists
+    sources = glob.glob(os.path.join(CSRC, '*.hip')) + glob.glob(os.path.join(CSRC, 'hip_*.h'))
+    sources += [os.path.join(CSRC, name) for name in ('worker_pool.h', 'codec.h', 'wire.h')]
+    sources += glob.glob(os.path.join(INCLUDE, '*.h'))
     if force or _newer(HIP_LIBRARY, sources):
         _run([
             _hipcc(), '--offload-arch=' + GPU_ARCH, '-O3', '-std=c++17', '-fPIC', '-shared',
@@ -79,8 +77,7 @@ def build_extension(force=False):
     sources = [os.path.join(CSRC, name) for name in names]
     headers = [os.path.join(CSRC, name) for name in
                ('reader.h', 'builder.h', 'compression_strategy.h', 'worker_pool.h', 'codec.h', 'wire.h')]
-    headers += [os.path.join(INCLUDE, name) for name in ('memb_hip.h', 'memb_hip_narrow.h', 'memb_hip_pooled.h', 'memb_hip_pooled_known.h',
-                                                        'memb_hip_pooled_chunked.h', 'memb_hip_pooled_union.h')]
+    headers += glob.glob(os.path.join(INCLUDE, '*.h'))
     build_hip_library(force)
     if force or _newer(EXTENSION, sources + headers + [HIP_LIBRARY]):
         _run([

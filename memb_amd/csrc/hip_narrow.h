@@ -1,4 +1,4 @@
-// The kernels of memb_hip_narrow.hip (bf16 / fp16 rows) as memb_hip.hip launches them (launchKernelAddress, launchRowwise):
+// The kernels of memb_hip_narrow.hip (bf16 / fp16 rows) as memb_hip.hip launches them (hip_kernel_table.h: launchKernelAddress; hip_decode_launch.h: launchRowwise):
 // host addresses for hipLaunchKernel / hipFuncGetAttributes. Their parameters are the TrainedParams / UniformParams / FullParams of the device
 // headers, which both translation units include.
 #pragma once

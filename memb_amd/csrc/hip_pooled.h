@@ -1,5 +1,5 @@
 // The kernels of memb_hip_pooled.hip (sum / mean of each bag of rows -- include/memb_hip_pooled.h -- or of a bag's KNOWN
-// rows -- include/memb_hip_pooled_known.h -- as fp32, bf16 or fp16 elements) as memb_hip.hip launches them (launchPooled):
+// rows -- include/memb_hip_pooled_known.h -- as fp32, bf16 or fp16 elements) as memb_hip.hip launches them (hip_pooled_launch.h: launchPooled):
 // host addresses for hipLaunchKernel / hipFuncGetAttributes. Their first parameter is the TrainedParams / UniformParams /
 // FullParams of the device headers, which both translation units include -- rows[0 .. n) are the ENTRIES, out / ld /
 // colOff describe the bags' rows -- their second the PoolParams below, the third of the known kernels the KnownParams.

@@ -1,5 +1,5 @@
 // The kernels of memb_hip_pooled_chunked.hip (pooled lookups under the chunked order: include/memb_hip_pooled_chunked.h) as
-// memb_hip.hip launches them: host addresses for hipLaunchKernel, their parameters, and the caller's workspace as both
+// memb_hip.hip launches them (hip_pooled_launch.h: pool_rows_chunked_checked): host addresses for hipLaunchKernel, their parameters, and the caller's workspace as both
 // sides lay it out. Three stages on one stream:
 //   (a) the chunk plan    chunk_block_sums -> chunk_scan_sums -> chunk_bag_starts -> chunk_offsets (ChunkPlanParams)
 //   (b) partial sums      launchPooled, MEMB_HIP_POOL_SUM over the derived offsets into the workspace: the kernels of

@@ -1,5 +1,5 @@
 // The kernels of memb_hip_pooled_union.hip (include/memb_hip_pooled_union.h: the sum or mean of each bag of a ReadersUnion's
-// AVERAGED rows, and of each bag of rows of a dense fp32 matrix) as memb_hip.hip launches them (launchPooledUnion,
+// AVERAGED rows, and of each bag of rows of a dense fp32 matrix) as memb_hip.hip launches them (hip_pooled_launch.h: launchPooledUnion,
 // launchPooledDense): host addresses for hipLaunchKernel / hipFuncGetAttributes, in the style of hip_pooled.h. The first
 // parameter of the union kernels is the UnionParams of hip_trained_kernels.h, which both translation units include -- every
 // model's rows[0 .. n) are the ENTRIES, model 0's out / ld / colOff describe the bags' rows --, that of the dense kernels

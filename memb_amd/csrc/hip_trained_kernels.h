@@ -92,7 +92,7 @@ __device__ __forceinline__ u32x4 loadPiece(const u32x4* source)
 // OUT_KEYS: no codebook gather -- `out` receives the symbol tile itself, dense rows of
 // keyRowBytes (one centroid index per byte, or per nibble when FAST), for the host-buffer
 // entry point: PCIe then carries 1/4 or 1/8 of the bytes and the host threads that copy rows
-// out of pinned memory anyway expand them (memb_hip.hip: expandKeyRows).
+// out of pinned memory anyway expand them (hip_host_path.h: expandKeyRows).
 enum OutputMode { OUT_SCALAR = 0, OUT_VEC4 = 1, OUT_FLAT = 2, OUT_INDEX = 3, OUT_KEYS = 4 };
 
 
@@ -211,7 +211,7 @@ __device__ __forceinline__ void unpackMeta(const TrainedParams& p, const LaneRol
 // Scalar registers the one-tile kernels may use (0 = no limit). The hardware admits wavefronts by scalar registers as well
 // as vector ones -- 800 per SIMD, .sgpr_count (this budget minus 2: VCC and friends are counted in) rounded up to 16, plus
 // 16 -- and without a limit the compiler takes 106 for these kernels: six wavefronts per SIMD where 61 vector registers
-// allow eight. 96 -> seven (memb_hip.hip: ONE_TILE_WAVES_PER_CU; HISTORY.md, "(r5) 5.0", has the measurements of 80, 88 and none).
+// allow eight. 96 -> seven (hip_decode_plan.h: ONE_TILE_WAVES_PER_CU; HISTORY.md, "(r5) 5.0", has the measurements of 80, 88 and none).
 #ifndef MEMB_HIP_SGPRS
 #define MEMB_HIP_SGPRS 96
 #endif
@@ -768,7 +768,7 @@ __device__ __forceinline__ TrainedParams batchOfTile(const TrainedParams& p, con
 // What order do the rows of this batch come in? Sixty-four pairs of neighbouring row ids, spread over the batch, looked at by
 // the first wavefront of the grid: 1 = at least three quarters of the pairs are consecutive rows (a key-order dump, or runs of
 // one), 0 = not. The answer goes to pinned host memory, where the NEXT launch of a very large batch reads it when it picks
-// its block size (memb_hip.hip: launchTrained) -- key-order dumps and shuffled batches want different ones, the caller of
+// its block size (hip_decode_launch.h: launchTrained) -- key-order dumps and shuffled batches want different ones, the caller of
 // the reference's API (src/reader.cpp:49-57) has no way to say which it brings, and the batches of one caller tend to look
 // like the batch before. A hint to the launch geometry, never to the result; two launches of one context on two streams
 // may both write it (a plain store of 0 or 1).
@@ -906,7 +906,7 @@ __global__ MEMB_SGPR_BUDGET void decode_trained_batches(TrainedParams p, BatchLi
 // ---------------------------------------------------------------------------
 // decode_records_persistent: a software pipeline for batches of more than one and up to four tiles per resident wavefront
 // ---------------------------------------------------------------------------
-// The one kernel besides decode_trained that a single model runs (memb_hip.hip: planTrained): batches of 57 000 to
+// The one kernel besides decode_trained that a single model runs (hip_decode_plan.h: planTrained): batches of 57 000 to
 // 131 000 words on 256 CUs -- BASELINE.json configs[1] -- where every wavefront has two or three tiles and a
 // wavefront with one tile spends its life in the three dependent hops row id -> row region -> decode. Row-record
 // layout only (TrainedParams::recordPieces): a row's address is arithmetic and its segment offsets arrive with its

@@ -476,7 +476,7 @@ int resolve_rows_device_checked(memb_hip_ctx* ctx, const memb_hip_words* batch, 
     return resolve_range_device_checked(ctx, batch, 0, batch->count, rows, stream);
 }
 
-// for decode_rows_checked (memb_hip.hip), which sits above this header: the context's mutex is held, its device current
+// for decode_rows_checked (hip_entry_points.h, included after this header): the context's mutex is held, its device current
 int resolveBatchOnContextStream(memb_hip_ctx* ctx, const memb_hip_words* batch, uint32_t* rowsDevice)
 {
     if (!batch->committed) {

@@ -409,7 +409,7 @@ static_assert(MEMB_HIP_OUT_F32 == 0 && MEMB_HIP_OUT_BF16 == 1 && MEMB_HIP_OUT_F1
 
 // Every instance of one family (KNOWN: the kernels that skip missing rows), indexed [HAS_SUB][FAST][VEC4][out type]
 // (trained) and [out type]. Key forms <HAS_SUB, FAST>: <false, true> nibble keys, <false, false> and <true, false> byte
-// keys (memb_hip.hip: KernelTable).
+// keys (hip_kernel_table.h: KernelTable).
 template <bool KNOWN>
 struct PoolTable {
     const void* trained[2][2][2][OUT_TYPES] = {};

@@ -233,7 +233,7 @@ struct Instance {
 };
 
 // Every instance, indexed [HAS_SUB][FAST][COUNT][out type] and [out type]. Key forms <HAS_SUB, FAST>: <false, true> nibble
-// keys in every model, <false, false> and <true, false> byte keys (memb_hip.hip: KernelTable).
+// keys in every model, <false, false> and <true, false> byte keys (hip_kernel_table.h: KernelTable).
 struct UnionPoolTable {
     Instance trained[2][2][UNION_MAX_MODELS + 1][OUT_TYPES];
     Instance dense[OUT_TYPES];

@@ -70,11 +70,11 @@ def test_full_vocabulary_dump(native, full_model):
     assert torch.equal(plain.view(torch.int32), out[everything.long()].view(torch.int32))
 
 
-ONE_TILE_WAVES_PER_CU = 28   # memb_hip.hip: what the scalar registers of decode_trained admit (tests/test_isa.py pins it)
+ONE_TILE_WAVES_PER_CU = 28   # hip_decode_plan.h: what the scalar registers of decode_trained admit (tests/test_isa.py pins it)
 
 
 def expected_kernel_class(words, words_per_tile, fine_words_per_tile, cus):
-    """The kernel a dense batch of `words` words runs with default options (memb_hip.hip planTrained, chooseGeometry;
+    """The kernel a dense batch of `words` words runs with default options (hip_decode_plan.h planTrained, chooseGeometry;
     DESIGN.md section 5.0 "which kernel owns which configuration") for a row-record model of dim 300 whose tables leave
     every block size the residency the registers allow -- the 2-, 4- and 6-bit models, nibble or byte keys. R = 16
     wavefronts per CU x CUs, one round = 28 x CUs tiles: decode_records_persistent for one round < tiles <= 4 R, else

@@ -1,4 +1,4 @@
-"""The bf16 / fp16 kernels (memb_hip_narrow.hip; outputTileNarrow; memb_hip.hip: launchTrained, launchUniform, launchFull) over the
+"""The bf16 / fp16 kernels (memb_hip_narrow.hip; outputTileNarrow; hip_decode_launch.h: launchTrained, launchUniform, launchFull) over the
 geometry the fp32 path is walked through in test_gpu_parity.py: lanes per word and block sizes, the finer index forced on
 and off, key forms and table widths, row layouts, the batch-size edges of the plan, very wide rows, arbitrary prefix
 codes, degenerate models, a seeded sweep, threads on streams of their own.
@@ -57,7 +57,7 @@ def expected_of(checker, rows):
 
 
 def narrow_output_mode(dim, ld, col_off, pointer, words_per_wave):
-    """memb_hip.hip: outputMode for 2-byte elements, restated"""
+    """hip_decode_plan.h: outputMode for 2-byte elements, restated"""
     if dim % 4 or ld % 4 or col_off % 4 or pointer % 8:
         return OUT_SCALAR
     dense = ld == dim and col_off == 0 and pointer % 16 == 0
@@ -297,7 +297,7 @@ def test_batch_size_edges_of_the_narrow_plan(native, make_model, bits):
     usual, fine = reader.info(), reader.info(1)
     usual_words, fine_words = WAVE // usual['lanes_per_word'], WAVE // fine['lanes_per_word']
     assert fine_words < usual_words
-    codebook_bytes = 2048 if key_form(reader)[1] else 1024   # memb_hip.hip: codebookDwords
+    codebook_bytes = 2048 if key_form(reader)[1] else 1024   # hip_decode_plan.h: codebookDwords
 
     def one_round(info, saved):
         # test_gpu_parity.py::test_small_batches_decode_with_the_finer_index; `saved`: what half a codebook leaves out

@@ -170,7 +170,7 @@ def test_host_copy_ring_chunks_threads_and_slices(native, make_model, monkeypatc
 
 def test_host_batches_cross_pcie_as_centroid_indices(native, make_model, monkeypatch):
     # trained storage + host buffers: the kernel writes rows of centroid indices, the host threads
-    # that empty the pinned ring expand them (memb_hip.hip: decodeRowsAsKeys). Same bits as the
+    # that empty the pinned ring expand them (hip_host_path.h: decodeRowsAsKeys). Same bits as the
     # fp32 path (option host_expand = 0) and as the checker, for nibble and byte keys, odd
     # dimensions, tile geometries whose key tiles are not dword multiples, absent rows.
     for dim, bits, lanes in ((300, 4, 8), (300, 8, 8), (7, 2, 1), (301, 4, 5), (33, 6, 3), (150, 4, 64), (2, 4, 1)):
@@ -715,7 +715,7 @@ def test_device_resident_lookup_matches_host_path(native, make_model):
 
 
 def test_large_tables_take_two_tiles_per_wavefront_by_default(native, make_model):
-    """The one rule of memb_hip.hip's oneTileSteps that no BASELINE model reaches: a model whose table and codebook are 16 KiB
+    """The one rule of hip_decode_plan.h's oneTileSteps that no BASELINE model reaches: a model whose table and codebook are 16 KiB
     and more (8-bit: a 13-bit first level) decodes two tiles per wavefront behind one copy once the batch has two tiles
     per resident wavefront slot -- DEFAULT options, against the checker."""
     import torch
@@ -1174,7 +1174,7 @@ def test_uniform_tile_kernel(native, make_model):
 
 @pytest.mark.parametrize('bits,dim', [(4, 300), (2, 300), (6, 300), (8, 300), (4, 128), (6, 100), (4, 52), (4, 1024), (4, 20)])
 def test_small_batches_decode_with_the_finer_index(native, make_model, bits, dim):
-    """Row-record models carry a second, finer segment index (about sixteen lanes per word; memb_hip.hip: stageIndex,
+    """Row-record models carry a second, finer segment index (about sixteen lanes per word; hip_staging.h: stageIndex; hip_decode_plan.h:
     planTrained): batches whose tiles under it fit the CUs at once run decode_trained with it. Same rows as the
     checker with the index forced on (2), off (1) and by rule (0), for batch sizes on both sides of a tile and of the
     rule's edge, misses included. Reference: src/huffman_table_decoder.h:102-118 (the serial chain being split)."""
@@ -1192,7 +1192,7 @@ def test_small_batches_decode_with_the_finer_index(native, make_model, bits, dim
     cus = torch.cuda.get_device_properties(0).multi_processor_count
 
     def round_of(info):
-        # tiles resident at once: per CU what the registers admit (28: memb_hip.hip ONE_TILE_WAVES_PER_CU) or what LDS --
+        # tiles resident at once: per CU what the registers admit (28: hip_decode_plan.h ONE_TILE_WAVES_PER_CU) or what LDS --
         # 160 KiB handed out per block in steps of 1 KiB -- leaves of it (the 8-bit model's tables, dim 1024's slots)
         waves, lds = info['waves_per_block'], info['lds_bytes_per_block']
         return cus * waves * min(160 * 1024 // ((lds + 1023) // 1024 * 1024), max(1, 28 // waves))

@@ -1,4 +1,4 @@
-"""Pooled lookups on the GPU (memb_hip_pooled.hip: pool_trained, pool_uniform, pool_full; memb_hip.hip: launchPooled).
+"""Pooled lookups on the GPU (memb_hip_pooled.hip: pool_trained, pool_uniform, pool_full; hip_pooled_launch.h: launchPooled).
 
 The oracle everywhere: the reader's own fp32 rows from rows_embedding_device -- which test_gpu_parity.py pins bit for bit
 to the CPU checker -- copied to the host and pooled by the explicit float32 loop of the contract

@@ -1,5 +1,5 @@
 """reduction='chunked' on the GPU over the plan sizes, batch edges, column blocks and launch geometries that
-tests/test_gpu_pooled_chunked.py does not reach (memb_hip_pooled_chunked.hip, pool_rows_chunked_checked in memb_hip.hip):
+tests/test_gpu_pooled_chunked.py does not reach (memb_hip_pooled_chunked.hip, pool_rows_chunked_checked in hip_pooled_launch.h):
 
   A  the plan: bag counts on every edge of a thread's 8 bags and of a block's 2048, and more than 256 blocks -- the second
      round of chunk_scan_sums;

@@ -1,5 +1,5 @@
 """Pooled lookups straight into bf16 / fp16 tensors (memb_hip_pooled_narrow.hip: pool_trained_narrow, pool_uniform_narrow,
-pool_full_narrow; memb_hip.hip: launchPooled with a narrow outType).
+pool_full_narrow; hip_pooled_launch.h: launchPooled with a narrow outType).
 
 The contract (include/memb_hip_pooled.h): a narrow value is the float32 pooled value rounded ONCE to nearest even. Two
 oracles, which must agree with each other before the device is asked:

@@ -1,4 +1,4 @@
-"""Pooled lookups of a ReadersUnion on the GPU (memb_hip_pooled_union.hip: pool_trained_union, pool_dense; memb_hip.hip:
+"""Pooled lookups of a ReadersUnion on the GPU (memb_hip_pooled_union.hip: pool_trained_union, pool_dense; hip_pooled_launch.h:
 launchPooledUnion, launchPooledDense; readers_union.py: pooled_rows_device, pooled_sentences_device, pooled_rows).
 
 The oracle everywhere is built on the host: every reader's own fp32 rows from rows_embedding_device -- which

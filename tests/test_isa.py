@@ -42,7 +42,7 @@ def test_the_kernel_zoo_is_what_design_md_says(kernels):
     families = collections.Counter(name.split('(anonymous namespace)::')[1].split('<')[0].split('(')[0] for name in kernels)
     # round 5: decode_trained_batches (decode_trained's body over the tiles of several batches), and word -> row on the
     # device: build_word_table at staging, resolve_words per batch.
-    # Instances per family (memb_hip.hip: KernelTable): three key forms x five output modes (decode_trained), x three
+    # Instances per family (hip_kernel_table.h: KernelTable): three key forms x five output modes (decode_trained), x three
     # (decode_trained_batches), x four (decode_records_persistent, no index pass); unions three key forms x COUNT 2..4 x
     # AVERAGE, split pairs three key forms x AVERAGE plus the two COMPACT nibble-key forms.
     assert families == {
@@ -84,7 +84,7 @@ def test_kernels_that_live_on_occupancy_keep_their_registers(kernels):
     # eight per SIMD (<= 64; MI355X_MICROARCH.md, register files), but the hardware hands out scalar registers too (800 per
     # SIMD, .sgpr_count rounded up to 16, plus 16: "Residency and cooperative launch"): rounds 1-4 shipped these kernels
     # with 106 of them -- SIX wavefronts per SIMD where the compiler's own occupancy line said eight. hip_trained_kernels.h
-    # holds them to a budget now (MEMB_HIP_SGPRS): SEVEN per SIMD, 28 per CU -- memb_hip.hip ONE_TILE_WAVES_PER_CU, which
+    # holds them to a budget now (MEMB_HIP_SGPRS): SEVEN per SIMD, 28 per CU -- hip_decode_plan.h ONE_TILE_WAVES_PER_CU, which
     # the kernel-by-batch-size rule counts rounds with.
     import isa
     for name, facts in kernels.items():

@@ -83,7 +83,7 @@ def test_dense_rows_leave_in_16_byte_stores(kernels):
 
 @needs_hipcc
 def test_narrow_kernels_keep_the_one_tile_residency(kernels):
-    # memb_hip.hip plans decode_trained_narrow with ONE_TILE_WAVES_PER_CU = 28, as decode_trained: seven per SIMD
+    # hip_decode_plan.h plans decode_trained_narrow with ONE_TILE_WAVES_PER_CU = 28, as decode_trained: seven per SIMD
     import isa
     for name, facts in kernels.items():
         if 'decode_trained_narrow<' in name:

@@ -1,4 +1,4 @@
-"""The argument check every pooled entry point of libmemb_hip.so shares (memb_hip.hip: PooledCall::check), through the C ABI
+"""The argument check every pooled entry point of libmemb_hip.so shares (hip_pooled_launch.h: PooledCall::check), through the C ABI
 without compute, in test_cabi.py's style: one argument per call is made wrong, and every entry point must refuse it with
 MEMB_HIP_ERR_INVALID and the same memb_hip_last_error() text; two mistakes at once show which check comes first. The texts
 are those of the entry points as they were written one by one, before they shared the check. No context is dereferenced

@@ -144,7 +144,7 @@ def test_every_accumulator_add_is_a_single_lane_op(code, family):
 
 @needs_hipcc
 def test_trained_pooled_kernels_keep_the_one_tile_residency_and_their_store_widths(kernels, family):
-    # memb_hip.hip plans every trained kernel like decode_trained, with ONE_TILE_WAVES_PER_CU = 28: seven wavefronts per SIMD
+    # hip_decode_plan.h plans every trained kernel like decode_trained, with ONE_TILE_WAVES_PER_CU = 28: seven wavefronts per SIMD
     # was planned for (eight accumulator registers on top of the decode's), and seven is what the compiler gave.
     # fp32: the piece form leaves as 16-byte stores. bf16 / fp16: as 8-byte stores of four elements, and the column form --
     # any alignment -- as single elements only.
