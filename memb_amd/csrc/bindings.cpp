@@ -8,6 +8,7 @@
 #include "compression_strategy.h"
 #include "codec.h"
 #include "../../include/memb_hip_pooled_union.h"
+#include "../../include/memb_hip_norms.h"
 
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -1026,7 +1027,74 @@ PYBIND11_MODULE(_memb, m) {
             },
             py::arg("rows"),
             py::arg("offsets"),
-            py::arg("out_type") = MEMB_HIP_OUT_F32);
+            py::arg("out_type") = MEMB_HIP_OUT_F32)
+        // include/memb_hip_norms.h. Device pointers. False where the fused kernel does not exist for this model
+        // (MEMB_HIP_UNSUPPORTED): the caller decodes the rows and calls dense_row_norms_to_device.
+        .def(
+            "row_norms_to_device",
+            [](memb::Reader& reader, uintptr_t rows, size_t n, uintptr_t norms, uintptr_t stream)
+            {
+                const int code = memb_hip_row_norms_device(
+                    reader.deviceContext(), reinterpret_cast<const uint32_t*>(rows), n, reinterpret_cast<float*>(norms),
+                    reinterpret_cast<void*>(stream));
+                if (code == MEMB_HIP_UNSUPPORTED) {
+                    return false;
+                }
+                if (code != MEMB_HIP_OK) {
+                    throw std::runtime_error(std::string("memb_hip_row_norms_device: ") + memb_hip_last_error());
+                }
+                return true;
+            },
+            py::arg("rows_ptr"),
+            py::arg("n"),
+            py::arg("norms_ptr"),
+            py::arg("stream") = 0)
+        .def(
+            "unit_rows_to_device",
+            [](memb::Reader& reader, uintptr_t rows, size_t n, uintptr_t out, size_t ld, size_t colOff, uintptr_t norms,
+               uintptr_t stream)
+            {
+                if (memb_hip_decode_unit_rows_device(
+                        reader.deviceContext(), reinterpret_cast<const uint32_t*>(rows), n, reinterpret_cast<float*>(out), ld,
+                        colOff, reinterpret_cast<float*>(norms), reinterpret_cast<void*>(stream)) != MEMB_HIP_OK) {
+                    throw std::runtime_error(std::string("memb_hip_decode_unit_rows_device: ") + memb_hip_last_error());
+                }
+            },
+            py::arg("rows_ptr"),
+            py::arg("n"),
+            py::arg("out_ptr"),
+            py::arg("ld"),
+            py::arg("col_off") = 0,
+            py::arg("norms_ptr") = 0,
+            py::arg("stream") = 0)
+        // the kernel family row_norms_to_device (unit_rows false) or unit_rows_to_device launches for this output
+        .def(
+            "norms_kernel_name",
+            [](memb::Reader& reader, bool unitRows, uintptr_t out, size_t ld, size_t colOff)
+            {
+                return std::string(memb_hip_norms_kernel_name(
+                    reader.deviceContext(), unitRows ? 1 : 0, reinterpret_cast<const void*>(out), ld, colOff));
+            },
+            py::arg("unit_rows"),
+            py::arg("out_ptr") = 0,
+            py::arg("ld") = 0,
+            py::arg("col_off") = 0)
+        .def(
+            "norms_algorithmic_bytes",
+            [](memb::Reader& reader, py::array_t<uint32_t, py::array::c_style | py::array::forcecast> rows, bool unitRows,
+               bool norms)
+            {
+                uint64_t bytes = 0;
+                if (memb_hip_norms_algorithmic_bytes(
+                        reader.deviceContext(), rows.data(), static_cast<size_t>(rows.size()), unitRows ? 1 : 0, norms ? 1 : 0,
+                        &bytes) != MEMB_HIP_OK) {
+                    throw std::runtime_error(std::string("memb_hip_norms_algorithmic_bytes: ") + memb_hip_last_error());
+                }
+                return bytes;
+            },
+            py::arg("rows"),
+            py::arg("unit_rows") = false,
+            py::arg("norms") = true);
 
     m.attr("OUT_F32") = MEMB_HIP_OUT_F32;
     m.attr("OUT_BF16") = MEMB_HIP_OUT_BF16;
@@ -1187,6 +1255,50 @@ PYBIND11_MODULE(_memb, m) {
         py::arg("mode") = MEMB_HIP_POOL_MEAN,
         py::arg("stream") = 0,
         py::arg("out_type") = MEMB_HIP_OUT_F32);
+    // the norms (memb_hip_dense_row_norms_device) and the unit rows (memb_hip_dense_unit_rows_device) of n rows of a dense
+    // fp32 matrix on `device`. Device pointers.
+    m.def(
+        "dense_row_norms_to_device",
+        [](int device, uintptr_t values, size_t n, size_t dim, size_t ldValues, uintptr_t norms, uintptr_t stream)
+        {
+            if (memb_hip_dense_row_norms_device(
+                    device, reinterpret_cast<const float*>(values), n, dim, ldValues, reinterpret_cast<float*>(norms),
+                    reinterpret_cast<void*>(stream)) != MEMB_HIP_OK) {
+                throw std::runtime_error(std::string("memb_hip_dense_row_norms_device: ") + memb_hip_last_error());
+            }
+        },
+        py::arg("device"),
+        py::arg("values_ptr"),
+        py::arg("n"),
+        py::arg("dim"),
+        py::arg("ld_values"),
+        py::arg("norms_ptr"),
+        py::arg("stream") = 0);
+    m.def(
+        "dense_unit_rows_to_device",
+        [](int device, uintptr_t values, size_t n, size_t dim, size_t ldValues, uintptr_t out, size_t ld, size_t colOff,
+           uintptr_t norms, uintptr_t stream)
+        {
+            if (memb_hip_dense_unit_rows_device(
+                    device, reinterpret_cast<const float*>(values), n, dim, ldValues, reinterpret_cast<float*>(out), ld, colOff,
+                    reinterpret_cast<float*>(norms), reinterpret_cast<void*>(stream)) != MEMB_HIP_OK) {
+                throw std::runtime_error(std::string("memb_hip_dense_unit_rows_device: ") + memb_hip_last_error());
+            }
+        },
+        py::arg("device"),
+        py::arg("values_ptr"),
+        py::arg("n"),
+        py::arg("dim"),
+        py::arg("ld_values"),
+        py::arg("out_ptr"),
+        py::arg("ld"),
+        py::arg("col_off") = 0,
+        py::arg("norms_ptr") = 0,
+        py::arg("stream") = 0);
+    // the kernels those two launch
+    m.def("dense_norms_kernel_name", [](bool unitRows) {
+        return std::string(memb_hip_norms_kernel_name(nullptr, unitRows ? 1 : 0, nullptr, 0, 0));
+    });
     // one batch of words resolved by several readers of one device (ReadersUnion): packed and copied once
     m.def(
         "union_words_to_rows_device",

@@ -42,7 +42,8 @@
 // (hip_narrow.h), planned and launched here; memb_hip_pooled.hip -- every sequential pooled kernel (sum / mean
 // of each bag of rows or of its known rows, as fp32, bf16 or fp16), handed over the same way through one selector
 // (hip_pooled.h); memb_hip_pooled_chunked.hip -- the chunked order's (hip_pooled_chunked.h); memb_hip_pooled_union.hip -- the
-// pooled kernels of a ReadersUnion's averaged rows and of dense rows (hip_pooled_union.h).
+// pooled kernels of a ReadersUnion's averaged rows and of dense rows (hip_pooled_union.h); memb_hip_norms.hip -- row norms
+// and rows of unit length (hip_norms.h), launched by hip_norms_launch.h, which also holds their entry points.
 #include <hip/hip_runtime.h>
 
 #include "../../include/memb_hip.h"
@@ -51,11 +52,13 @@
 #include "../../include/memb_hip_pooled_known.h"
 #include "../../include/memb_hip_pooled_chunked.h"
 #include "../../include/memb_hip_pooled_union.h"
+#include "../../include/memb_hip_norms.h"
 #include "codec.h"
 #include "hip_narrow.h"
 #include "hip_pooled.h"
 #include "hip_pooled_chunked.h"
 #include "hip_pooled_union.h"
+#include "hip_norms.h"
 #include "wire.h"
 #include "worker_pool.h"
 
@@ -127,6 +130,7 @@ namespace {
 namespace {
 
 #include "hip_entry_points.h"
+#include "hip_norms_launch.h"
 
 // No C++ exception leaves the library: allocation failures and the like become error codes.
 template <typename Call>
@@ -322,6 +326,43 @@ int memb_hip_pooled_algorithmic_bytes_typed(
     const memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, int out_type, uint64_t* bytes)
 {
     return guarded([&] { return pooled_algorithmic_bytes_checked(ctx, rows, n, offsets, bags, out_type, bytes); });
+}
+
+int memb_hip_row_norms_device(memb_hip_ctx* ctx, const uint32_t* rows, size_t n, float* norms, void* stream)
+{
+    return guarded([&] { return row_norms_device_checked(ctx, rows, n, norms, stream); });
+}
+
+int memb_hip_decode_unit_rows_device(
+    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, float* out, size_t ld, size_t col_off, float* norms_or_null, void* stream)
+{
+    return guarded([&] { return decode_unit_rows_device_checked(ctx, rows, n, out, ld, col_off, norms_or_null, stream); });
+}
+
+int memb_hip_dense_row_norms_device(
+    int device, const float* values, size_t n, size_t dim, size_t ld_values, float* norms, void* stream)
+{
+    return guarded([&] { return dense_norms_device_checked(device, values, n, dim, ld_values, false, nullptr, 0, 0, norms, stream); });
+}
+
+int memb_hip_dense_unit_rows_device(
+    int device, const float* values, size_t n, size_t dim, size_t ld_values, float* out, size_t ld, size_t col_off,
+    float* norms_or_null, void* stream)
+{
+    return guarded([&] {
+        return dense_norms_device_checked(device, values, n, dim, ld_values, true, out, ld, col_off, norms_or_null, stream);
+    });
+}
+
+const char* memb_hip_norms_kernel_name(const memb_hip_ctx* ctx, int unit_rows, const void* out, size_t ld, size_t col_off)
+{
+    return norms_kernel_name(ctx, unit_rows != 0, out, ld, col_off);
+}
+
+int memb_hip_norms_algorithmic_bytes(
+    const memb_hip_ctx* ctx, const uint32_t* rows, size_t n, int unit_rows, int norms, uint64_t* bytes)
+{
+    return guarded([&] { return norms_algorithmic_bytes_checked(ctx, rows, n, unit_rows != 0, norms != 0, bytes); });
 }
 
 int memb_hip_decode_batches_device(memb_hip_ctx* ctx, const memb_hip_batch* batches, size_t count, void* stream)

@@ -277,6 +277,45 @@ def pool_slices_host(offsets, n, dim, slice_entries, mean, skip, slice_values):
     return out, known_counts
 
 
+NORMS_HOST_CHUNK = 1 << 16      # rows row_norms / unit_rows_embedding of a device='cpu' reader decode at a time
+NORMS_DEVICE_SLICE = 1 << 20    # rows row_norms_device decodes into a temporary at a time where no fused kernel exists
+UNIT_EPS = np.float32(1e-12)    # torch.nn.functional.normalize's eps
+
+
+def row_norms_host(values):
+    """The norm contract of include/memb_hip_norms.h in numpy: the float32 (n,) norms of the rows of a float32 (n, dim)
+    matrix, every product, sum and root one IEEE float32 operation in the kernels' order -- piece sums
+    ((v0 v0 + v1 v1) + v2 v2) + v3 v3 over columns 4k .. 4k + 3 (a column >= dim is +0.0), 64 lane partials over the pieces
+    l, l + 64, .., a butterfly of strides 1 .. 32, one square root."""
+    values = np.ascontiguousarray(values, dtype=np.float32)
+    n, dim = values.shape
+    pieces = -(-dim // 4)
+    padded = np.zeros((n, 4 * pieces), dtype=np.float32)
+    padded[:, :dim] = values
+    with np.errstate(over='ignore', under='ignore', invalid='ignore'):
+        squares = (padded * padded).reshape(n, pieces, 4)
+        sums = ((squares[:, :, 0] + squares[:, :, 1]) + squares[:, :, 2]) + squares[:, :, 3]
+        partial = np.zeros((n, 64), dtype=np.float32)
+        partial[:, :min(64, pieces)] = sums[:, :64]
+        for first in range(64, pieces, 64):
+            width = min(64, pieces - first)
+            partial[:, :width] = partial[:, :width] + sums[:, first:first + width]
+        lanes = np.arange(64)
+        for stride in (1, 2, 4, 8, 16, 32):
+            partial = partial + partial[:, lanes ^ stride]
+        return np.sqrt(partial[:, 0])
+
+
+def unit_rows_host(values, norms=None):
+    """values / max(norm, 1e-12) row by row, one float32 division per element (include/memb_hip_norms.h); norms:
+    row_norms_host(values) where the caller has them already."""
+    values = np.ascontiguousarray(values, dtype=np.float32)
+    if norms is None:
+        norms = row_norms_host(values)
+    with np.errstate(over='ignore', under='ignore', invalid='ignore'):
+        return values / np.where(norms < UNIT_EPS, UNIT_EPS, norms)[:, None]
+
+
 def tokenizer_word_list(tokenizer):
     """The words of a keras Tokenizer placed at their indices, '' where an index
     has no word (index 0 never has one). With `num_words` set only indices below
@@ -329,6 +368,7 @@ class Reader(BaseReader):
         if host_below is not None:
             self._impl.set_host_below(int(host_below))
         self._word_batches = WordBatches()   # of resolve_rows_device / resolve_packed_device: one per call in flight
+        self._last_norms_kernel = ''
 
     @property
     def _word_batch(self):
@@ -624,6 +664,118 @@ class Reader(BaseReader):
             out[filled] = out[filled] / counts[filled][:, None]
         if return_counts:
             return out, known_counts.astype(np.uint32)
+        return out
+
+    @property
+    def last_norms_kernel(self):
+        """The kernel family of the last row_norms_device / unit_rows_embedding_device call: 'norms_trained' /
+        'unit_trained' (fused with the decode), or 'norms_dense' / 'unit_dense' behind a plain decode of the rows -- uniform
+        and full storage, dims that are no multiple of 4 or beyond 512, unit rows whose output is not aligned to 16 bytes.
+        '' before any call. Informational: the bits are the same."""
+        return self._last_norms_kernel
+
+    def _norms_arguments(self, torch, rows):
+        """the checks row_norms_device and unit_rows_embedding_device share with rows_embedding_device"""
+        index = self._impl.device()
+        if index == _memb.HOST_DEVICE:
+            raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
+        device = rows.device
+        if device.type != 'cuda' or rows.dtype not in (torch.int32, torch.uint32) or not rows.is_contiguous():
+            raise TypeError('rows must be a contiguous int32/uint32 tensor on the GPU')
+        return index, device
+
+    def row_norms_device(self, rows, out=None):
+        '''The Euclidean norm of each row, left on the GPU: a float32 (n,) tensor. For trained models whose dim is a
+        multiple of 4 and at most 512 ONE kernel computes it from the compressed rows and writes no row; otherwise the
+        rows are decoded in slices of at most 2^20 into a temporary and reduced there (last_norms_kernel says which). Bit
+        for bit the contract of include/memb_hip_norms.h over rows_embedding_device(rows): float32 piece sums, a fixed
+        reduction tree, a correctly rounded root -- whichever kernel ran. A row that is not in the model has norm 0.
+        rows : torch.Tensor, as in rows_embedding_device
+        out : optional contiguous float32 (n,) tensor on the same device'''
+        import torch
+        index, device = self._norms_arguments(torch, rows)
+        n = rows.numel()
+        if out is None:
+            out = torch.empty((n,), dtype=torch.float32, device=device)
+        if out.dtype != torch.float32 or out.dim() != 1 or out.shape[0] != n or not out.is_contiguous():
+            raise TypeError('out must be a contiguous float32 (n,) tensor')
+        if device.index != index or out.device != device:
+            raise ValueError('rows and out must be on cuda:{} (the device this reader is staged on), got {} and {}'.format(
+                self.device, device, out.device))
+        stream = _current_stream(torch, index)
+        if self._impl.row_norms_to_device(rows.data_ptr(), n, out.data_ptr(), stream):
+            self._last_norms_kernel = self._impl.norms_kernel_name(False)
+            return out
+        flat = rows.reshape(-1)
+        dim = self.dim
+        temporary = torch.empty((min(n, NORMS_DEVICE_SLICE), dim), dtype=torch.float32, device=device)
+        for start in range(0, n, NORMS_DEVICE_SLICE):
+            stop = min(n, start + NORMS_DEVICE_SLICE)
+            decoded = self.rows_embedding_device(flat[start:stop], out=temporary[:stop - start])
+            _memb.dense_row_norms_to_device(index, decoded.data_ptr(), stop - start, dim, dim, out[start:stop].data_ptr(), stream)
+        self._last_norms_kernel = _memb.dense_norms_kernel_name(False)
+        return out
+
+    def unit_rows_embedding_device(self, rows, out=None, col_off=0, return_norms=False):
+        '''rows_embedding_device with every row divided by max(its norm, 1e-12) -- torch.nn.functional.normalize's
+        definition -- in the kernel that decodes it where row_norms_device's fused form exists and every row of `out` is
+        aligned to 16 bytes; otherwise the plain decode into `out` and a second kernel in place (last_norms_kernel says
+        which): no temporary either way. Bit for bit the contract of include/memb_hip_norms.h: row_norms_device's norm, one
+        correctly rounded float32 division per element. A missing or all-zero row stays zeros.
+        out : float32 (n, >= col_off + dim) tensor with unit column stride on the same device, optional; nothing outside
+            columns [col_off, col_off + dim) is written
+        return_norms : True returns (rows, norms), norms the float32 (n,) tensor of row_norms_device
+        float32 only: no bfloat16 / float16 unit rows.'''
+        import torch
+        index, device = self._norms_arguments(torch, rows)
+        n = rows.numel()
+        dim = self.dim
+        if out is None:
+            out = torch.empty((n, col_off + dim), dtype=torch.float32, device=device)
+        if out.dtype != torch.float32 or out.dim() != 2 or out.stride(1) != 1 or out.shape[0] != n:
+            raise TypeError('out must be a float32 (n, width) tensor with unit column stride')
+        if device.index != index or out.device != device:
+            raise ValueError('rows and out must be on cuda:{} (the device this reader is staged on), got {} and {}'.format(
+                self.device, device, out.device))
+        if out.shape[1] < col_off + dim:
+            raise ValueError('out is narrower than col_off + dim')
+        norms = torch.empty((n,), dtype=torch.float32, device=device) if return_norms else None
+        ld = out.stride(0) if n > 1 else out.shape[1]
+        self._impl.unit_rows_to_device(
+            rows.data_ptr(), n, out.data_ptr(), ld, col_off, norms.data_ptr() if return_norms else 0,
+            _current_stream(torch, index))
+        self._last_norms_kernel = self._impl.norms_kernel_name(True, out.data_ptr(), ld, col_off)
+        return (out, norms) if return_norms else out
+
+    def unit_batch_embedding_device(self, words):
+        '''batch_embedding_device with rows of unit length (unit_rows_embedding_device); an unknown word stays zeros'''
+        return self.unit_rows_embedding_device(self.resolve_rows_device(words))
+
+    def row_norms(self, rows):
+        '''row_norms_device for host arrays: numpy row ids in, a numpy float32 (n,) array out. A reader on a GPU sends the
+        ids up and brings n floats back; a device='cpu' reader evaluates the same contract in numpy over rows_embedding in
+        bounded slices: the same bits.'''
+        rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        if self._impl.device() != _memb.HOST_DEVICE:
+            import torch
+            on_device = torch.from_numpy(rows.view(np.int32)).to('cuda:{}'.format(self._impl.device()))
+            return self.row_norms_device(on_device).cpu().numpy()
+        out = np.zeros(rows.size, dtype=np.float32)
+        for start in range(0, rows.size, NORMS_HOST_CHUNK):
+            out[start:start + NORMS_HOST_CHUNK] = row_norms_host(self.rows_embedding(rows[start:start + NORMS_HOST_CHUNK]))
+        return out
+
+    def unit_rows_embedding(self, rows):
+        '''unit_rows_embedding_device for host arrays: a numpy float32 (n, dim) matrix of unit rows, on either path with
+        the same bits (row_norms)'''
+        rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        if self._impl.device() != _memb.HOST_DEVICE:
+            import torch
+            on_device = torch.from_numpy(rows.view(np.int32)).to('cuda:{}'.format(self._impl.device()))
+            return self.unit_rows_embedding_device(on_device).cpu().numpy()
+        out = np.zeros((rows.size, self.dim), dtype=np.float32)
+        for start in range(0, rows.size, NORMS_HOST_CHUNK):
+            out[start:start + NORMS_HOST_CHUNK] = unit_rows_host(self.rows_embedding(rows[start:start + NORMS_HOST_CHUNK]))
         return out
 
     def stage_words(self):

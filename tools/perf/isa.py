@@ -24,7 +24,8 @@ NARROW_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_narrow.hip')
 POOLED_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_pooled.hip')
 POOLED_CHUNKED_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_pooled_chunked.hip')
 POOLED_UNION_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_pooled_union.hip')
-SOURCES = (SOURCE, NARROW_SOURCE, POOLED_SOURCE, POOLED_CHUNKED_SOURCE, POOLED_UNION_SOURCE)   # every translation unit of build_native.build_hip_library
+NORMS_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_norms.hip')
+SOURCES = (SOURCE, NARROW_SOURCE, POOLED_SOURCE, POOLED_CHUNKED_SOURCE, POOLED_UNION_SOURCE, NORMS_SOURCE)   # every translation unit of build_native.build_hip_library
 # the flags of build_native.build_hip_library
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt',
          '-Wno-unused-value', '-Wno-align-mismatch', '-Wno-pass-failed', '-Wno-unused-command-line-argument']
@@ -58,7 +59,7 @@ def _instructions(code, symbol):
 def kernel_table(extra_flags=(), source=SOURCE):
     """{demangled kernel name: facts} for every kernel of one translation unit of libmemb_hip.so (default memb_hip.hip;
     NARROW_SOURCE: the bf16 / fp16 decode kernels; POOLED_SOURCE: every sequential pooled kernel; POOLED_CHUNKED_SOURCE: the
-    chunked order's; POOLED_UNION_SOURCE: the pooled kernels of averaged unions and of dense rows; or any other path, such as a unit of another checkout)"""
+    chunked order's; POOLED_UNION_SOURCE: the pooled kernels of averaged unions and of dense rows; NORMS_SOURCE: row norms and unit rows; or any other path, such as a unit of another checkout)"""
     text = device_assembly(extra_flags, source)
     names = re.findall(r'^\s*\.amdhsa_kernel (\S+)$', text, flags=re.M)
     demangled = subprocess.run([_tool('c++filt')], input='\n'.join(names), stdout=subprocess.PIPE, text=True,
