@@ -9,6 +9,7 @@
 #include "codec.h"
 #include "../../include/memb_hip_pooled_union.h"
 #include "../../include/memb_hip_norms.h"
+#include "../../include/memb_hip_pairs.h"
 
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -1094,7 +1095,53 @@ PYBIND11_MODULE(_memb, m) {
             },
             py::arg("rows"),
             py::arg("unit_rows") = false,
-            py::arg("norms") = true);
+            py::arg("norms") = true)
+        // include/memb_hip_pairs.h. Device pointers: 2 n interleaved row ids; each of the three outputs may be 0. False where
+        // the fused kernel does not exist for this model (MEMB_HIP_UNSUPPORTED): the caller decodes the rows and calls
+        // dense_pair_similarity_to_device.
+        .def(
+            "pair_similarity_to_device",
+            [](memb::Reader& reader, uintptr_t pairs, size_t n, uintptr_t cosines, uintptr_t dots, uintptr_t norms,
+               uintptr_t stream)
+            {
+                const int code = memb_hip_pair_similarity_device(
+                    reader.deviceContext(), reinterpret_cast<const uint32_t*>(pairs), n, reinterpret_cast<float*>(cosines),
+                    reinterpret_cast<float*>(dots), reinterpret_cast<float*>(norms), reinterpret_cast<void*>(stream));
+                if (code == MEMB_HIP_UNSUPPORTED) {
+                    return false;
+                }
+                if (code != MEMB_HIP_OK) {
+                    throw std::runtime_error(std::string("memb_hip_pair_similarity_device: ") + memb_hip_last_error());
+                }
+                return true;
+            },
+            py::arg("pairs_ptr"),
+            py::arg("n"),
+            py::arg("cosines_ptr"),
+            py::arg("dots_ptr") = 0,
+            py::arg("norms_ptr") = 0,
+            py::arg("stream") = 0)
+        // the kernel family pair_similarity_to_device launches, '' where it returns False
+        .def(
+            "pairs_kernel_name",
+            [](memb::Reader& reader) { return std::string(memb_hip_pairs_kernel_name(reader.deviceContext())); })
+        .def(
+            "pairs_algorithmic_bytes",
+            [](memb::Reader& reader, py::array_t<uint32_t, py::array::c_style | py::array::forcecast> pairs, bool cosines,
+               bool dots, bool norms)
+            {
+                uint64_t bytes = 0;
+                if (memb_hip_pairs_algorithmic_bytes(
+                        reader.deviceContext(), pairs.data(), static_cast<size_t>(pairs.size() / 2), cosines ? 1 : 0,
+                        dots ? 1 : 0, norms ? 1 : 0, &bytes) != MEMB_HIP_OK) {
+                    throw std::runtime_error(std::string("memb_hip_pairs_algorithmic_bytes: ") + memb_hip_last_error());
+                }
+                return bytes;
+            },
+            py::arg("pairs"),
+            py::arg("cosines") = true,
+            py::arg("dots") = false,
+            py::arg("norms") = false);
 
     m.attr("OUT_F32") = MEMB_HIP_OUT_F32;
     m.attr("OUT_BF16") = MEMB_HIP_OUT_BF16;
@@ -1299,6 +1346,30 @@ PYBIND11_MODULE(_memb, m) {
     m.def("dense_norms_kernel_name", [](bool unitRows) {
         return std::string(memb_hip_norms_kernel_name(nullptr, unitRows ? 1 : 0, nullptr, 0, 0));
     });
+    // the cosines, dots and norms (memb_hip_dense_pair_similarity_device) of the n pairs of rows (2i, 2i + 1) of a dense fp32
+    // matrix of 2 n rows on `device`. Device pointers; each of the three outputs may be 0.
+    m.def(
+        "dense_pair_similarity_to_device",
+        [](int device, uintptr_t values, size_t n, size_t dim, size_t ldValues, uintptr_t cosines, uintptr_t dots,
+           uintptr_t norms, uintptr_t stream)
+        {
+            if (memb_hip_dense_pair_similarity_device(
+                    device, reinterpret_cast<const float*>(values), n, dim, ldValues, reinterpret_cast<float*>(cosines),
+                    reinterpret_cast<float*>(dots), reinterpret_cast<float*>(norms), reinterpret_cast<void*>(stream)) !=
+                MEMB_HIP_OK) {
+                throw std::runtime_error(std::string("memb_hip_dense_pair_similarity_device: ") + memb_hip_last_error());
+            }
+        },
+        py::arg("device"),
+        py::arg("values_ptr"),
+        py::arg("n"),
+        py::arg("dim"),
+        py::arg("ld_values"),
+        py::arg("cosines_ptr"),
+        py::arg("dots_ptr") = 0,
+        py::arg("norms_ptr") = 0,
+        py::arg("stream") = 0);
+    m.def("dense_pairs_kernel_name", [] { return std::string(memb_hip_pairs_kernel_name(nullptr)); });
     // one batch of words resolved by several readers of one device (ReadersUnion): packed and copied once
     m.def(
         "union_words_to_rows_device",

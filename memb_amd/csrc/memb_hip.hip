@@ -43,7 +43,8 @@
 // of each bag of rows or of its known rows, as fp32, bf16 or fp16), handed over the same way through one selector
 // (hip_pooled.h); memb_hip_pooled_chunked.hip -- the chunked order's (hip_pooled_chunked.h); memb_hip_pooled_union.hip -- the
 // pooled kernels of a ReadersUnion's averaged rows and of dense rows (hip_pooled_union.h); memb_hip_norms.hip -- row norms
-// and rows of unit length (hip_norms.h), launched by hip_norms_launch.h, which also holds their entry points.
+// and rows of unit length (hip_norms.h), launched by hip_norms_launch.h, which also holds their entry points;
+// memb_hip_pairs.hip -- the cosine similarity of pairs of rows (hip_pairs.h), launched by hip_pairs_launch.h likewise.
 #include <hip/hip_runtime.h>
 
 #include "../../include/memb_hip.h"
@@ -53,12 +54,14 @@
 #include "../../include/memb_hip_pooled_chunked.h"
 #include "../../include/memb_hip_pooled_union.h"
 #include "../../include/memb_hip_norms.h"
+#include "../../include/memb_hip_pairs.h"
 #include "codec.h"
 #include "hip_narrow.h"
 #include "hip_pooled.h"
 #include "hip_pooled_chunked.h"
 #include "hip_pooled_union.h"
 #include "hip_norms.h"
+#include "hip_pairs.h"
 #include "wire.h"
 #include "worker_pool.h"
 
@@ -131,6 +134,7 @@ namespace {
 
 #include "hip_entry_points.h"
 #include "hip_norms_launch.h"
+#include "hip_pairs_launch.h"
 
 // No C++ exception leaves the library: allocation failures and the like become error codes.
 template <typename Call>
@@ -363,6 +367,30 @@ int memb_hip_norms_algorithmic_bytes(
     const memb_hip_ctx* ctx, const uint32_t* rows, size_t n, int unit_rows, int norms, uint64_t* bytes)
 {
     return guarded([&] { return norms_algorithmic_bytes_checked(ctx, rows, n, unit_rows != 0, norms != 0, bytes); });
+}
+
+int memb_hip_pair_similarity_device(
+    memb_hip_ctx* ctx, const uint32_t* pairs, size_t n, float* cosines, float* dots, float* norms, void* stream)
+{
+    return guarded([&] { return pair_similarity_device_checked(ctx, pairs, n, cosines, dots, norms, stream); });
+}
+
+int memb_hip_dense_pair_similarity_device(
+    int device, const float* values, size_t n, size_t dim, size_t ld_values, float* cosines, float* dots, float* norms,
+    void* stream)
+{
+    return guarded([&] { return dense_pair_similarity_device_checked(device, values, n, dim, ld_values, cosines, dots, norms, stream); });
+}
+
+const char* memb_hip_pairs_kernel_name(const memb_hip_ctx* ctx)
+{
+    return pairs_kernel_name(ctx);
+}
+
+int memb_hip_pairs_algorithmic_bytes(
+    const memb_hip_ctx* ctx, const uint32_t* pairs, size_t n, int cosines, int dots, int norms, uint64_t* bytes)
+{
+    return guarded([&] { return pairs_algorithmic_bytes_checked(ctx, pairs, n, cosines != 0, dots != 0, norms != 0, bytes); });
 }
 
 int memb_hip_decode_batches_device(memb_hip_ctx* ctx, const memb_hip_batch* batches, size_t count, void* stream)

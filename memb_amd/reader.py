@@ -282,28 +282,55 @@ NORMS_DEVICE_SLICE = 1 << 20    # rows row_norms_device decodes into a temporary
 UNIT_EPS = np.float32(1e-12)    # torch.nn.functional.normalize's eps
 
 
+def _contract_sums(products):
+    """The reduction include/memb_hip_norms.h and include/memb_hip_pairs.h share, over a float32 (n, 4 * pieces) matrix of
+    products: piece sums ((t0 + t1) + t2) + t3, 64 lane partials over the pieces l, l + 64, .. (a lane without a further
+    piece keeps its bits), a butterfly of strides 1 .. 32. Returns the float32 (n,) totals."""
+    n = products.shape[0]
+    pieces = products.shape[1] // 4
+    terms = products.reshape(n, pieces, 4)
+    sums = ((terms[:, :, 0] + terms[:, :, 1]) + terms[:, :, 2]) + terms[:, :, 3]
+    partial = np.zeros((n, 64), dtype=np.float32)
+    partial[:, :min(64, pieces)] = sums[:, :64]
+    for first in range(64, pieces, 64):
+        width = min(64, pieces - first)
+        partial[:, :width] = partial[:, :width] + sums[:, first:first + width]
+    lanes = np.arange(64)
+    for stride in (1, 2, 4, 8, 16, 32):
+        partial = partial + partial[:, lanes ^ stride]
+    return partial[:, 0]
+
+
+def _padded_to_pieces(values):
+    """a float32 (n, dim) matrix with +0.0 columns up to a multiple of 4"""
+    values = np.ascontiguousarray(values, dtype=np.float32)
+    n, dim = values.shape
+    padded = np.zeros((n, 4 * -(-dim // 4)), dtype=np.float32)
+    padded[:, :dim] = values
+    return padded
+
+
 def row_norms_host(values):
     """The norm contract of include/memb_hip_norms.h in numpy: the float32 (n,) norms of the rows of a float32 (n, dim)
     matrix, every product, sum and root one IEEE float32 operation in the kernels' order -- piece sums
     ((v0 v0 + v1 v1) + v2 v2) + v3 v3 over columns 4k .. 4k + 3 (a column >= dim is +0.0), 64 lane partials over the pieces
     l, l + 64, .., a butterfly of strides 1 .. 32, one square root."""
-    values = np.ascontiguousarray(values, dtype=np.float32)
-    n, dim = values.shape
-    pieces = -(-dim // 4)
-    padded = np.zeros((n, 4 * pieces), dtype=np.float32)
-    padded[:, :dim] = values
+    padded = _padded_to_pieces(values)
     with np.errstate(over='ignore', under='ignore', invalid='ignore'):
-        squares = (padded * padded).reshape(n, pieces, 4)
-        sums = ((squares[:, :, 0] + squares[:, :, 1]) + squares[:, :, 2]) + squares[:, :, 3]
-        partial = np.zeros((n, 64), dtype=np.float32)
-        partial[:, :min(64, pieces)] = sums[:, :64]
-        for first in range(64, pieces, 64):
-            width = min(64, pieces - first)
-            partial[:, :width] = partial[:, :width] + sums[:, first:first + width]
-        lanes = np.arange(64)
-        for stride in (1, 2, 4, 8, 16, 32):
-            partial = partial + partial[:, lanes ^ stride]
-        return np.sqrt(partial[:, 0])
+        return np.sqrt(_contract_sums(padded * padded))
+
+
+def pair_similarity_host(x, y):
+    """The contract of include/memb_hip_pairs.h in numpy for the pairs (x[i], y[i]) of two float32 (n, dim) matrices:
+    (cosines, dots, norms), float32 (n,), (n,) and (n, 2). The dot is row_norms_host's reduction over the products x * y,
+    the norms are row_norms_host's, cos = dot / (max(na, 1e-12) * max(nb, 1e-12)): one float32 product and one float32
+    quotient, not clamped to [-1, 1]."""
+    x, y = _padded_to_pieces(x), _padded_to_pieces(y)
+    with np.errstate(over='ignore', under='ignore', invalid='ignore'):
+        dots = _contract_sums(x * y)
+        norms = np.stack([np.sqrt(_contract_sums(x * x)), np.sqrt(_contract_sums(y * y))], axis=1)
+        floored = np.where(norms < UNIT_EPS, UNIT_EPS, norms)
+        return dots / (floored[:, 0] * floored[:, 1]), dots, norms
 
 
 def unit_rows_host(values, norms=None):
@@ -369,6 +396,7 @@ class Reader(BaseReader):
             self._impl.set_host_below(int(host_below))
         self._word_batches = WordBatches()   # of resolve_rows_device / resolve_packed_device: one per call in flight
         self._last_norms_kernel = ''
+        self._last_pairs_kernel = ''
 
     @property
     def _word_batch(self):
@@ -777,6 +805,103 @@ class Reader(BaseReader):
         for start in range(0, rows.size, NORMS_HOST_CHUNK):
             out[start:start + NORMS_HOST_CHUNK] = unit_rows_host(self.rows_embedding(rows[start:start + NORMS_HOST_CHUNK]))
         return out
+
+    @property
+    def last_pairs_kernel(self):
+        """The kernel family of the last pair_similarity_device call: 'pairs_trained' (fused with the decode) or
+        'pairs_dense' behind a plain decode of the rows -- uniform and full storage, dims that are no multiple of 4 or
+        beyond 512, geometries of one word per wavefront. '' before any call. Informational: the bits are the same."""
+        return self._last_pairs_kernel
+
+    def pair_similarity_device(self, rows_a, rows_b=None, *, return_dots=False, return_norms=False, out=None):
+        '''The cosine similarity of pairs of rows, left on the GPU: a float32 (n,) tensor, cos[i] of the rows rows_a[i] and
+        rows_b[i]. For trained models whose dim is a multiple of 4 and at most 512 ONE kernel computes it from the
+        compressed rows and writes no row; otherwise the rows are decoded in slices of at most 2^20 into a temporary and
+        reduced there (last_pairs_kernel says which). Bit for bit the contract of include/memb_hip_pairs.h over
+        rows_embedding_device: float32 piece products, row_norms_device's reduction tree and norms,
+        cos = dot / (max(na, 1e-12) * max(nb, 1e-12)) -- whichever kernel ran. Not clamped: the cosine of a row with itself
+        may be 1.0000001. A pair with a row that is not in the model has cosine 0.
+        rows_a, rows_b : two contiguous int32 / uint32 (n,) tensors on this reader's device, as in rows_embedding_device
+            (they are interleaved by one torch.stack), or rows_b=None and rows_a a contiguous (n, 2) tensor of pairs, which
+            is passed as it is: nothing is allocated but the results
+        return_dots, return_norms : either one returns (cosines, dots, norms) instead, dots a float32 (n,) and norms a
+            float32 (n, 2) tensor -- row_norms_device's of rows_a and rows_b --, None where not asked for
+        out : optional contiguous float32 (n,) tensor on the same device for the cosines
+        One model, float32 only: no ReadersUnion, no ShardedReader, no bfloat16 / float16, no one-against-many search.'''
+        import torch
+        index, device = self._norms_arguments(torch, rows_a)
+        if rows_b is None:
+            if rows_a.dim() != 2 or rows_a.shape[1] != 2:
+                raise TypeError('without rows_b, rows_a must be a contiguous (n, 2) tensor of pairs')
+            pairs = rows_a
+        else:
+            self._norms_arguments(torch, rows_b)
+            if rows_a.dim() != 1 or rows_b.shape != rows_a.shape or rows_b.dtype != rows_a.dtype or rows_b.device != device:
+                raise TypeError('rows_a and rows_b must be (n,) tensors of one dtype on one device')
+            pairs = torch.stack((rows_a.view(torch.int32), rows_b.view(torch.int32)), dim=1)   # (the ids' bits)
+        n = pairs.shape[0]
+        if out is None:
+            out = torch.empty((n,), dtype=torch.float32, device=device)
+        if out.dtype != torch.float32 or out.dim() != 1 or out.shape[0] != n or not out.is_contiguous():
+            raise TypeError('out must be a contiguous float32 (n,) tensor')
+        if device.index != index or out.device != device:
+            raise ValueError('rows and out must be on cuda:{} (the device this reader is staged on), got {} and {}'.format(
+                self.device, device, out.device))
+        dots = torch.empty((n,), dtype=torch.float32, device=device) if return_dots else None
+        norms = torch.empty((n, 2), dtype=torch.float32, device=device) if return_norms else None
+        result = (out, dots, norms) if return_dots or return_norms else out
+
+        def pointers(start, stop):
+            return (out[start:stop].data_ptr(), dots[start:stop].data_ptr() if return_dots else 0,
+                    norms[start:stop].data_ptr() if return_norms else 0)
+
+        stream = _current_stream(torch, index)
+        if self._impl.pair_similarity_to_device(pairs.data_ptr(), n, *pointers(0, n), stream):
+            self._last_pairs_kernel = self._impl.pairs_kernel_name()
+            return result
+        flat = pairs.reshape(-1)
+        dim = self.dim
+        slice_pairs = max(NORMS_DEVICE_SLICE // 2, 1)   # slices of at most NORMS_DEVICE_SLICE rows, an even number
+        temporary = torch.empty((2 * min(n, slice_pairs), dim), dtype=torch.float32, device=device)
+        for start in range(0, n, slice_pairs):
+            stop = min(n, start + slice_pairs)
+            decoded = self.rows_embedding_device(flat[2 * start:2 * stop], out=temporary[:2 * (stop - start)])
+            _memb.dense_pair_similarity_to_device(index, decoded.data_ptr(), stop - start, dim, dim, *pointers(start, stop), stream)
+        self._last_pairs_kernel = _memb.dense_pairs_kernel_name()
+        return result
+
+    def similarity_device(self, words_a, words_b):
+        '''The cosine similarity of words_a[i] and words_b[i], a float32 (n,) tensor on the GPU: both lists resolved by
+        resolve_rows_device, then pair_similarity_device. An unknown word gives 0.'''
+        return self.pair_similarity_device(self.resolve_rows_device(words_a), self.resolve_rows_device(words_b))
+
+    def pair_similarity(self, rows_a, rows_b, return_dots=False, return_norms=False):
+        '''pair_similarity_device for host arrays: numpy row ids in, a numpy float32 (n,) array of cosines out, or
+        (cosines, dots, norms) with either flag (None where not asked for). A reader on a GPU sends the ids up and brings
+        the scalars back; a device='cpu' reader evaluates the same contract in numpy (pair_similarity_host) over
+        rows_embedding in bounded slices: the same bits.'''
+        rows_a = np.ascontiguousarray(rows_a, dtype=np.uint32).reshape(-1)
+        rows_b = np.ascontiguousarray(rows_b, dtype=np.uint32).reshape(-1)
+        if rows_a.size != rows_b.size:
+            raise ValueError('rows_a and rows_b must have the same length')
+        n = rows_a.size
+        if self._impl.device() != _memb.HOST_DEVICE:
+            import torch
+            pairs = torch.from_numpy(np.stack((rows_a, rows_b), axis=1).view(np.int32)).to('cuda:{}'.format(self._impl.device()))
+            result = self.pair_similarity_device(pairs, return_dots=return_dots, return_norms=return_norms)
+            if return_dots or return_norms:
+                return tuple(None if part is None else part.cpu().numpy() for part in result)
+            return result.cpu().numpy()
+        cosines = np.zeros(n, dtype=np.float32)
+        dots = np.zeros(n, dtype=np.float32)
+        norms = np.zeros((n, 2), dtype=np.float32)
+        for start in range(0, n, NORMS_HOST_CHUNK):
+            stop = start + NORMS_HOST_CHUNK
+            cosines[start:stop], dots[start:stop], norms[start:stop] = pair_similarity_host(
+                self.rows_embedding(rows_a[start:stop]), self.rows_embedding(rows_b[start:stop]))
+        if return_dots or return_norms:
+            return cosines, dots if return_dots else None, norms if return_norms else None
+        return cosines
 
     def stage_words(self):
         '''Copy the model's keys to the GPU and build the hash table over them there (once; resolve_rows_device does it
