@@ -67,7 +67,7 @@ def build_hip_library(force=False, extra_flags=()):
             '-o', HIP_LIBRARY, os.path.join(CSRC, 'memb_hip.hip'), os.path.join(CSRC, 'memb_hip_narrow.hip'),
             os.path.join(CSRC, 'memb_hip_pooled.hip'), os.path.join(CSRC, 'memb_hip_pooled_chunked.hip'),
             os.path.join(CSRC, 'memb_hip_pooled_union.hip'), os.path.join(CSRC, 'memb_hip_norms.hip'),
-            os.path.join(CSRC, 'memb_hip_pairs.hip'),
+            os.path.join(CSRC, 'memb_hip_pairs.hip'), os.path.join(CSRC, 'memb_hip_bag_pairs.hip'),
         ])
     return HIP_LIBRARY
 

@@ -44,7 +44,8 @@
 // (hip_pooled.h); memb_hip_pooled_chunked.hip -- the chunked order's (hip_pooled_chunked.h); memb_hip_pooled_union.hip -- the
 // pooled kernels of a ReadersUnion's averaged rows and of dense rows (hip_pooled_union.h); memb_hip_norms.hip -- row norms
 // and rows of unit length (hip_norms.h), launched by hip_norms_launch.h, which also holds their entry points;
-// memb_hip_pairs.hip -- the cosine similarity of pairs of rows (hip_pairs.h), launched by hip_pairs_launch.h likewise.
+// memb_hip_pairs.hip -- the cosine similarity of pairs of rows (hip_pairs.h), launched by hip_pairs_launch.h likewise;
+// memb_hip_bag_pairs.hip -- that of pairs of pooled bags (hip_bag_pairs.h), launched by hip_bag_pairs_launch.h.
 #include <hip/hip_runtime.h>
 
 #include "../../include/memb_hip.h"
@@ -55,6 +56,7 @@
 #include "../../include/memb_hip_pooled_union.h"
 #include "../../include/memb_hip_norms.h"
 #include "../../include/memb_hip_pairs.h"
+#include "../../include/memb_hip_bag_pairs.h"
 #include "codec.h"
 #include "hip_narrow.h"
 #include "hip_pooled.h"
@@ -62,6 +64,7 @@
 #include "hip_pooled_union.h"
 #include "hip_norms.h"
 #include "hip_pairs.h"
+#include "hip_bag_pairs.h"
 #include "wire.h"
 #include "worker_pool.h"
 
@@ -135,6 +138,7 @@ namespace {
 #include "hip_entry_points.h"
 #include "hip_norms_launch.h"
 #include "hip_pairs_launch.h"
+#include "hip_bag_pairs_launch.h"
 
 // No C++ exception leaves the library: allocation failures and the like become error codes.
 template <typename Call>
@@ -391,6 +395,27 @@ int memb_hip_pairs_algorithmic_bytes(
     const memb_hip_ctx* ctx, const uint32_t* pairs, size_t n, int cosines, int dots, int norms, uint64_t* bytes)
 {
     return guarded([&] { return pairs_algorithmic_bytes_checked(ctx, pairs, n, cosines != 0, dots != 0, norms != 0, bytes); });
+}
+
+int memb_hip_bag_pair_similarity_device(
+    memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t pairs, int mode, float* cosines,
+    float* dots, float* norms, void* stream)
+{
+    return guarded([&] { return bag_pair_similarity_device_checked(ctx, rows, n, offsets, pairs, mode, cosines, dots, norms, stream); });
+}
+
+const char* memb_hip_bag_pairs_kernel_name(const memb_hip_ctx* ctx)
+{
+    return bag_pairs_kernel_name(ctx);
+}
+
+int memb_hip_bag_pairs_algorithmic_bytes(
+    const memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t pairs, int cosines, int dots,
+    int norms, uint64_t* bytes)
+{
+    return guarded([&] {
+        return bag_pairs_algorithmic_bytes_checked(ctx, rows, n, offsets, pairs, cosines != 0, dots != 0, norms != 0, bytes);
+    });
 }
 
 int memb_hip_decode_batches_device(memb_hip_ctx* ctx, const memb_hip_batch* batches, size_t count, void* stream)

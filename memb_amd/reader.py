@@ -397,6 +397,7 @@ class Reader(BaseReader):
         self._word_batches = WordBatches()   # of resolve_rows_device / resolve_packed_device: one per call in flight
         self._last_norms_kernel = ''
         self._last_pairs_kernel = ''
+        self._last_bag_pairs_kernel = ''
 
     @property
     def _word_batch(self):
@@ -899,6 +900,138 @@ class Reader(BaseReader):
             stop = start + NORMS_HOST_CHUNK
             cosines[start:stop], dots[start:stop], norms[start:stop] = pair_similarity_host(
                 self.rows_embedding(rows_a[start:stop]), self.rows_embedding(rows_b[start:stop]))
+        if return_dots or return_norms:
+            return cosines, dots if return_dots else None, norms if return_norms else None
+        return cosines
+
+    @property
+    def last_bag_pairs_kernel(self):
+        """The kernel family of the last bag_pair_similarity_device call: 'bag_pairs_trained' (fused with the pooling) or
+        'pairs_dense' behind a pooled lookup of the bags -- uniform and full storage, dims that are no multiple of 4 or
+        beyond 512. '' before any call. Informational: the bits are the same."""
+        return self._last_bag_pairs_kernel
+
+    def bag_pair_similarity_device(self, rows, offsets, mode='mean', *, return_dots=False, return_norms=False, out=None):
+        '''The cosine similarity of pairs of bags of rows, left on the GPU: a float32 (pairs,) tensor, cos[j] of the sums
+        or means of the bags 2j and 2j + 1 -- the similarity of two sentences as averaged word vectors. For trained models
+        whose dim is a multiple of 4 and at most 512 ONE kernel computes it from the compressed rows and writes no row;
+        otherwise slices of whole pairs, of at most 2^20 bags, are pooled into a temporary (bags_embedding_device) and
+        reduced there (last_bag_pairs_kernel says which). Bit for bit the contract of include/memb_hip_bag_pairs.h:
+        pair_similarity_device's reduction over the rows bags_embedding_device(rows, offsets, mode) gives -- whichever
+        kernel ran. Not clamped. A pair with an empty bag, or a bag of rows that are not in the model, has cosine 0.
+        rows, offsets : as in bags_embedding_device; offsets holds 2 * pairs + 1 entries, an odd number (ValueError)
+        mode : 'mean' or 'sum'
+        return_dots, return_norms : either one returns (cosines, dots, norms) instead, dots a float32 (pairs,) and norms
+            a float32 (pairs, 2) tensor -- row_norms_device's of the two pooled rows --, None where not asked for
+        out : optional contiguous float32 (pairs,) tensor on the same device for the cosines
+        One model, float32, missing='zero', the sequential order: no missing='skip', no reduction='chunked', no
+        bfloat16 / float16, no ReadersUnion, no ShardedReader, no one-against-many search.'''
+        import torch
+        code = pool_mode(mode)
+        index, device = self._norms_arguments(torch, rows)
+        if (not isinstance(offsets, torch.Tensor) or offsets.device.type != 'cuda' or offsets.dtype not in (torch.int32, torch.uint32)
+                or not offsets.is_contiguous() or offsets.dim() != 1):
+            raise TypeError('offsets must be a contiguous int32/uint32 tensor of 2 * pairs + 1 entries on the GPU')
+        if offsets.numel() % 2 != 1:
+            raise ValueError('offsets needs 2 * pairs + 1 entries, an odd number: pair j is the bags 2j and 2j + 1')
+        n = offsets.numel() // 2
+        if out is None:
+            out = torch.empty((n,), dtype=torch.float32, device=device)
+        if out.dtype != torch.float32 or out.dim() != 1 or out.shape[0] != n or not out.is_contiguous():
+            raise TypeError('out must be a contiguous float32 (pairs,) tensor')
+        if device.index != index or out.device != device or offsets.device != device:
+            raise ValueError('rows, offsets and out must be on cuda:{} (the device this reader is staged on), got {}, {} and {}'.format(
+                self.device, device, offsets.device, out.device))
+        dots = torch.empty((n,), dtype=torch.float32, device=device) if return_dots else None
+        norms = torch.empty((n, 2), dtype=torch.float32, device=device) if return_norms else None
+        result = (out, dots, norms) if return_dots or return_norms else out
+
+        def pointers(start, stop):
+            return (out[start:stop].data_ptr(), dots[start:stop].data_ptr() if return_dots else 0,
+                    norms[start:stop].data_ptr() if return_norms else 0)
+
+        stream = _current_stream(torch, index)
+        if self._impl.bag_pair_similarity_to_device(
+                rows.data_ptr(), rows.numel(), offsets.data_ptr(), n, code, *pointers(0, n), stream):
+            self._last_bag_pairs_kernel = self._impl.bag_pairs_kernel_name()
+            return result
+        flat = rows.reshape(-1)
+        dim = self.dim
+        slice_pairs = max(NORMS_DEVICE_SLICE // 2, 1)   # slices of at most NORMS_DEVICE_SLICE bags, an even number
+        temporary = torch.empty((2 * min(n, slice_pairs), dim), dtype=torch.float32, device=device)
+        for start in range(0, n, slice_pairs):
+            stop = min(n, start + slice_pairs)
+            entries, cut = flat, offsets
+            if n > slice_pairs:
+                # the slice's offsets as the kernel clamps them, rebased on the slice's lowest entry so that the pooled
+                # launch is planned for the slice's entries alone: made on the device, with one scalar read back to cut
+                # those entries out of `rows` (batches of more than 2^20 bags only)
+                cut = offsets[2 * start:2 * stop + 1].view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+                cut = torch.clamp(cut, max=flat.numel())
+                first = int(cut.min())
+                entries, cut = flat[first:], (cut - first).to(torch.int32)
+            pooled = self.bags_embedding_device(entries, cut, mode=mode, out=temporary[:2 * (stop - start)])
+            _memb.dense_pair_similarity_to_device(index, pooled.data_ptr(), stop - start, dim, dim, *pointers(start, stop), stream)
+        self._last_bag_pairs_kernel = _memb.dense_pairs_kernel_name()
+        return result
+
+    def sentence_similarity_device(self, sentences_a, sentences_b, mode='mean'):
+        '''The cosine similarity of sentences_a[i] and sentences_b[i] as pooled word vectors, a float32 (n,) tensor on the
+        GPU: two equally long sequences of word sequences, interleaved, flattened (flatten_sentences), resolved on the
+        device (resolve_rows_device) and reduced by bag_pair_similarity_device. An unknown word is a zero row that counts;
+        a pair with a sentence without words gives 0.'''
+        import torch
+        pool_mode(mode)
+        if len(sentences_a) != len(sentences_b):
+            raise ValueError('sentences_a and sentences_b must have the same length')
+        index = self._impl.device()
+        if index == _memb.HOST_DEVICE:
+            raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
+        interleaved = [sentence for pair in zip(sentences_a, sentences_b) for sentence in pair]
+        words, offsets = flatten_sentences(interleaved)
+        device = 'cuda:{}'.format(index)
+        rows = self.resolve_rows_device(words) if words else torch.empty((0,), dtype=torch.int32, device=device)
+        on_device = torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).to(device)
+        return self.bag_pair_similarity_device(rows, on_device, mode=mode)
+
+    def bag_pair_similarity(self, rows, offsets, mode='mean', return_dots=False, return_norms=False):
+        '''bag_pair_similarity_device for host arrays: numpy row ids and 2 * pairs + 1 offsets (bags_embedding's: ascending,
+        within 0 .. len(rows)) in, a numpy float32 (pairs,) array of cosines out, or (cosines, dots, norms) with either
+        flag (None where not asked for). A reader on a GPU sends the ids and offsets up and brings the scalars back; a
+        device='cpu' reader evaluates the same contract in numpy (bags_embedding's sums, pair_similarity_host) in bounded
+        slices: the same bits.'''
+        code = pool_mode(mode)
+        rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        offsets = bag_offsets(offsets, rows.size)
+        if offsets.size % 2 != 1:
+            raise ValueError('offsets needs 2 * pairs + 1 entries, an odd number: pair j is the bags 2j and 2j + 1')
+        n = offsets.size // 2
+        if self._impl.device() != _memb.HOST_DEVICE:
+            import torch
+            device = 'cuda:{}'.format(self._impl.device())
+            result = self.bag_pair_similarity_device(
+                torch.from_numpy(rows.view(np.int32)).to(device),
+                torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).to(device), mode=mode, return_dots=return_dots,
+                return_norms=return_norms)
+            if return_dots or return_norms:
+                return tuple(None if part is None else part.cpu().numpy() for part in result)
+            return result.cpu().numpy()
+        cosines = np.zeros(n, dtype=np.float32)
+        dots = np.zeros(n, dtype=np.float32)
+        norms = np.zeros((n, 2), dtype=np.float32)
+        slice_pairs = max(NORMS_HOST_CHUNK // 2, 1)
+        for start in range(0, n, slice_pairs):
+            stop = min(n, start + slice_pairs)
+            cut = offsets[2 * start:2 * stop + 1]
+            first, last = int(cut[0]), int(cut[-1])
+            entries = rows[first:last]
+
+            def slice_values(begin, end):
+                yield self.rows_embedding(entries[begin:end])
+
+            pooled, _ = pool_slices_host(
+                cut - first, last - first, self.dim, BAGS_HOST_CHUNK, code == _memb.POOL_MEAN, False, slice_values)
+            cosines[start:stop], dots[start:stop], norms[start:stop] = pair_similarity_host(pooled[0::2], pooled[1::2])
         if return_dots or return_norms:
             return cosines, dots if return_dots else None, norms if return_norms else None
         return cosines
