@@ -11,6 +11,7 @@
 #include "../../include/memb_hip_norms.h"
 #include "../../include/memb_hip_pairs.h"
 #include "../../include/memb_hip_bag_pairs.h"
+#include "../../include/memb_hip_queries.h"
 
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -1190,6 +1191,64 @@ PYBIND11_MODULE(_memb, m) {
                         static_cast<size_t>(offsets.size() / 2), cosines ? 1 : 0, dots ? 1 : 0, norms ? 1 : 0,
                         &bytes) != MEMB_HIP_OK) {
                     throw std::runtime_error(std::string("memb_hip_bag_pairs_algorithmic_bytes: ") + memb_hip_last_error());
+                }
+                return bytes;
+            },
+            py::arg("rows"),
+            py::arg("offsets"),
+            py::arg("cosines") = true,
+            py::arg("dots") = false,
+            py::arg("norms") = false)
+        // include/memb_hip_queries.h. Device pointers: `groups` fp32 query rows ld_queries floats apart, n candidate row ids
+        // cut into groups by groups + 1 offsets; each of the three outputs (n floats) may be 0. False where the fused kernel
+        // does not exist for this model (MEMB_HIP_UNSUPPORTED): the caller decodes the candidates and calls
+        // dense_pair_similarity_to_device.
+        .def(
+            "query_similarity_to_device",
+            [](memb::Reader& reader, uintptr_t queries, size_t groups, size_t ldQueries, uintptr_t rows, size_t n,
+               uintptr_t offsets, uintptr_t cosines, uintptr_t dots, uintptr_t norms, uintptr_t stream)
+            {
+                const int code = memb_hip_query_similarity_device(
+                    reader.deviceContext(), reinterpret_cast<const float*>(queries), groups, ldQueries,
+                    reinterpret_cast<const uint32_t*>(rows), n, reinterpret_cast<const uint32_t*>(offsets),
+                    reinterpret_cast<float*>(cosines), reinterpret_cast<float*>(dots), reinterpret_cast<float*>(norms),
+                    reinterpret_cast<void*>(stream));
+                if (code == MEMB_HIP_UNSUPPORTED) {
+                    return false;
+                }
+                if (code != MEMB_HIP_OK) {
+                    throw std::runtime_error(std::string("memb_hip_query_similarity_device: ") + memb_hip_last_error());
+                }
+                return true;
+            },
+            py::arg("queries_ptr"),
+            py::arg("groups"),
+            py::arg("ld_queries"),
+            py::arg("rows_ptr"),
+            py::arg("n"),
+            py::arg("offsets_ptr"),
+            py::arg("cosines_ptr"),
+            py::arg("dots_ptr") = 0,
+            py::arg("norms_ptr") = 0,
+            py::arg("stream") = 0)
+        // the kernel family query_similarity_to_device launches, '' where it returns False
+        .def(
+            "query_kernel_name",
+            [](memb::Reader& reader) { return std::string(memb_hip_query_kernel_name(reader.deviceContext())); })
+        .def(
+            "query_algorithmic_bytes",
+            [](memb::Reader& reader, py::array_t<uint32_t, py::array::c_style | py::array::forcecast> rows,
+               py::array_t<uint32_t, py::array::c_style | py::array::forcecast> offsets, bool cosines, bool dots, bool norms)
+            {
+                if (offsets.size() < 1) {
+                    throw std::invalid_argument("offsets needs groups + 1 entries");
+                }
+                uint64_t bytes = 0;
+                if (memb_hip_query_algorithmic_bytes(
+                        reader.deviceContext(), rows.data(), static_cast<size_t>(rows.size()), offsets.data(),
+                        static_cast<size_t>(offsets.size() - 1), cosines ? 1 : 0, dots ? 1 : 0, norms ? 1 : 0,
+                        &bytes) != MEMB_HIP_OK) {
+                    throw std::runtime_error(std::string("memb_hip_query_algorithmic_bytes: ") + memb_hip_last_error());
                 }
                 return bytes;
             },

@@ -45,7 +45,9 @@
 // pooled kernels of a ReadersUnion's averaged rows and of dense rows (hip_pooled_union.h); memb_hip_norms.hip -- row norms
 // and rows of unit length (hip_norms.h), launched by hip_norms_launch.h, which also holds their entry points;
 // memb_hip_pairs.hip -- the cosine similarity of pairs of rows (hip_pairs.h), launched by hip_pairs_launch.h likewise;
-// memb_hip_bag_pairs.hip -- that of pairs of pooled bags (hip_bag_pairs.h), launched by hip_bag_pairs_launch.h.
+// memb_hip_bag_pairs.hip -- that of pairs of pooled bags (hip_bag_pairs.h), launched by hip_bag_pairs_launch.h;
+// memb_hip_queries.hip -- that of query vectors against groups of candidate rows (hip_queries.h), launched by
+// hip_queries_launch.h.
 #include <hip/hip_runtime.h>
 
 #include "../../include/memb_hip.h"
@@ -57,6 +59,7 @@
 #include "../../include/memb_hip_norms.h"
 #include "../../include/memb_hip_pairs.h"
 #include "../../include/memb_hip_bag_pairs.h"
+#include "../../include/memb_hip_queries.h"
 #include "codec.h"
 #include "hip_narrow.h"
 #include "hip_pooled.h"
@@ -65,6 +68,7 @@
 #include "hip_norms.h"
 #include "hip_pairs.h"
 #include "hip_bag_pairs.h"
+#include "hip_queries.h"
 #include "wire.h"
 #include "worker_pool.h"
 
@@ -139,6 +143,7 @@ namespace {
 #include "hip_norms_launch.h"
 #include "hip_pairs_launch.h"
 #include "hip_bag_pairs_launch.h"
+#include "hip_queries_launch.h"
 
 // No C++ exception leaves the library: allocation failures and the like become error codes.
 template <typename Call>
@@ -415,6 +420,29 @@ int memb_hip_bag_pairs_algorithmic_bytes(
 {
     return guarded([&] {
         return bag_pairs_algorithmic_bytes_checked(ctx, rows, n, offsets, pairs, cosines != 0, dots != 0, norms != 0, bytes);
+    });
+}
+
+int memb_hip_query_similarity_device(
+    memb_hip_ctx* ctx, const float* queries, size_t groups, size_t ld_queries, const uint32_t* rows, size_t n,
+    const uint32_t* offsets, float* cosines, float* dots, float* norms, void* stream)
+{
+    return guarded([&] {
+        return query_similarity_device_checked(ctx, queries, groups, ld_queries, rows, n, offsets, cosines, dots, norms, stream);
+    });
+}
+
+const char* memb_hip_query_kernel_name(const memb_hip_ctx* ctx)
+{
+    return query_kernel_name(ctx);
+}
+
+int memb_hip_query_algorithmic_bytes(
+    const memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t groups, int cosines, int dots,
+    int norms, uint64_t* bytes)
+{
+    return guarded([&] {
+        return query_algorithmic_bytes_checked(ctx, rows, n, offsets, groups, cosines != 0, dots != 0, norms != 0, bytes);
     });
 }
 

@@ -279,6 +279,7 @@ def pool_slices_host(offsets, n, dim, slice_entries, mean, skip, slice_values):
 
 NORMS_HOST_CHUNK = 1 << 16      # rows row_norms / unit_rows_embedding of a device='cpu' reader decode at a time
 NORMS_DEVICE_SLICE = 1 << 20    # rows row_norms_device decodes into a temporary at a time where no fused kernel exists
+QUERY_DEVICE_SLICE = 1 << 19    # candidates query_similarity_device decodes beside their queries at a time where no fused kernel exists
 UNIT_EPS = np.float32(1e-12)    # torch.nn.functional.normalize's eps
 
 
@@ -398,6 +399,8 @@ class Reader(BaseReader):
         self._last_norms_kernel = ''
         self._last_pairs_kernel = ''
         self._last_bag_pairs_kernel = ''
+        self._last_query_kernel = ''
+        self._whole_group_offsets = None   # ((n, device), the device tensor [0, n]) of query_similarity_device(offsets=None)
 
     @property
     def _word_batch(self):
@@ -1034,6 +1037,187 @@ class Reader(BaseReader):
             cosines[start:stop], dots[start:stop], norms[start:stop] = pair_similarity_host(pooled[0::2], pooled[1::2])
         if return_dots or return_norms:
             return cosines, dots if return_dots else None, norms if return_norms else None
+        return cosines
+
+    @property
+    def last_query_kernel(self):
+        '''The kernel family of the last query_similarity_device call: 'query_trained' (fused with the decode) or
+        'pairs_dense' behind a plain decode of the candidates -- uniform and full storage, dims that are no multiple of 4
+        or beyond 512. '' before any call. Informational: the bits are the same.'''
+        return self._last_query_kernel
+
+    def query_similarity_device(self, queries, rows, offsets=None, *, return_dots=False, return_norms=False, out=None):
+        '''The cosine similarity of query vectors against groups of candidate rows, left on the GPU: a float32 (n,) tensor,
+        cos[i] of query g and the row rows[i] for every entry i of group g -- one vector (a row, a difference of rows, a
+        centroid, a pooled sentence) against a list of candidate words. For trained models whose dim is a multiple of 4 and
+        at most 512 ONE kernel computes it from the compressed rows, a wavefront keeping its group's query in registers,
+        and writes no row; otherwise slices of at most 2^19 candidates are decoded beside their queries into a temporary
+        and reduced there (last_query_kernel says which). Bit for bit the contract of include/memb_hip_queries.h:
+        pair_similarity_device's reduction over (query g, rows_embedding_device(rows)[i]) -- whichever kernel ran. Not
+        clamped. A candidate that is not in the model has cosine 0. For the k best, torch.topk of the result.
+        queries : float32 tensor of shape (G, dim), or (dim,) for one query, on this reader's device; rows may be strided
+            (stride >= dim), the last dimension must be contiguous
+        rows : as in rows_embedding_device, the n candidates of every group one after the other
+        offsets : contiguous int32 / uint32 tensor of G + 1 ascending entries on the device, as in bags_embedding_device:
+            group g owns the entries [min(offsets[g], n), min(offsets[g + 1], n)); None: one group of all rows (G == 1;
+            the two offsets are copied to the device on the first call with that many rows and kept)
+        return_dots, return_norms : either one returns (cosines, dots, norms) instead, dots a float32 (n,) tensor and norms
+            the pair (query_norms (G,), row_norms (n,)) -- row_norms_device's of the candidates --, None where not asked for
+        out : optional contiguous float32 (n,) tensor on the same device for the cosines; an entry that lies in no group is
+            not written (it holds +0.0 in the tensors this method allocates)
+        One model, float32: no top-k, no (G, n) matrix of every query against one list, no bfloat16 / float16, no
+        ReadersUnion, no ShardedReader.'''
+        import torch
+        index, device = self._norms_arguments(torch, rows)
+        dim = self.dim
+        if not isinstance(queries, torch.Tensor) or queries.dtype != torch.float32:
+            raise TypeError('queries must be a float32 tensor of shape (G, dim) or (dim,)')
+        if queries.device.type != 'cuda':
+            raise TypeError('queries must be on the GPU')
+        if queries.dim() == 1:
+            queries = queries.unsqueeze(0)
+        if queries.dim() != 2 or queries.shape[1] != dim:
+            raise ValueError('queries must have shape (G, {}) or ({},), got {}'.format(dim, dim, tuple(queries.shape)))
+        groups = queries.shape[0]
+        if (dim > 1 and queries.stride(1) != 1) or (groups > 1 and queries.stride(0) < dim):
+            raise ValueError('queries must have a contiguous last dimension and a row stride of at least dim')
+        ld = queries.stride(0) if groups > 1 else dim
+        n = rows.numel()
+        covered = offsets is None
+        if covered:
+            if groups != 1:
+                raise ValueError('offsets=None means one group of all rows: queries must hold one query, got {}'.format(groups))
+            # (kept from the last call with this many rows: repeated calls copy and allocate nothing)
+            kept = self._whole_group_offsets
+            if kept is None or kept[0] != (n, device):
+                kept = ((n, device), torch.from_numpy(np.array([0, n], dtype=np.uint32).view(np.int32)).to(device))
+                self._whole_group_offsets = kept
+            offsets = kept[1]
+        elif (not isinstance(offsets, torch.Tensor) or offsets.device.type != 'cuda' or offsets.dtype not in (torch.int32, torch.uint32)
+                or not offsets.is_contiguous() or offsets.dim() != 1):
+            raise TypeError('offsets must be a contiguous int32/uint32 tensor of G + 1 entries on the GPU')
+        if offsets.numel() != groups + 1:
+            raise ValueError('offsets needs G + 1 = {} entries, got {}'.format(groups + 1, offsets.numel()))
+        allocate = torch.empty if covered else torch.zeros
+        if out is None:
+            out = allocate((n,), dtype=torch.float32, device=device)
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.dim() != 1 or out.shape[0] != n or not out.is_contiguous():
+            raise TypeError('out must be a contiguous float32 (n,) tensor')
+        if device.index != index or out.device != device or offsets.device != device or queries.device != device:
+            raise ValueError('queries, rows, offsets and out must be on cuda:{} (the device this reader is staged on), got {}, {}, {} and {}'.format(
+                self.device, queries.device, device, offsets.device, out.device))
+        dots = allocate((n,), dtype=torch.float32, device=device) if return_dots else None
+        row_norms = allocate((n,), dtype=torch.float32, device=device) if return_norms else None
+        stream = _current_stream(torch, index)
+        norms = None
+        if return_norms:
+            query_norms = torch.empty((groups,), dtype=torch.float32, device=device)
+            if groups:
+                _memb.dense_row_norms_to_device(index, queries.data_ptr(), groups, dim, ld, query_norms.data_ptr(), stream)
+            norms = (query_norms, row_norms)
+        result = (out, dots, norms) if return_dots or return_norms else out
+        if n == 0 or groups == 0:   # (nothing to score: the C call would see three null outputs where n == 0)
+            self._last_query_kernel = self._impl.query_kernel_name() or _memb.dense_pairs_kernel_name()
+            return result
+        if self._impl.query_similarity_to_device(
+                queries.data_ptr(), groups, ld, rows.data_ptr(), n, offsets.data_ptr(), out.data_ptr(),
+                dots.data_ptr() if return_dots else 0, row_norms.data_ptr() if return_norms else 0, stream):
+            self._last_query_kernel = self._impl.query_kernel_name()
+            return result
+        self._last_query_kernel = _memb.dense_pairs_kernel_name()
+        flat = rows.reshape(-1)
+        # the entry-to-group map on the device: entry i lies in the last group whose clamped offset is <= i
+        clamped = torch.clamp(offsets.view(torch.int32).to(torch.int64) & 0xFFFFFFFF, max=n)
+        width = min(n, QUERY_DEVICE_SLICE)
+        temporary = torch.empty((width, 2, dim), dtype=torch.float32, device=device)
+        scalars = torch.empty((4, width), dtype=torch.float32, device=device)   # cosines, dots, the (width, 2) norms
+        for start in range(0, n, QUERY_DEVICE_SLICE):
+            stop = min(n, start + QUERY_DEVICE_SLICE)
+            count = stop - start
+            group = torch.searchsorted(clamped, torch.arange(start, stop, device=device), right=True) - 1
+            inside = (group >= 0) & (group < groups)
+            temporary[:count, 0] = queries[torch.clamp(group, 0, groups - 1)]
+            self.rows_embedding_device(flat[start:stop], out=temporary.view(width, 2 * dim)[:count], col_off=dim)
+            pair_norms = scalars[2:].reshape(-1)[:2 * count].view(count, 2)
+            _memb.dense_pair_similarity_to_device(
+                index, temporary.data_ptr(), count, dim, dim, scalars[0].data_ptr(), scalars[1].data_ptr(),
+                pair_norms.data_ptr(), stream)
+            for target, values in ((out, scalars[0, :count]), (dots, scalars[1, :count]), (row_norms, pair_norms[:, 1])):
+                if target is not None:
+                    target[start:stop] = torch.where(inside, values, target[start:stop])
+        return result
+
+    def candidates_similarity_device(self, words, candidate_lists):
+        '''The cosine similarity of words[g] and each word of candidate_lists[g], on the GPU: (cosines, offsets), cosines a
+        float32 (n,) tensor over the candidates of every list one after the other and offsets the int32 tensor of
+        len(words) + 1 entries that says where each list begins among them. The query words and the flattened candidates
+        (flatten_sentences) are resolved on the device (resolve_rows_device), the query rows decoded by
+        rows_embedding_device, the rest is query_similarity_device. An unknown word -- query or candidate -- gives 0.'''
+        import torch
+        if len(words) != len(candidate_lists):
+            raise ValueError('one list of candidates per word: got {} words and {} lists'.format(len(words), len(candidate_lists)))
+        index = self._impl.device()
+        if index == _memb.HOST_DEVICE:
+            raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
+        device = 'cuda:{}'.format(index)
+        candidates, offsets = flatten_sentences(candidate_lists)
+        on_device = torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).to(device)
+        if not words:
+            return torch.zeros((0,), dtype=torch.float32, device=device), on_device
+        queries = self.rows_embedding_device(self.resolve_rows_device(list(words)))
+        rows = self.resolve_rows_device(candidates) if candidates else torch.empty((0,), dtype=torch.int32, device=device)
+        return self.query_similarity_device(queries, rows, on_device), on_device
+
+    def query_similarity(self, queries, rows, offsets=None, return_dots=False, return_norms=False):
+        '''query_similarity_device for host arrays: a numpy float32 (G, dim) or (dim,) array of queries, numpy row ids and
+        G + 1 offsets (bags_embedding's: ascending, within 0 .. len(rows); None: one group of all rows) in, a numpy float32
+        (n,) array of cosines out, or (cosines, dots, (query_norms, row_norms)) with either flag (None where not asked
+        for). A reader on a GPU sends everything up and brings the scalars back; a device='cpu' reader evaluates the same
+        contract in numpy (pair_similarity_host over rows_embedding) in bounded slices: the same bits. An entry that lies
+        in no group is +0.0.'''
+        queries = np.asarray(queries)
+        if queries.dtype != np.float32:
+            raise TypeError('queries must be a float32 array of shape (G, dim) or (dim,)')
+        if queries.ndim == 1:
+            queries = queries[None, :]
+        if queries.ndim != 2 or queries.shape[1] != self.dim:
+            raise ValueError('queries must have shape (G, {}) or ({},), got {}'.format(self.dim, self.dim, queries.shape))
+        queries = np.ascontiguousarray(queries)
+        groups = queries.shape[0]
+        rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        n = rows.size
+        if offsets is None:
+            if groups != 1:
+                raise ValueError('offsets=None means one group of all rows: queries must hold one query, got {}'.format(groups))
+            offsets = np.array([0, n], dtype=np.int64)
+        offsets = bag_offsets(offsets, n)
+        if offsets.size != groups + 1:
+            raise ValueError('offsets needs G + 1 = {} entries, got {}'.format(groups + 1, offsets.size))
+        if self._impl.device() != _memb.HOST_DEVICE:
+            import torch
+            device = 'cuda:{}'.format(self._impl.device())
+            result = self.query_similarity_device(
+                torch.from_numpy(queries).to(device), torch.from_numpy(rows.view(np.int32)).to(device),
+                torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).to(device), return_dots=return_dots,
+                return_norms=return_norms)
+            if not (return_dots or return_norms):
+                return result.cpu().numpy()
+            cosines, dots, norms = result
+            return (cosines.cpu().numpy(), None if dots is None else dots.cpu().numpy(),
+                    None if norms is None else tuple(part.cpu().numpy() for part in norms))
+        cosines = np.zeros(n, dtype=np.float32)
+        dots = np.zeros(n, dtype=np.float32)
+        row_norms = np.zeros(n, dtype=np.float32)
+        group = np.searchsorted(offsets.astype(np.int64), np.arange(n, dtype=np.int64), side='right') - 1
+        inside = (group >= 0) & (group < groups)
+        for start in range(0, n, NORMS_HOST_CHUNK):
+            chosen = start + np.flatnonzero(inside[start:start + NORMS_HOST_CHUNK])
+            if chosen.size:
+                cosines[chosen], dots[chosen], norms = pair_similarity_host(queries[group[chosen]], self.rows_embedding(rows[chosen]))
+                row_norms[chosen] = norms[:, 1]
+        if return_dots or return_norms:
+            return (cosines, dots if return_dots else None,
+                    (row_norms_host(queries) if groups else np.zeros(0, dtype=np.float32), row_norms) if return_norms else None)
         return cosines
 
     def stage_words(self):
