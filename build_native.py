@@ -68,7 +68,7 @@ def build_hip_library(force=False, extra_flags=()):
             os.path.join(CSRC, 'memb_hip_pooled.hip'), os.path.join(CSRC, 'memb_hip_pooled_chunked.hip'),
             os.path.join(CSRC, 'memb_hip_pooled_union.hip'), os.path.join(CSRC, 'memb_hip_norms.hip'),
             os.path.join(CSRC, 'memb_hip_pairs.hip'), os.path.join(CSRC, 'memb_hip_bag_pairs.hip'),
-            os.path.join(CSRC, 'memb_hip_queries.hip'),
+            os.path.join(CSRC, 'memb_hip_queries.hip'), os.path.join(CSRC, 'memb_hip_query_matrix.hip'),
         ])
     return HIP_LIBRARY
 

@@ -12,6 +12,8 @@
 #include "../../include/memb_hip_pairs.h"
 #include "../../include/memb_hip_bag_pairs.h"
 #include "../../include/memb_hip_queries.h"
+#include "../../include/memb_hip_query_matrix.h"
+#include "hip_query_matrix.h"
 
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -1256,8 +1258,63 @@ PYBIND11_MODULE(_memb, m) {
             py::arg("offsets"),
             py::arg("cosines") = true,
             py::arg("dots") = false,
+            py::arg("norms") = false)
+        // include/memb_hip_query_matrix.h. Device pointers: n_queries fp32 query rows ld_queries floats apart, n candidate
+        // row ids every query shares; cosines and dots are (n_queries, n) matrices with rows ld_out floats apart, norms n
+        // floats; each of the three may be 0. False where the fused kernel does not exist for this model
+        // (MEMB_HIP_UNSUPPORTED): the caller decodes the candidates and calls dense_pair_similarity_to_device.
+        .def(
+            "query_matrix_to_device",
+            [](memb::Reader& reader, uintptr_t queries, size_t nQueries, size_t ldQueries, uintptr_t rows, size_t n,
+               uintptr_t cosines, uintptr_t dots, size_t ldOut, uintptr_t norms, uintptr_t stream)
+            {
+                const int code = memb_hip_query_matrix_device(
+                    reader.deviceContext(), reinterpret_cast<const float*>(queries), nQueries, ldQueries,
+                    reinterpret_cast<const uint32_t*>(rows), n, reinterpret_cast<float*>(cosines), reinterpret_cast<float*>(dots),
+                    ldOut, reinterpret_cast<float*>(norms), reinterpret_cast<void*>(stream));
+                if (code == MEMB_HIP_UNSUPPORTED) {
+                    return false;
+                }
+                if (code != MEMB_HIP_OK) {
+                    throw std::runtime_error(std::string("memb_hip_query_matrix_device: ") + memb_hip_last_error());
+                }
+                return true;
+            },
+            py::arg("queries_ptr"),
+            py::arg("n_queries"),
+            py::arg("ld_queries"),
+            py::arg("rows_ptr"),
+            py::arg("n"),
+            py::arg("cosines_ptr"),
+            py::arg("dots_ptr"),
+            py::arg("ld_out"),
+            py::arg("norms_ptr") = 0,
+            py::arg("stream") = 0)
+        // the kernel family query_matrix_to_device launches, '' where it returns False
+        .def(
+            "query_matrix_kernel_name",
+            [](memb::Reader& reader) { return std::string(memb_hip_query_matrix_kernel_name(reader.deviceContext())); })
+        .def(
+            "query_matrix_algorithmic_bytes",
+            [](memb::Reader& reader, py::array_t<uint32_t, py::array::c_style | py::array::forcecast> rows, size_t nQueries,
+               bool cosines, bool dots, bool norms)
+            {
+                uint64_t bytes = 0;
+                if (memb_hip_query_matrix_algorithmic_bytes(
+                        reader.deviceContext(), rows.data(), static_cast<size_t>(rows.size()), nQueries, cosines ? 1 : 0,
+                        dots ? 1 : 0, norms ? 1 : 0, &bytes) != MEMB_HIP_OK) {
+                    throw std::runtime_error(std::string("memb_hip_query_matrix_algorithmic_bytes: ") + memb_hip_last_error());
+                }
+                return bytes;
+            },
+            py::arg("rows"),
+            py::arg("n_queries"),
+            py::arg("cosines") = true,
+            py::arg("dots") = false,
             py::arg("norms") = false);
 
+    // queries query_matrix_trained holds in registers at once (hip_query_matrix.h): geometry, never the result
+    m.attr("QUERY_MATRIX_BLOCK") = memb_query_matrix::QUERY_BLOCK;
     m.attr("OUT_F32") = MEMB_HIP_OUT_F32;
     m.attr("OUT_BF16") = MEMB_HIP_OUT_BF16;
     m.attr("OUT_F16") = MEMB_HIP_OUT_F16;

@@ -47,7 +47,8 @@
 // memb_hip_pairs.hip -- the cosine similarity of pairs of rows (hip_pairs.h), launched by hip_pairs_launch.h likewise;
 // memb_hip_bag_pairs.hip -- that of pairs of pooled bags (hip_bag_pairs.h), launched by hip_bag_pairs_launch.h;
 // memb_hip_queries.hip -- that of query vectors against groups of candidate rows (hip_queries.h), launched by
-// hip_queries_launch.h.
+// hip_queries_launch.h; memb_hip_query_matrix.hip -- that of every query against one shared candidate list
+// (hip_query_matrix.h), launched by hip_query_matrix_launch.h.
 #include <hip/hip_runtime.h>
 
 #include "../../include/memb_hip.h"
@@ -60,6 +61,7 @@
 #include "../../include/memb_hip_pairs.h"
 #include "../../include/memb_hip_bag_pairs.h"
 #include "../../include/memb_hip_queries.h"
+#include "../../include/memb_hip_query_matrix.h"
 #include "codec.h"
 #include "hip_narrow.h"
 #include "hip_pooled.h"
@@ -69,6 +71,7 @@
 #include "hip_pairs.h"
 #include "hip_bag_pairs.h"
 #include "hip_queries.h"
+#include "hip_query_matrix.h"
 #include "wire.h"
 #include "worker_pool.h"
 
@@ -144,6 +147,7 @@ namespace {
 #include "hip_pairs_launch.h"
 #include "hip_bag_pairs_launch.h"
 #include "hip_queries_launch.h"
+#include "hip_query_matrix_launch.h"
 
 // No C++ exception leaves the library: allocation failures and the like become error codes.
 template <typename Call>
@@ -443,6 +447,28 @@ int memb_hip_query_algorithmic_bytes(
 {
     return guarded([&] {
         return query_algorithmic_bytes_checked(ctx, rows, n, offsets, groups, cosines != 0, dots != 0, norms != 0, bytes);
+    });
+}
+
+int memb_hip_query_matrix_device(
+    memb_hip_ctx* ctx, const float* queries, size_t n_queries, size_t ld_queries, const uint32_t* rows, size_t n, float* cosines,
+    float* dots, size_t ld_out, float* norms, void* stream)
+{
+    return guarded([&] {
+        return query_matrix_device_checked(ctx, queries, n_queries, ld_queries, rows, n, cosines, dots, ld_out, norms, stream);
+    });
+}
+
+const char* memb_hip_query_matrix_kernel_name(const memb_hip_ctx* ctx)
+{
+    return query_matrix_kernel_name(ctx);
+}
+
+int memb_hip_query_matrix_algorithmic_bytes(
+    const memb_hip_ctx* ctx, const uint32_t* rows, size_t n, size_t n_queries, int cosines, int dots, int norms, uint64_t* bytes)
+{
+    return guarded([&] {
+        return query_matrix_algorithmic_bytes_checked(ctx, rows, n, n_queries, cosines != 0, dots != 0, norms != 0, bytes);
     });
 }
 

@@ -400,6 +400,7 @@ class Reader(BaseReader):
         self._last_pairs_kernel = ''
         self._last_bag_pairs_kernel = ''
         self._last_query_kernel = ''
+        self._last_query_matrix_kernel = ''
         self._whole_group_offsets = None   # ((n, device), the device tensor [0, n]) of query_similarity_device(offsets=None)
 
     @property
@@ -1065,8 +1066,8 @@ class Reader(BaseReader):
             the pair (query_norms (G,), row_norms (n,)) -- row_norms_device's of the candidates --, None where not asked for
         out : optional contiguous float32 (n,) tensor on the same device for the cosines; an entry that lies in no group is
             not written (it holds +0.0 in the tensors this method allocates)
-        One model, float32: no top-k, no (G, n) matrix of every query against one list, no bfloat16 / float16, no
-        ReadersUnion, no ShardedReader.'''
+        One model, float32: no top-k, no bfloat16 / float16, no ReadersUnion, no ShardedReader. Every query against ONE
+        shared list, a (G, n) matrix, is similarity_matrix_device.'''
         import torch
         index, device = self._norms_arguments(torch, rows)
         dim = self.dim
@@ -1218,6 +1219,157 @@ class Reader(BaseReader):
         if return_dots or return_norms:
             return (cosines, dots if return_dots else None,
                     (row_norms_host(queries) if groups else np.zeros(0, dtype=np.float32), row_norms) if return_norms else None)
+        return cosines
+
+    @property
+    def last_query_matrix_kernel(self):
+        '''The kernel family of the last similarity_matrix_device call: 'query_matrix_trained' (fused with the decode) or
+        'pairs_dense' behind a plain decode of the candidates -- uniform and full storage, dims that are no multiple of 4
+        or beyond 512. '' before any call. Informational: the bits are the same.'''
+        return self._last_query_matrix_kernel
+
+    def similarity_matrix_device(self, queries, rows, *, return_dots=False, return_norms=False, out=None):
+        '''The cosine similarity of EVERY query vector against EVERY row of one shared candidate list, left on the GPU: a
+        float32 (Q, n) tensor, cos[q, i] of query q and the row rows[i] -- a batch of analogy questions against the
+        vocabulary, the neighbours of a few dozen words at once, a word-by-word matrix over a word list. For trained models
+        whose dim is a multiple of 4 and at most 512 ONE kernel decodes every compressed row once, whatever Q is, scores it
+        against all queries and writes no row; otherwise slices of at most 2^19 candidates are decoded once into a
+        temporary and reduced there against one query after the other (last_query_matrix_kernel says which). Bit for bit
+        the contract of include/memb_hip_query_matrix.h: row q is query_similarity_device(queries[q], rows) -- whichever
+        kernel ran. Not clamped. A candidate that is not in the model has cosine 0. For the k best, torch.topk of the result.
+        A matrix multiply over decoded rows is faster from some Q on, at other bits; this method never switches to it.
+        queries : float32 tensor of shape (Q, dim), or (dim,) for one query, on this reader's device; rows may be strided
+            (stride >= dim), the last dimension must be contiguous
+        rows : as in rows_embedding_device, the n candidates every query shares
+        return_dots, return_norms : either one returns (cosines, dots, norms) instead, dots a float32 (Q, n) tensor and norms
+            the pair (query_norms (Q,), row_norms (n,)) -- row_norms_device's of the candidates --, None where not asked for
+        out : optional float32 (Q, n) tensor on the same device for the cosines, with a contiguous last dimension and a row
+            stride of at least n; nothing between its rows is written
+        One model, float32: no top-k, no bfloat16 / float16, no ReadersUnion, no ShardedReader.'''
+        import torch
+        index, device = self._norms_arguments(torch, rows)
+        dim = self.dim
+        if not isinstance(queries, torch.Tensor) or queries.dtype != torch.float32:
+            raise TypeError('queries must be a float32 tensor of shape (Q, dim) or (dim,)')
+        if queries.device.type != 'cuda':
+            raise TypeError('queries must be on the GPU')
+        if queries.dim() == 1:
+            queries = queries.unsqueeze(0)
+        if queries.dim() != 2 or queries.shape[1] != dim:
+            raise ValueError('queries must have shape (Q, {}) or ({},), got {}'.format(dim, dim, tuple(queries.shape)))
+        count = queries.shape[0]
+        if (dim > 1 and queries.stride(1) != 1) or (count > 1 and queries.stride(0) < dim):
+            raise ValueError('queries must have a contiguous last dimension and a row stride of at least dim')
+        ld = queries.stride(0) if count > 1 else dim
+        n = rows.numel()
+        if out is None:
+            out = torch.empty((count, n), dtype=torch.float32, device=device)
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.dim() != 2 or tuple(out.shape) != (count, n):
+            raise TypeError('out must be a float32 (Q, n) tensor')
+        if (n > 1 and out.stride(1) != 1) or (count > 1 and out.stride(0) < n):
+            raise ValueError('out must have a contiguous last dimension and a row stride of at least n')
+        if device.index != index or out.device != device or queries.device != device:
+            raise ValueError('queries, rows and out must be on cuda:{} (the device this reader is staged on), got {}, {} and {}'.format(
+                self.device, queries.device, device, out.device))
+        ld_out = out.stride(0) if count > 1 else n
+        dots = torch.empty((count, n), dtype=torch.float32, device=device) if return_dots else None
+        row_norms = torch.empty((n,), dtype=torch.float32, device=device) if return_norms else None
+        stream = _current_stream(torch, index)
+        norms = None
+        if return_norms:
+            query_norms = torch.empty((count,), dtype=torch.float32, device=device)
+            if count:
+                _memb.dense_row_norms_to_device(index, queries.data_ptr(), count, dim, ld, query_norms.data_ptr(), stream)
+            norms = (query_norms, row_norms)
+        result = (out, dots, norms) if return_dots or return_norms else out
+        if n == 0:
+            self._last_query_matrix_kernel = self._impl.query_matrix_kernel_name() or _memb.dense_pairs_kernel_name()
+            return result
+        if count == 0:   # (no query: the candidates' norms are all there is to work out)
+            if return_norms:
+                self.row_norms_device(rows.reshape(-1), out=row_norms)
+            self._last_query_matrix_kernel = self._impl.query_matrix_kernel_name() or _memb.dense_pairs_kernel_name()
+            return result
+        if self._impl.query_matrix_to_device(
+                queries.data_ptr(), count, ld, rows.data_ptr(), n, out.data_ptr(), dots.data_ptr() if return_dots else 0,
+                ld_out, row_norms.data_ptr() if return_norms else 0, stream):
+            self._last_query_matrix_kernel = self._impl.query_matrix_kernel_name()
+            return result
+        self._last_query_matrix_kernel = _memb.dense_pairs_kernel_name()
+        flat = rows.reshape(-1)
+        width = min(n, QUERY_DEVICE_SLICE)
+        temporary = torch.empty((width, 2, dim), dtype=torch.float32, device=device)   # (query, decoded row) side by side
+        pair_norms = torch.empty((width, 2), dtype=torch.float32, device=device)
+        for start in range(0, n, QUERY_DEVICE_SLICE):
+            stop = min(n, start + QUERY_DEVICE_SLICE)
+            size = stop - start
+            # the slice is decoded ONCE; every query is then written beside the same decoded rows
+            self.rows_embedding_device(flat[start:stop], out=temporary.view(width, 2 * dim)[:size], col_off=dim)
+            for q in range(count):
+                temporary[:size, 0] = queries[q]
+                _memb.dense_pair_similarity_to_device(
+                    index, temporary.data_ptr(), size, dim, dim, out[q, start:stop].data_ptr(),
+                    dots[q, start:stop].data_ptr() if return_dots else 0,
+                    pair_norms.data_ptr() if return_norms and q == 0 else 0, stream)
+                if return_norms and q == 0:
+                    row_norms[start:stop] = pair_norms[:size, 1]
+        return result
+
+    def words_similarity_matrix_device(self, words_a, words_b):
+        '''The cosine similarity of every word of words_a against every word of words_b, a float32
+        (len(words_a), len(words_b)) tensor on the GPU: both lists resolved by resolve_rows_device, the rows of words_a
+        decoded by rows_embedding_device as the queries, the rest is similarity_matrix_device. An unknown word -- on either
+        side -- gives 0.'''
+        import torch
+        index = self._impl.device()
+        if index == _memb.HOST_DEVICE:
+            raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
+        device = 'cuda:{}'.format(index)
+        if not len(words_a) or not len(words_b):
+            return torch.zeros((len(words_a), len(words_b)), dtype=torch.float32, device=device)
+        queries = self.rows_embedding_device(self.resolve_rows_device(list(words_a)))
+        return self.similarity_matrix_device(queries, self.resolve_rows_device(list(words_b)))
+
+    def similarity_matrix(self, queries, rows, return_dots=False, return_norms=False):
+        '''similarity_matrix_device for host arrays: a numpy float32 (Q, dim) or (dim,) array of queries and numpy row ids
+        in, a numpy float32 (Q, n) array of cosines out, or (cosines, dots, (query_norms, row_norms)) with either flag (None
+        where not asked for). A reader on a GPU sends everything up and brings the matrix back; a device='cpu' reader
+        evaluates the same contract in numpy (pair_similarity_host over rows_embedding) in bounded slices, each slice
+        decoded once for every query: the same bits.'''
+        queries = np.asarray(queries)
+        if queries.dtype != np.float32:
+            raise TypeError('queries must be a float32 array of shape (Q, dim) or (dim,)')
+        if queries.ndim == 1:
+            queries = queries[None, :]
+        if queries.ndim != 2 or queries.shape[1] != self.dim:
+            raise ValueError('queries must have shape (Q, {}) or ({},), got {}'.format(self.dim, self.dim, queries.shape))
+        queries = np.ascontiguousarray(queries)
+        count = queries.shape[0]
+        rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        n = rows.size
+        if self._impl.device() != _memb.HOST_DEVICE:
+            import torch
+            device = 'cuda:{}'.format(self._impl.device())
+            result = self.similarity_matrix_device(
+                torch.from_numpy(queries).to(device), torch.from_numpy(rows.view(np.int32)).to(device),
+                return_dots=return_dots, return_norms=return_norms)
+            if not (return_dots or return_norms):
+                return result.cpu().numpy()
+            cosines, dots, norms = result
+            return (cosines.cpu().numpy(), None if dots is None else dots.cpu().numpy(),
+                    None if norms is None else tuple(part.cpu().numpy() for part in norms))
+        cosines = np.zeros((count, n), dtype=np.float32)
+        dots = np.zeros((count, n), dtype=np.float32)
+        row_norms = np.zeros(n, dtype=np.float32)
+        for start in range(0, n, NORMS_HOST_CHUNK):
+            values = self.rows_embedding(rows[start:start + NORMS_HOST_CHUNK])
+            stop = start + len(values)
+            row_norms[start:stop] = row_norms_host(values)
+            for q in range(count):
+                cosines[q, start:stop], dots[q, start:stop], _ = pair_similarity_host(np.broadcast_to(queries[q], values.shape), values)
+        if return_dots or return_norms:
+            return (cosines, dots if return_dots else None,
+                    (row_norms_host(queries) if count else np.zeros(0, dtype=np.float32), row_norms) if return_norms else None)
         return cosines
 
     def stage_words(self):

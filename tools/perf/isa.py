@@ -2,7 +2,7 @@
 registers, scratch and LDS, read from the device assembly (no GPU needed).
 
     python tools/perf/isa.py [substring of the demangled kernel name] [-- extra hipcc flags]
-    python tools/perf/isa.py --digests     one line per kernel of every translation unit of libmemb_hip.so (EVERY_SOURCE),
+    python tools/perf/isa.py --digests     one line per kernel of every translation unit of libmemb_hip.so (WHOLE_LIBRARY),
                                            instruction digest and resources: run it on two commits and diff the listings
                                            to see which kernels a change touched
 
@@ -35,9 +35,13 @@ ALL_SOURCES = SOURCES + (PAIRS_SOURCE,)
 BAG_PAIRS_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_bag_pairs.hip')
 LIBRARY_SOURCES = ALL_SOURCES + (BAG_PAIRS_SOURCE,)
 # the query kernel's unit, kept out of LIBRARY_SOURCES likewise (tests/test_bag_pairs_isa.py pins it); EVERY_SOURCE is every
-# translation unit of the library, and what --digests lists
+# translation unit of the library before the query-matrix unit, and what --digests listed then
 QUERIES_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_queries.hip')
 EVERY_SOURCE = LIBRARY_SOURCES + (QUERIES_SOURCE,)
+# the query-matrix kernel's unit, kept out of EVERY_SOURCE likewise (tests/test_queries_isa.py pins it); WHOLE_LIBRARY is
+# every translation unit of the library, and what --digests lists
+QUERY_MATRIX_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_query_matrix.hip')
+WHOLE_LIBRARY = EVERY_SOURCE + (QUERY_MATRIX_SOURCE,)
 # the flags of build_native.build_hip_library
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt',
          '-Wno-unused-value', '-Wno-align-mismatch', '-Wno-pass-failed', '-Wno-unused-command-line-argument']
@@ -71,7 +75,7 @@ def _instructions(code, symbol):
 def kernel_table(extra_flags=(), source=SOURCE):
     """{demangled kernel name: facts} for every kernel of one translation unit of libmemb_hip.so (default memb_hip.hip;
     NARROW_SOURCE: the bf16 / fp16 decode kernels; POOLED_SOURCE: every sequential pooled kernel; POOLED_CHUNKED_SOURCE: the
-    chunked order's; POOLED_UNION_SOURCE: the pooled kernels of averaged unions and of dense rows; NORMS_SOURCE: row norms and unit rows; PAIRS_SOURCE: the cosine of row pairs; BAG_PAIRS_SOURCE: the cosine of pairs of pooled bags; QUERIES_SOURCE: the cosine of query vectors against groups of rows; or any other path, such as a unit of another checkout)"""
+    chunked order's; POOLED_UNION_SOURCE: the pooled kernels of averaged unions and of dense rows; NORMS_SOURCE: row norms and unit rows; PAIRS_SOURCE: the cosine of row pairs; BAG_PAIRS_SOURCE: the cosine of pairs of pooled bags; QUERIES_SOURCE: the cosine of query vectors against groups of rows; QUERY_MATRIX_SOURCE: the cosine of every query against one shared list of rows; or any other path, such as a unit of another checkout)"""
     text = device_assembly(extra_flags, source)
     names = re.findall(r'^\s*\.amdhsa_kernel (\S+)$', text, flags=re.M)
     demangled = subprocess.run([_tool('c++filt')], input='\n'.join(names), stdout=subprocess.PIPE, text=True,
@@ -146,7 +150,7 @@ if __name__ == '__main__':
         extra = arguments[arguments.index('--') + 1:]
         arguments = arguments[:arguments.index('--')]
     if arguments[:1] == ['--digests']:   # one line per kernel, to diff against another commit's; [units of that commit]
-        for pretty, facts in sorted(kernel_digests(arguments[1:] or EVERY_SOURCE).items()):
+        for pretty, facts in sorted(kernel_digests(arguments[1:] or WHOLE_LIBRARY).items()):
             print(pretty.replace('(anonymous namespace)::', '').split('(')[0], *facts)
         sys.exit(0)
     needle = arguments[0] if arguments else ''
