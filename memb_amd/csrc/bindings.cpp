@@ -14,6 +14,8 @@
 #include "../../include/memb_hip_queries.h"
 #include "../../include/memb_hip_query_matrix.h"
 #include "hip_query_matrix.h"
+#include "../../include/memb_hip_query_topk.h"
+#include "hip_query_topk.h"
 
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -1311,7 +1313,108 @@ PYBIND11_MODULE(_memb, m) {
             py::arg("n_queries"),
             py::arg("cosines") = true,
             py::arg("dots") = false,
-            py::arg("norms") = false);
+            py::arg("norms") = false)
+        // include/memb_hip_query_topk.h. Device pointers: the queries and candidates of query_matrix_to_device, k values
+        // (float32) and k positions (int64) per query with rows ld_out elements apart, and a workspace of at least
+        // query_topk_workspace_bytes(.., minimal=True) bytes, which decides the slicing. False where the fused kernel does
+        // not exist for this model (MEMB_HIP_UNSUPPORTED): the caller takes the matrix in slices and calls
+        // dense_topk_to_device with merge.
+        .def(
+            "query_topk_to_device",
+            [](memb::Reader& reader, uintptr_t queries, size_t nQueries, size_t ldQueries, uintptr_t rows, size_t n, uint32_t k,
+               uintptr_t values, uintptr_t positions, size_t ldOut, uintptr_t workspace, size_t workspaceBytes, uintptr_t stream)
+            {
+                const int code = memb_hip_query_topk_device(
+                    reader.deviceContext(), reinterpret_cast<const float*>(queries), nQueries, ldQueries,
+                    reinterpret_cast<const uint32_t*>(rows), n, k, reinterpret_cast<float*>(values),
+                    reinterpret_cast<int64_t*>(positions), ldOut, reinterpret_cast<void*>(workspace), workspaceBytes,
+                    reinterpret_cast<void*>(stream));
+                if (code == MEMB_HIP_UNSUPPORTED) {
+                    return false;
+                }
+                if (code != MEMB_HIP_OK) {
+                    throw std::runtime_error(std::string("memb_hip_query_topk_device: ") + memb_hip_last_error());
+                }
+                return true;
+            },
+            py::arg("queries_ptr"),
+            py::arg("n_queries"),
+            py::arg("ld_queries"),
+            py::arg("rows_ptr"),
+            py::arg("n"),
+            py::arg("k"),
+            py::arg("values_ptr"),
+            py::arg("positions_ptr"),
+            py::arg("ld_out"),
+            py::arg("workspace_ptr"),
+            py::arg("workspace_bytes"),
+            py::arg("stream") = 0)
+        .def(
+            "query_topk_workspace_bytes",
+            [](memb::Reader& reader, size_t nQueries, size_t n, uint32_t k, bool minimal) {
+                return memb_hip_query_topk_workspace_bytes(reader.deviceContext(), nQueries, n, k, minimal ? 1 : 0);
+            },
+            py::arg("n_queries"),
+            py::arg("n"),
+            py::arg("k"),
+            py::arg("minimal") = false)
+        // the kernel families query_topk_to_device launches, '' where it returns False
+        .def(
+            "query_topk_kernel_name",
+            [](memb::Reader& reader) {
+                memb_hip_ctx* ctx = reader.deviceContext();
+                return std::string(ctx ? memb_hip_query_topk_kernel_name(ctx) : "");
+            })
+        .def(
+            "query_topk_algorithmic_bytes",
+            [](memb::Reader& reader, py::array_t<uint32_t, py::array::c_style | py::array::forcecast> rows, size_t nQueries,
+               uint32_t k)
+            {
+                uint64_t bytes = 0;
+                if (memb_hip_query_topk_algorithmic_bytes(
+                        reader.deviceContext(), rows.data(), static_cast<size_t>(rows.size()), nQueries, k, &bytes) != MEMB_HIP_OK) {
+                    throw std::runtime_error(std::string("memb_hip_query_topk_algorithmic_bytes: ") + memb_hip_last_error());
+                }
+                return bytes;
+            },
+            py::arg("rows"),
+            py::arg("n_queries"),
+            py::arg("k"));
+
+    // include/memb_hip_query_topk.h: the k best columns of every row of any fp32 device matrix, positions as base +
+    // column; merge: what values / positions hold takes part. The workspace needs dense_topk_workspace_bytes bytes.
+    m.def(
+        "dense_topk_to_device",
+        [](int device, uintptr_t matrix, size_t nRows, size_t n, size_t ld, int64_t base, uint32_t k, bool merge,
+           uintptr_t values, uintptr_t positions, size_t ldOut, uintptr_t workspace, size_t workspaceBytes, uintptr_t stream)
+        {
+            if (memb_hip_dense_topk_device(
+                    device, reinterpret_cast<const float*>(matrix), nRows, n, ld, base, k, merge ? 1 : 0,
+                    reinterpret_cast<float*>(values), reinterpret_cast<int64_t*>(positions), ldOut,
+                    reinterpret_cast<void*>(workspace), workspaceBytes, reinterpret_cast<void*>(stream)) != MEMB_HIP_OK) {
+                throw std::runtime_error(std::string("memb_hip_dense_topk_device: ") + memb_hip_last_error());
+            }
+        },
+        py::arg("device"),
+        py::arg("matrix_ptr"),
+        py::arg("n_rows"),
+        py::arg("n"),
+        py::arg("ld"),
+        py::arg("base"),
+        py::arg("k"),
+        py::arg("merge"),
+        py::arg("values_ptr"),
+        py::arg("positions_ptr"),
+        py::arg("ld_out"),
+        py::arg("workspace_ptr"),
+        py::arg("workspace_bytes"),
+        py::arg("stream") = 0);
+    m.def("dense_topk_workspace_bytes", &memb_hip_dense_topk_workspace_bytes, py::arg("n_rows"), py::arg("n"), py::arg("k"));
+    m.def("dense_topk_kernel_name", []() { return std::string(memb_hip_query_topk_kernel_name(nullptr)); });
+    m.attr("QUERY_TOPK_MAX_K") = MEMB_HIP_TOPK_MAX_K;
+    // launch geometry of the selection (hip_query_topk.h), never the result: the tests size their matrices by these
+    m.attr("QUERY_TOPK_MIN_SEGMENT") = memb_query_topk::MIN_SEGMENT;
+    m.attr("QUERY_TOPK_MIN_SLICE") = memb_query_topk::MIN_SLICE;
 
     // queries query_matrix_trained holds in registers at once (hip_query_matrix.h): geometry, never the result
     m.attr("QUERY_MATRIX_BLOCK") = memb_query_matrix::QUERY_BLOCK;

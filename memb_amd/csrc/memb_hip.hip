@@ -48,7 +48,8 @@
 // memb_hip_bag_pairs.hip -- that of pairs of pooled bags (hip_bag_pairs.h), launched by hip_bag_pairs_launch.h;
 // memb_hip_queries.hip -- that of query vectors against groups of candidate rows (hip_queries.h), launched by
 // hip_queries_launch.h; memb_hip_query_matrix.hip -- that of every query against one shared candidate list
-// (hip_query_matrix.h), launched by hip_query_matrix_launch.h.
+// (hip_query_matrix.h), launched by hip_query_matrix_launch.h; memb_hip_query_topk.hip -- the k best columns of every row
+// of a matrix (hip_query_topk.h), launched by hip_query_topk_launch.h, slice after slice of the query matrix.
 #include <hip/hip_runtime.h>
 
 #include "../../include/memb_hip.h"
@@ -62,6 +63,7 @@
 #include "../../include/memb_hip_bag_pairs.h"
 #include "../../include/memb_hip_queries.h"
 #include "../../include/memb_hip_query_matrix.h"
+#include "../../include/memb_hip_query_topk.h"
 #include "codec.h"
 #include "hip_narrow.h"
 #include "hip_pooled.h"
@@ -72,6 +74,7 @@
 #include "hip_bag_pairs.h"
 #include "hip_queries.h"
 #include "hip_query_matrix.h"
+#include "hip_query_topk.h"
 #include "wire.h"
 #include "worker_pool.h"
 
@@ -148,6 +151,7 @@ namespace {
 #include "hip_bag_pairs_launch.h"
 #include "hip_queries_launch.h"
 #include "hip_query_matrix_launch.h"
+#include "hip_query_topk_launch.h"
 
 // No C++ exception leaves the library: allocation failures and the like become error codes.
 template <typename Call>
@@ -470,6 +474,47 @@ int memb_hip_query_matrix_algorithmic_bytes(
     return guarded([&] {
         return query_matrix_algorithmic_bytes_checked(ctx, rows, n, n_queries, cosines != 0, dots != 0, norms != 0, bytes);
     });
+}
+
+int memb_hip_dense_topk_device(
+    int device, const float* matrix, size_t n_rows, size_t n, size_t ld, int64_t base, uint32_t k, int merge, float* values,
+    int64_t* positions, size_t ld_out, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return guarded([&] {
+        return dense_topk_device_checked(
+            device, matrix, n_rows, n, ld, base, k, merge != 0, values, positions, ld_out, workspace, workspace_bytes, stream);
+    });
+}
+
+size_t memb_hip_dense_topk_workspace_bytes(size_t n_rows, size_t n, uint32_t k)
+{
+    return static_cast<size_t>(denseTopkWorkspaceBytes(n_rows, n, k));
+}
+
+int memb_hip_query_topk_device(
+    memb_hip_ctx* ctx, const float* queries, size_t n_queries, size_t ld_queries, const uint32_t* rows, size_t n, uint32_t k,
+    float* values, int64_t* positions, size_t ld_out, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return guarded([&] {
+        return query_topk_device_checked(
+            ctx, queries, n_queries, ld_queries, rows, n, k, values, positions, ld_out, workspace, workspace_bytes, stream);
+    });
+}
+
+size_t memb_hip_query_topk_workspace_bytes(const memb_hip_ctx* ctx, size_t n_queries, size_t n, uint32_t k, int minimal)
+{
+    return query_topk_workspace_bytes(ctx, n_queries, n, k, minimal != 0);
+}
+
+const char* memb_hip_query_topk_kernel_name(const memb_hip_ctx* ctx)
+{
+    return query_topk_kernel_name(ctx);
+}
+
+int memb_hip_query_topk_algorithmic_bytes(
+    const memb_hip_ctx* ctx, const uint32_t* rows, size_t n, size_t n_queries, uint32_t k, uint64_t* bytes)
+{
+    return guarded([&] { return query_topk_algorithmic_bytes_checked(ctx, rows, n, n_queries, k, bytes); });
 }
 
 int memb_hip_decode_batches_device(memb_hip_ctx* ctx, const memb_hip_batch* batches, size_t count, void* stream)

@@ -344,6 +344,63 @@ def unit_rows_host(values, norms=None):
         return values / np.where(norms < UNIT_EPS, UNIT_EPS, norms)[:, None]
 
 
+QUERY_TOPK_MAX_K = _memb.QUERY_TOPK_MAX_K   # one rank per lane of a wavefront (MEMB_HIP_TOPK_MAX_K)
+
+
+def topk_size(k, spare=0):
+    """k as an int; ValueError unless 1 <= k <= QUERY_TOPK_MAX_K - spare"""
+    if isinstance(k, bool) or int(k) != k:
+        raise TypeError('k must be an integer')
+    if not 1 <= k <= QUERY_TOPK_MAX_K - spare:
+        raise ValueError('k must be 1 .. {} (the selection keeps at most {} entries per query{}), got {}'.format(
+            QUERY_TOPK_MAX_K - spare, QUERY_TOPK_MAX_K, ', one of them the word itself' if spare else '', k))
+    return int(k)
+
+
+def topk_fallback_list_bytes(count, n, k, slice_size):
+    """The bytes of segment lists similarity_topk_device's fallback needs for its dense_topk_to_device calls over n
+    candidates in slices of slice_size: the larger of what a full slice and what the shorter last slice ask for. A shorter
+    slice can need MORE: segments are whole multiples of 256 columns, so fewer columns may be cut into more segments (33
+    queries: 228 segments for 524 288 columns, 249 for 509 952)."""
+    sizes = {min(n, slice_size)}
+    if n > slice_size and n % slice_size:
+        sizes.add(n % slice_size)
+    return max(_memb.dense_topk_workspace_bytes(count, size, k) for size in sizes)
+
+
+def topk_keys(values):
+    """include/memb_hip_query_topk.h's order on float32 values as uint32 keys, greater first: every NaN the one greatest
+    key, -0.0 the key of +0.0, -inf the smallest; no value has key 0"""
+    bits = np.ascontiguousarray(values, dtype=np.float32).view(np.uint32)
+    bits = np.where(bits == np.uint32(0x80000000), np.uint32(0), bits)
+    keys = np.where(bits & np.uint32(0x80000000), ~bits, bits | np.uint32(0x80000000))
+    return np.where((bits & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000), np.uint32(0xFFFFFFFF), keys).astype(np.uint32)
+
+
+def topk_host(matrix, k, base=0, held=None):
+    """The contract of include/memb_hip_query_topk.h in numpy: (values float32 (Q, k), positions int64 (Q, k)) of the
+    float32 (Q, n) matrix, positions as base + column; held: a (values, positions) pair of an earlier call whose entries
+    (position -1: empty) take part, their positions outside [base, base + n)."""
+    matrix = np.ascontiguousarray(matrix, dtype=np.float32)
+    count, n = matrix.shape
+    bits = matrix.view(np.uint32)
+    positions = np.broadcast_to(base + np.arange(n, dtype=np.int64), (count, n))
+    keys = topk_keys(matrix).astype(np.int64)
+    if held is not None:
+        bits = np.concatenate([held[0].view(np.uint32), bits], axis=1)
+        keys = np.concatenate([np.where(held[1] < 0, 0, topk_keys(held[0]).astype(np.int64)), keys], axis=1)
+        positions = np.concatenate([held[1], positions], axis=1)
+    # key descending, then position ascending; an empty entry (key 0) behind every real one
+    order = np.lexsort((positions, -keys), axis=1)[:, :k]
+    keys = np.take_along_axis(keys, order, axis=1)
+    values = np.full((count, k), 0xFF800000, dtype=np.uint32)
+    found = np.full((count, k), -1, dtype=np.int64)
+    width = order.shape[1]
+    values[:, :width] = np.where(keys > 0, np.take_along_axis(bits, order, axis=1), np.uint32(0xFF800000))
+    found[:, :width] = np.where(keys > 0, np.take_along_axis(positions, order, axis=1), -1)
+    return values.view(np.float32), found
+
+
 def tokenizer_word_list(tokenizer):
     """The words of a keras Tokenizer placed at their indices, '' where an index
     has no word (index 0 never has one). With `num_words` set only indices below
@@ -401,6 +458,8 @@ class Reader(BaseReader):
         self._last_bag_pairs_kernel = ''
         self._last_query_kernel = ''
         self._last_query_matrix_kernel = ''
+        self._last_query_topk_kernel = ''
+        self._all_rows = None              # every row id in order on the device, of similarity_topk_device(rows=None)
         self._whole_group_offsets = None   # ((n, device), the device tensor [0, n]) of query_similarity_device(offsets=None)
 
     @property
@@ -1371,6 +1430,186 @@ class Reader(BaseReader):
             return (cosines, dots if return_dots else None,
                     (row_norms_host(queries) if count else np.zeros(0, dtype=np.float32), row_norms) if return_norms else None)
         return cosines
+
+    # ---- the k nearest candidates of every query (include/memb_hip_query_topk.h) ----
+
+    @property
+    def last_query_topk_kernel(self):
+        '''The kernel families of the last similarity_topk_device call, joined by '+':
+        'query_matrix_trained+topk_select+topk_merge' (slices of the fused matrix kernel in a workspace, selected there), or
+        'pairs_dense+topk_select+topk_merge' where the matrix of a slice comes from similarity_matrix_device's fallback --
+        uniform and full storage, dims that are no multiple of 4 or beyond 512; 'topk_merge' where such a model is asked
+        with no candidate at all (the empty slots are all there is to write). '' before any call and after a call without
+        queries, which launches nothing. Informational: the bits are the same.'''
+        return self._last_query_topk_kernel
+
+    def _topk_queries(self, torch, queries, index):
+        """the checks of similarity_matrix_device on its queries: (queries as (Q, dim), Q, ld)"""
+        dim = self.dim
+        if not isinstance(queries, torch.Tensor) or queries.dtype != torch.float32:
+            raise TypeError('queries must be a float32 tensor of shape (Q, dim) or (dim,)')
+        if queries.device.type != 'cuda':
+            raise TypeError('queries must be on the GPU')
+        if queries.dim() == 1:
+            queries = queries.unsqueeze(0)
+        if queries.dim() != 2 or queries.shape[1] != dim:
+            raise ValueError('queries must have shape (Q, {}) or ({},), got {}'.format(dim, dim, tuple(queries.shape)))
+        count = queries.shape[0]
+        if (dim > 1 and queries.stride(1) != 1) or (count > 1 and queries.stride(0) < dim):
+            raise ValueError('queries must have a contiguous last dimension and a row stride of at least dim')
+        if queries.device.index != index:
+            raise ValueError('queries must be on cuda:{} (the device this reader is staged on), got {}'.format(index, queries.device))
+        return queries, count, queries.stride(0) if count > 1 else dim
+
+    def _all_rows_device(self, torch, index):
+        """every row id of the model in order, on the device. Kept for the reader's lifetime once rows=None was asked for:
+        4 bytes per word (8.8 MB for 2.2 M words), a torch tensor, so not part of info()['device_bytes']"""
+        if self._all_rows is None or self._all_rows.device.index != index:
+            self._all_rows = torch.arange(len(self), dtype=torch.int32, device='cuda:{}'.format(index))
+        return self._all_rows
+
+    def similarity_topk_device(self, queries, rows, k, *, workspace=None):
+        '''The k most similar candidates of EVERY query, left on the GPU, WITHOUT the (Q, n) matrix of
+        similarity_matrix_device in device memory: (values, positions), a float32 (Q, k) and an int64 (Q, k) tensor.
+        Row q of similarity_matrix_device(queries, rows) ordered by a stable descending sort -- a greater cosine first, NaN
+        before every number, equal cosines (-0.0 == +0.0) lower position first --, cut to k: positions[q, j] is the index
+        into `rows` of the j-th best candidate and values[q, j] the matrix's bits there. Where n < k the last k - n
+        entries are empty: position -1, value -inf (an empty slot is told by its position). The order is total, so this is
+        torch.sort(matrix, dim=1, descending=True, stable=True) cut to k, whatever the slicing. For trained models whose dim
+        is a multiple of 4 and at most 512 the matrix kernel fills a slice of the candidates in a workspace (about 32 MiB,
+        independent of n) and two selection kernels merge it into the result; otherwise slices of at most 2^19 candidates
+        go through similarity_matrix_device into one reused temporary and the same selection (last_query_topk_kernel says
+        which).
+        queries : as in similarity_matrix_device
+        rows : as in rows_embedding_device, the n candidates every query shares; None: every row of the model in order, so
+            positions are row ids (the ids are built on the device at the first such call and kept, 4 bytes per word,
+            outside info()['device_bytes'])
+        k : 1 .. 64 (QUERY_TOPK_MAX_K)
+        workspace : optional contiguous uint8 tensor on the same device, aligned to 8 bytes, of at least
+            self._impl.query_topk_workspace_bytes(Q, n, k, minimal=True) bytes, for the fused path: a call with it allocates
+            nothing but its two results. Its size decides the slicing, never the result.
+        One model, float32: no k > 64, no bfloat16 / float16, no ReadersUnion, no ShardedReader, no exclusion list.'''
+        import torch
+        index = self._impl.device()
+        if index == _memb.HOST_DEVICE:
+            raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
+        k = topk_size(k)
+        if rows is None:
+            rows = self._all_rows_device(torch, index)
+        self._norms_arguments(torch, rows)
+        queries, count, ld = self._topk_queries(torch, queries, index)
+        device = rows.device
+        if device.index != index:
+            raise ValueError('queries and rows must be on cuda:{} (the device this reader is staged on), got {} and {}'.format(
+                self.device, queries.device, device))
+        rows = rows.reshape(-1)
+        n = rows.numel()
+        values = torch.empty((count, k), dtype=torch.float32, device=device)
+        positions = torch.empty((count, k), dtype=torch.int64, device=device)
+        stream = _current_stream(torch, index)
+        fused = self._impl.query_topk_kernel_name()
+        self._last_query_topk_kernel = fused if count else ''
+        if count == 0:   # (nothing is launched)
+            return values, positions
+        if fused or n == 0:
+            if not fused:   # (no candidate: topk_merge alone fills the empty slots, whatever the model)
+                self._last_query_topk_kernel = 'topk_merge'
+            if workspace is None:
+                workspace = torch.empty((self._impl.query_topk_workspace_bytes(count, n, k),), dtype=torch.uint8, device=device)
+            elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1
+                    or not workspace.is_contiguous() or workspace.device != device):
+                raise TypeError('workspace must be a contiguous uint8 tensor on cuda:{}'.format(index))
+            done = self._impl.query_topk_to_device(
+                queries.data_ptr(), count, ld, rows.data_ptr(), n, k, values.data_ptr(), positions.data_ptr(), k,
+                workspace.data_ptr() if workspace.numel() else 0, workspace.numel(), stream)
+            assert done   # (n == 0 is answered for every model)
+            return values, positions
+        width = min(n, QUERY_DEVICE_SLICE)
+        temporary = torch.empty((count, width), dtype=torch.float32, device=device)
+        lists = torch.empty((topk_fallback_list_bytes(count, n, k, QUERY_DEVICE_SLICE),), dtype=torch.uint8, device=device)
+        for start in range(0, n, QUERY_DEVICE_SLICE):
+            size = min(n, start + QUERY_DEVICE_SLICE) - start
+            self.similarity_matrix_device(queries, rows[start:start + size], out=temporary[:, :size])
+            _memb.dense_topk_to_device(
+                index, temporary.data_ptr(), count, size, width, start, k, start > 0, values.data_ptr(), positions.data_ptr(), k,
+                lists.data_ptr(), lists.numel(), stream)
+        self._last_query_topk_kernel = self._last_query_matrix_kernel + '+' + _memb.dense_topk_kernel_name()
+        return values, positions
+
+    def most_similar_device(self, words, k=10, *, exclude_self=True):
+        '''The k nearest words of each word over the WHOLE vocabulary, left on the GPU: (values, rows), a float32
+        (len(words), k) tensor of cosines and an int64 (len(words), k) tensor of row ids (positions in keys()), best first
+        in similarity_topk_device's order. The words are resolved and their rows decoded on the device, the rest is
+        similarity_topk_device over every row. exclude_self: the word's own row is left out -- k + 1 are selected, the
+        own row is dropped on the device, the rest keeps its order and its first k are returned --, so k <= 63. A repeated
+        word gives repeated rows of output. A word that is not in the model gives a row of empty slots: row id -1, value
+        -inf. No other exclusion list.'''
+        import torch
+        index = self._impl.device()
+        if index == _memb.HOST_DEVICE:
+            raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
+        k = topk_size(k, 1 if exclude_self else 0)
+        device = 'cuda:{}'.format(index)
+        words = list(words)
+        if not words:
+            return torch.empty((0, k), dtype=torch.float32, device=device), torch.empty((0, k), dtype=torch.int64, device=device)
+        own = self.resolve_rows_device(words)
+        values, positions = self.similarity_topk_device(self.rows_embedding_device(own), None, k + 1 if exclude_self else k)
+        own = own.to(torch.int64).unsqueeze(1)   # (a missing word is -1)
+        if exclude_self:
+            # stable: the entries that stay keep their order, the own row goes behind them
+            order = torch.sort((positions == own).to(torch.int8), dim=1, stable=True).indices[:, :k]
+            values, positions = torch.gather(values, 1, order), torch.gather(positions, 1, order)
+        unknown = own < 0
+        return (torch.where(unknown, torch.full_like(values, float('-inf')), values),
+                torch.where(unknown, torch.full_like(positions, -1), positions))
+
+    def most_similar(self, words, k=10):
+        '''The k nearest words of each word over the whole vocabulary, on the host: one list of (word, cosine) pairs per
+        word, best first, the word itself left out; [] for a word the model lacks. most_similar_device on a GPU reader,
+        similarity_topk on a device='cpu' reader: the same pairs.'''
+        words = list(words)
+        k = topk_size(k, 1)
+        if not words:
+            return []
+        if self._impl.device() != _memb.HOST_DEVICE:
+            values, positions = (part.cpu().numpy() for part in self.most_similar_device(words, k))
+        else:
+            own = self.resolve_rows(words)
+            values, positions = self.similarity_topk(self.rows_embedding(own), None, k + 1)
+            order = np.argsort(positions == own.astype(np.int64)[:, None], axis=1, kind='stable')[:, :k]
+            values, positions = np.take_along_axis(values, order, axis=1), np.take_along_axis(positions, order, axis=1)
+            positions = np.where((own == 0xFFFFFFFF)[:, None], -1, positions)
+        vocabulary = self.keys()
+        return [[(vocabulary[row], float(value)) for value, row in zip(values[i], positions[i]) if row >= 0] for i in range(len(words))]
+
+    def similarity_topk(self, queries, rows, k):
+        '''similarity_topk_device for host arrays: a numpy float32 (Q, dim) or (dim,) array of queries and numpy row ids
+        (None: every row of the model) in, (values float32 (Q, k), positions int64 (Q, k)) out. A reader on a GPU sends
+        everything up and brings the result back; a device='cpu' reader takes similarity_matrix chunk by chunk and selects
+        by the same order in numpy (topk_host): the same bits.'''
+        queries = np.asarray(queries)
+        if queries.dtype != np.float32:
+            raise TypeError('queries must be a float32 array of shape (Q, dim) or (dim,)')
+        if queries.ndim == 1:
+            queries = queries[None, :]
+        if queries.ndim != 2 or queries.shape[1] != self.dim:
+            raise ValueError('queries must have shape (Q, {}) or ({},), got {}'.format(self.dim, self.dim, queries.shape))
+        k = topk_size(k)
+        queries = np.ascontiguousarray(queries)
+        rows = np.arange(len(self), dtype=np.uint32) if rows is None else np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        if self._impl.device() != _memb.HOST_DEVICE:
+            import torch
+            device = 'cuda:{}'.format(self._impl.device())
+            values, positions = self.similarity_topk_device(
+                torch.from_numpy(queries).to(device), torch.from_numpy(rows.view(np.int32)).to(device), k)
+            return values.cpu().numpy(), positions.cpu().numpy()
+        values = np.full((queries.shape[0], k), -np.inf, dtype=np.float32)
+        positions = np.full((queries.shape[0], k), -1, dtype=np.int64)
+        for start in range(0, rows.size, NORMS_HOST_CHUNK):
+            matrix = self.similarity_matrix(queries, rows[start:start + NORMS_HOST_CHUNK])
+            values, positions = topk_host(matrix, k, start, (values, positions))
+        return values, positions
 
     def stage_words(self):
         '''Copy the model's keys to the GPU and build the hash table over them there (once; resolve_rows_device does it
