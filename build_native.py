@@ -69,7 +69,7 @@ def build_hip_library(force=False, extra_flags=()):
             os.path.join(CSRC, 'memb_hip_pooled_union.hip'), os.path.join(CSRC, 'memb_hip_norms.hip'),
             os.path.join(CSRC, 'memb_hip_pairs.hip'), os.path.join(CSRC, 'memb_hip_bag_pairs.hip'),
             os.path.join(CSRC, 'memb_hip_queries.hip'), os.path.join(CSRC, 'memb_hip_query_matrix.hip'),
-            os.path.join(CSRC, 'memb_hip_query_topk.hip'),
+            os.path.join(CSRC, 'memb_hip_query_topk.hip'), os.path.join(CSRC, 'memb_hip_query_bags.hip'),
         ])
     return HIP_LIBRARY
 

@@ -16,6 +16,8 @@
 #include "hip_query_matrix.h"
 #include "../../include/memb_hip_query_topk.h"
 #include "hip_query_topk.h"
+#include "../../include/memb_hip_query_bags.h"
+#include "hip_query_bags.h"
 
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -1379,7 +1381,120 @@ PYBIND11_MODULE(_memb, m) {
             },
             py::arg("rows"),
             py::arg("n_queries"),
-            py::arg("k"));
+            py::arg("k"))
+        // include/memb_hip_query_bags.h. Device pointers: the queries of query_matrix_to_device, n entry ids cut into bags
+        // by bags + 1 offsets, mode POOL_SUM / POOL_MEAN; cosines and dots (n_queries rows of bags floats, ld_out floats
+        // apart) and norms (bags floats), each of which may be 0. False where the fused kernel does not exist for this
+        // model (MEMB_HIP_UNSUPPORTED): the caller pools the bags and calls dense_pair_similarity_to_device.
+        .def(
+            "query_bags_to_device",
+            [](memb::Reader& reader, uintptr_t queries, size_t nQueries, size_t ldQueries, uintptr_t rows, size_t n,
+               uintptr_t offsets, size_t bags, int mode, uintptr_t cosines, uintptr_t dots, size_t ldOut, uintptr_t norms,
+               uintptr_t stream)
+            {
+                const int code = memb_hip_query_bags_device(
+                    reader.deviceContext(), reinterpret_cast<const float*>(queries), nQueries, ldQueries,
+                    reinterpret_cast<const uint32_t*>(rows), n, reinterpret_cast<const uint32_t*>(offsets), bags, mode,
+                    reinterpret_cast<float*>(cosines), reinterpret_cast<float*>(dots), ldOut, reinterpret_cast<float*>(norms),
+                    reinterpret_cast<void*>(stream));
+                if (code == MEMB_HIP_UNSUPPORTED) {
+                    return false;
+                }
+                if (code != MEMB_HIP_OK) {
+                    throw std::runtime_error(std::string("memb_hip_query_bags_device: ") + memb_hip_last_error());
+                }
+                return true;
+            },
+            py::arg("queries_ptr"),
+            py::arg("n_queries"),
+            py::arg("ld_queries"),
+            py::arg("rows_ptr"),
+            py::arg("n"),
+            py::arg("offsets_ptr"),
+            py::arg("bags"),
+            py::arg("mode"),
+            py::arg("cosines_ptr"),
+            py::arg("dots_ptr"),
+            py::arg("ld_out"),
+            py::arg("norms_ptr"),
+            py::arg("stream") = 0)
+        // the kernel family query_bags_to_device launches, '' where it returns False
+        .def(
+            "query_bags_kernel_name",
+            [](memb::Reader& reader) { return std::string(memb_hip_query_bags_kernel_name(reader.deviceContext())); })
+        .def(
+            "query_bags_algorithmic_bytes",
+            [](memb::Reader& reader, py::array_t<uint32_t, py::array::c_style | py::array::forcecast> rows,
+               py::array_t<uint32_t, py::array::c_style | py::array::forcecast> offsets, size_t nQueries, bool cosines, bool dots,
+               bool norms)
+            {
+                if (offsets.size() < 1) {
+                    throw std::invalid_argument("offsets needs bags + 1 entries");
+                }
+                uint64_t bytes = 0;
+                if (memb_hip_query_bags_algorithmic_bytes(
+                        reader.deviceContext(), rows.data(), static_cast<size_t>(rows.size()), offsets.data(),
+                        static_cast<size_t>(offsets.size() - 1), nQueries, cosines ? 1 : 0, dots ? 1 : 0, norms ? 1 : 0,
+                        &bytes) != MEMB_HIP_OK) {
+                    throw std::runtime_error(std::string("memb_hip_query_bags_algorithmic_bytes: ") + memb_hip_last_error());
+                }
+                return bytes;
+            },
+            py::arg("rows"),
+            py::arg("offsets"),
+            py::arg("n_queries"),
+            py::arg("cosines") = true,
+            py::arg("dots") = false,
+            py::arg("norms") = false)
+        // the k nearest bags of every query: query_topk_to_device with bags for candidates. False likewise: the caller takes
+        // the matrix in slices and calls dense_topk_to_device with merge.
+        .def(
+            "query_bags_topk_to_device",
+            [](memb::Reader& reader, uintptr_t queries, size_t nQueries, size_t ldQueries, uintptr_t rows, size_t n,
+               uintptr_t offsets, size_t bags, int mode, uint32_t k, uintptr_t values, uintptr_t positions, size_t ldOut,
+               uintptr_t workspace, size_t workspaceBytes, uintptr_t stream)
+            {
+                const int code = memb_hip_query_bags_topk_device(
+                    reader.deviceContext(), reinterpret_cast<const float*>(queries), nQueries, ldQueries,
+                    reinterpret_cast<const uint32_t*>(rows), n, reinterpret_cast<const uint32_t*>(offsets), bags, mode, k,
+                    reinterpret_cast<float*>(values), reinterpret_cast<int64_t*>(positions), ldOut,
+                    reinterpret_cast<void*>(workspace), workspaceBytes, reinterpret_cast<void*>(stream));
+                if (code == MEMB_HIP_UNSUPPORTED) {
+                    return false;
+                }
+                if (code != MEMB_HIP_OK) {
+                    throw std::runtime_error(std::string("memb_hip_query_bags_topk_device: ") + memb_hip_last_error());
+                }
+                return true;
+            },
+            py::arg("queries_ptr"),
+            py::arg("n_queries"),
+            py::arg("ld_queries"),
+            py::arg("rows_ptr"),
+            py::arg("n"),
+            py::arg("offsets_ptr"),
+            py::arg("bags"),
+            py::arg("mode"),
+            py::arg("k"),
+            py::arg("values_ptr"),
+            py::arg("positions_ptr"),
+            py::arg("ld_out"),
+            py::arg("workspace_ptr"),
+            py::arg("workspace_bytes"),
+            py::arg("stream") = 0)
+        .def(
+            "query_bags_topk_workspace_bytes",
+            [](memb::Reader& reader, size_t nQueries, size_t bags, uint32_t k, bool minimal) {
+                return memb_hip_query_bags_topk_workspace_bytes(reader.deviceContext(), nQueries, bags, k, minimal ? 1 : 0);
+            },
+            py::arg("n_queries"),
+            py::arg("bags"),
+            py::arg("k"),
+            py::arg("minimal") = false)
+        // the kernel families query_bags_topk_to_device launches, '' where it returns False
+        .def(
+            "query_bags_topk_kernel_name",
+            [](memb::Reader& reader) { return std::string(memb_hip_query_bags_topk_kernel_name(reader.deviceContext())); });
 
     // include/memb_hip_query_topk.h: the k best columns of every row of any fp32 device matrix, positions as base +
     // column; merge: what values / positions hold takes part. The workspace needs dense_topk_workspace_bytes bytes.
@@ -1418,6 +1533,8 @@ PYBIND11_MODULE(_memb, m) {
 
     // queries query_matrix_trained holds in registers at once (hip_query_matrix.h): geometry, never the result
     m.attr("QUERY_MATRIX_BLOCK") = memb_query_matrix::QUERY_BLOCK;
+    // pooled rows query_bags_trained holds in registers at once (hip_query_bags.h): geometry, never the result
+    m.attr("QUERY_BAGS_GROUP") = memb_query_bags::BAG_GROUP;
     m.attr("OUT_F32") = MEMB_HIP_OUT_F32;
     m.attr("OUT_BF16") = MEMB_HIP_OUT_BF16;
     m.attr("OUT_F16") = MEMB_HIP_OUT_F16;

@@ -49,7 +49,9 @@
 // memb_hip_queries.hip -- that of query vectors against groups of candidate rows (hip_queries.h), launched by
 // hip_queries_launch.h; memb_hip_query_matrix.hip -- that of every query against one shared candidate list
 // (hip_query_matrix.h), launched by hip_query_matrix_launch.h; memb_hip_query_topk.hip -- the k best columns of every row
-// of a matrix (hip_query_topk.h), launched by hip_query_topk_launch.h, slice after slice of the query matrix.
+// of a matrix (hip_query_topk.h), launched by hip_query_topk_launch.h, slice after slice of the query matrix;
+// memb_hip_query_bags.hip -- that of every query against every pooled bag of rows (hip_query_bags.h), launched by
+// hip_query_bags_launch.h, as a matrix or slice after slice in front of the same selection.
 #include <hip/hip_runtime.h>
 
 #include "../../include/memb_hip.h"
@@ -64,6 +66,7 @@
 #include "../../include/memb_hip_queries.h"
 #include "../../include/memb_hip_query_matrix.h"
 #include "../../include/memb_hip_query_topk.h"
+#include "../../include/memb_hip_query_bags.h"
 #include "codec.h"
 #include "hip_narrow.h"
 #include "hip_pooled.h"
@@ -75,6 +78,7 @@
 #include "hip_queries.h"
 #include "hip_query_matrix.h"
 #include "hip_query_topk.h"
+#include "hip_query_bags.h"
 #include "wire.h"
 #include "worker_pool.h"
 
@@ -152,6 +156,7 @@ namespace {
 #include "hip_queries_launch.h"
 #include "hip_query_matrix_launch.h"
 #include "hip_query_topk_launch.h"
+#include "hip_query_bags_launch.h"
 
 // No C++ exception leaves the library: allocation failures and the like become error codes.
 template <typename Call>
@@ -515,6 +520,52 @@ int memb_hip_query_topk_algorithmic_bytes(
     const memb_hip_ctx* ctx, const uint32_t* rows, size_t n, size_t n_queries, uint32_t k, uint64_t* bytes)
 {
     return guarded([&] { return query_topk_algorithmic_bytes_checked(ctx, rows, n, n_queries, k, bytes); });
+}
+
+int memb_hip_query_bags_device(
+    memb_hip_ctx* ctx, const float* queries, size_t n_queries, size_t ld_queries, const uint32_t* rows, size_t n,
+    const uint32_t* offsets, size_t bags, int mode, float* cosines, float* dots, size_t ld_out, float* norms, void* stream)
+{
+    return guarded([&] {
+        return query_bags_device_checked(
+            ctx, queries, n_queries, ld_queries, rows, n, offsets, bags, mode, cosines, dots, ld_out, norms, stream);
+    });
+}
+
+const char* memb_hip_query_bags_kernel_name(const memb_hip_ctx* ctx)
+{
+    return query_bags_kernel_name(ctx);
+}
+
+int memb_hip_query_bags_algorithmic_bytes(
+    const memb_hip_ctx* ctx, const uint32_t* rows, size_t n, const uint32_t* offsets, size_t bags, size_t n_queries, int cosines,
+    int dots, int norms, uint64_t* bytes)
+{
+    return guarded([&] {
+        return query_bags_algorithmic_bytes_checked(ctx, rows, n, offsets, bags, n_queries, cosines != 0, dots != 0, norms != 0, bytes);
+    });
+}
+
+int memb_hip_query_bags_topk_device(
+    memb_hip_ctx* ctx, const float* queries, size_t n_queries, size_t ld_queries, const uint32_t* rows, size_t n,
+    const uint32_t* offsets, size_t bags, int mode, uint32_t k, float* values, int64_t* positions, size_t ld_out, void* workspace,
+    size_t workspace_bytes, void* stream)
+{
+    return guarded([&] {
+        return query_bags_topk_device_checked(
+            ctx, queries, n_queries, ld_queries, rows, n, offsets, bags, mode, k, values, positions, ld_out, workspace,
+            workspace_bytes, stream);
+    });
+}
+
+size_t memb_hip_query_bags_topk_workspace_bytes(const memb_hip_ctx* ctx, size_t n_queries, size_t bags, uint32_t k, int minimal)
+{
+    return query_bags_topk_workspace_bytes(ctx, n_queries, bags, k, minimal != 0);
+}
+
+const char* memb_hip_query_bags_topk_kernel_name(const memb_hip_ctx* ctx)
+{
+    return query_bags_topk_kernel_name(ctx);
 }
 
 int memb_hip_decode_batches_device(memb_hip_ctx* ctx, const memb_hip_batch* batches, size_t count, void* stream)

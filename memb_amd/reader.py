@@ -344,6 +344,8 @@ def unit_rows_host(values, norms=None):
         return values / np.where(norms < UNIT_EPS, UNIT_EPS, norms)[:, None]
 
 
+QUERY_BAGS_DEVICE_SLICE = 1 << 16   # bags bag_similarity_matrix_device pools into a temporary at a time where no fused kernel exists
+QUERY_BAGS_HOST_SLICE = 1 << 12     # bags bag_similarity_matrix of a device='cpu' reader pools at a time
 QUERY_TOPK_MAX_K = _memb.QUERY_TOPK_MAX_K   # one rank per lane of a wavefront (MEMB_HIP_TOPK_MAX_K)
 
 
@@ -459,6 +461,8 @@ class Reader(BaseReader):
         self._last_query_kernel = ''
         self._last_query_matrix_kernel = ''
         self._last_query_topk_kernel = ''
+        self._last_query_bags_kernel = ''
+        self._last_query_bags_topk_kernel = ''
         self._all_rows = None              # every row id in order on the device, of similarity_topk_device(rows=None)
         self._whole_group_offsets = None   # ((n, device), the device tensor [0, n]) of query_similarity_device(offsets=None)
 
@@ -988,7 +992,8 @@ class Reader(BaseReader):
             a float32 (pairs, 2) tensor -- row_norms_device's of the two pooled rows --, None where not asked for
         out : optional contiguous float32 (pairs,) tensor on the same device for the cosines
         One model, float32, missing='zero', the sequential order: no missing='skip', no reduction='chunked', no
-        bfloat16 / float16, no ReadersUnion, no ShardedReader, no one-against-many search.'''
+        bfloat16 / float16, no ReadersUnion, no ShardedReader. One against many bags and the k nearest bags:
+        bag_similarity_matrix_device, bag_similarity_topk_device.'''
         import torch
         code = pool_mode(mode)
         index, device = self._norms_arguments(torch, rows)
@@ -1608,6 +1613,299 @@ class Reader(BaseReader):
         positions = np.full((queries.shape[0], k), -1, dtype=np.int64)
         for start in range(0, rows.size, NORMS_HOST_CHUNK):
             matrix = self.similarity_matrix(queries, rows[start:start + NORMS_HOST_CHUNK])
+            values, positions = topk_host(matrix, k, start, (values, positions))
+        return values, positions
+
+    # ---- every query against every pooled bag of rows, matrix and top-k (include/memb_hip_query_bags.h) ----
+
+    @property
+    def last_query_bags_kernel(self):
+        '''The kernel family of the last bag_similarity_matrix_device call: 'query_bags_trained' (fused with the pooling) or
+        'pairs_dense' behind a pooled lookup of a slice of the bags -- uniform and full storage, dims that are no multiple
+        of 4 or beyond 512. '' before any call. Informational: the bits are the same.'''
+        return self._last_query_bags_kernel
+
+    @property
+    def last_query_bags_topk_kernel(self):
+        '''The kernel families of the last bag_similarity_topk_device call, joined by '+':
+        'query_bags_trained+topk_select+topk_merge' (slices of the fused kernel in a workspace, selected there), or
+        'pairs_dense+topk_select+topk_merge' where the matrix of a slice comes from bag_similarity_matrix_device's fallback;
+        'topk_merge' where such a model is asked with no bag at all. '' before any call and after a call without queries,
+        which launches nothing. Informational: the bits are the same.'''
+        return self._last_query_bags_topk_kernel
+
+    def _bag_arguments(self, torch, rows, offsets, index, device):
+        '''bags_embedding_device's checks on its offsets; returns the number of bags'''
+        if (not isinstance(offsets, torch.Tensor) or offsets.device.type != 'cuda' or offsets.dtype not in (torch.int32, torch.uint32)
+                or not offsets.is_contiguous() or offsets.dim() != 1):
+            raise TypeError('offsets must be a contiguous int32/uint32 tensor of bags + 1 entries on the GPU')
+        if offsets.numel() < 1:
+            raise ValueError('offsets needs bags + 1 entries')
+        if device.index != index or offsets.device != device:
+            raise ValueError('rows and offsets must be on cuda:{} (the device this reader is staged on), got {} and {}'.format(
+                self.device, device, offsets.device))
+        return offsets.numel() - 1
+
+    @staticmethod
+    def _bag_slice(torch, flat, offsets, start, stop):
+        '''(entries, offsets) of the bags [start, stop) for a pooled launch of their own: the slice's offsets as the kernel
+        clamps them, rebased on the slice's lowest entry so that the launch is planned for the slice's entries alone --
+        made on the device, with one scalar read back to cut those entries out of `rows`. All bags: as they are.'''
+        if start == 0 and stop == offsets.numel() - 1:
+            return flat, offsets
+        cut = offsets[start:stop + 1].view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+        cut = torch.clamp(cut, max=flat.numel())
+        first = int(cut.min())
+        return flat[first:], (cut - first).to(torch.int32)
+
+    def _bag_matrix_fallback(self, torch, queries, count, flat, offsets, start, stop, mode, temporary, out, dots, norms, stream):
+        '''the bags [start, stop) pooled ONCE into temporary[:, 1], then every query written beside the same pooled rows and
+        reduced by the dense pair kernel into out[:, :stop - start] (dots likewise; norms: the pooled rows')'''
+        index, dim, size = self._impl.device(), self.dim, stop - start
+        entries, cut = self._bag_slice(torch, flat, offsets, start, stop)
+        self.bags_embedding_device(entries, cut, mode=mode, out=temporary.view(temporary.shape[0], 2 * dim)[:size], col_off=dim)
+        pair_norms = torch.empty((size, 2), dtype=torch.float32, device=flat.device) if norms is not None else None
+        for q in range(count):
+            temporary[:size, 0] = queries[q]
+            _memb.dense_pair_similarity_to_device(
+                index, temporary.data_ptr(), size, dim, dim, out[q, :size].data_ptr() if out is not None else 0,
+                dots[q, :size].data_ptr() if dots is not None else 0,
+                pair_norms.data_ptr() if norms is not None and q == 0 else 0, stream)
+            if norms is not None and q == 0:
+                norms[:size] = pair_norms[:, 1]
+
+    def bag_similarity_matrix_device(self, queries, rows, offsets, mode='mean', *, return_dots=False, return_norms=False, out=None):
+        '''The cosine similarity of EVERY query vector against EVERY pooled bag of rows, left on the GPU: a float32 (Q, bags)
+        tensor, cos[q, b] of query q and the sum or mean of bag b -- query vectors against a corpus of sentences as
+        averaged word vectors. For trained models whose dim is a multiple of 4 and at most 512 ONE kernel pools every bag in
+        registers, scores it against all queries and writes neither a pooled nor a decoded row; otherwise slices of at most
+        2^16 bags are pooled once into a reused temporary (bags_embedding_device) and reduced there against one query
+        after the other (last_query_bags_kernel says which). Bit for bit the contract of include/memb_hip_query_bags.h:
+        similarity_matrix_device's reduction with the rows bags_embedding_device(rows, offsets, mode) gives for its
+        candidates -- whichever kernel ran. Not clamped. An empty bag, or a bag of rows that are not in the model, has cosine 0.
+        queries : as in similarity_matrix_device (callers with sentences for queries pool them first:
+            sentences_embedding_device)
+        rows, offsets : as in bags_embedding_device, offsets holding bags + 1 entries
+        mode : 'mean' or 'sum'
+        return_dots, return_norms : either one returns (cosines, dots, norms) instead, dots a float32 (Q, bags) tensor and
+            norms the pair (query_norms (Q,), bag_norms (bags,)) -- row_norms of the pooled rows --, None where not asked for
+        out : optional float32 (Q, bags) tensor on the same device for the cosines, with a contiguous last dimension and a
+            row stride of at least bags; nothing between its rows is written
+        One model, float32, missing='zero', the sequential order: no missing='skip', no reduction='chunked', no bfloat16 /
+        float16, no ReadersUnion, no ShardedReader.'''
+        import torch
+        code = pool_mode(mode)
+        index, device = self._norms_arguments(torch, rows)
+        dim = self.dim
+        queries, count, ld = self._topk_queries(torch, queries, index)
+        bags = self._bag_arguments(torch, rows, offsets, index, device)
+        if out is None:
+            out = torch.empty((count, bags), dtype=torch.float32, device=device)
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.dim() != 2 or tuple(out.shape) != (count, bags):
+            raise TypeError('out must be a float32 (Q, bags) tensor')
+        if (bags > 1 and out.stride(1) != 1) or (count > 1 and out.stride(0) < bags):
+            raise ValueError('out must have a contiguous last dimension and a row stride of at least bags')
+        if out.device != device or queries.device != device:
+            raise ValueError('queries, rows and out must be on cuda:{} (the device this reader is staged on), got {}, {} and {}'.format(
+                self.device, queries.device, device, out.device))
+        ld_out = out.stride(0) if count > 1 else bags
+        dots = torch.empty((count, bags), dtype=torch.float32, device=device) if return_dots else None
+        bag_norms = torch.empty((bags,), dtype=torch.float32, device=device) if return_norms else None
+        stream = _current_stream(torch, index)
+        norms = None
+        if return_norms:
+            query_norms = torch.empty((count,), dtype=torch.float32, device=device)
+            if count:
+                _memb.dense_row_norms_to_device(index, queries.data_ptr(), count, dim, ld, query_norms.data_ptr(), stream)
+            norms = (query_norms, bag_norms)
+        result = (out, dots, norms) if return_dots or return_norms else out
+        flat = rows.reshape(-1)
+        self._last_query_bags_kernel = self._impl.query_bags_kernel_name() or _memb.dense_pairs_kernel_name()
+        if bags == 0:
+            return result
+        if count == 0:   # (no query: the pooled rows' norms are all there is to work out)
+            if return_norms:
+                for start in range(0, bags, QUERY_BAGS_DEVICE_SLICE):
+                    stop = min(bags, start + QUERY_BAGS_DEVICE_SLICE)
+                    entries, cut = self._bag_slice(torch, flat, offsets, start, stop)
+                    pooled = self.bags_embedding_device(entries, cut, mode=mode)
+                    _memb.dense_row_norms_to_device(index, pooled.data_ptr(), stop - start, dim, dim, bag_norms[start:stop].data_ptr(), stream)
+            return result
+        if self._impl.query_bags_to_device(
+                queries.data_ptr(), count, ld, flat.data_ptr(), flat.numel(), offsets.data_ptr(), bags, code, out.data_ptr(),
+                dots.data_ptr() if return_dots else 0, ld_out, bag_norms.data_ptr() if return_norms else 0, stream):
+            return result
+        self._last_query_bags_kernel = _memb.dense_pairs_kernel_name()
+        temporary = torch.empty((min(bags, QUERY_BAGS_DEVICE_SLICE), 2, dim), dtype=torch.float32, device=device)   # (query, pooled row) side by side
+        for start in range(0, bags, QUERY_BAGS_DEVICE_SLICE):
+            stop = min(bags, start + QUERY_BAGS_DEVICE_SLICE)
+            self._bag_matrix_fallback(
+                torch, queries, count, flat, offsets, start, stop, mode, temporary, out[:, start:stop],
+                dots[:, start:stop] if return_dots else None, bag_norms[start:stop] if return_norms else None, stream)
+        return result
+
+    def bag_similarity_topk_device(self, queries, rows, offsets, k, mode='mean', *, workspace=None):
+        '''The k most similar pooled bags of EVERY query, left on the GPU, without the (bags, dim) matrix of pooled rows and
+        without the (Q, bags) matrix of bag_similarity_matrix_device in device memory: (values, positions), a float32 (Q, k)
+        and an int64 (Q, k) tensor. Row q of bag_similarity_matrix_device(queries, rows, offsets, mode) in
+        similarity_topk_device's order -- a stable descending sort, NaN first, equal cosines lower bag index first --, cut
+        to k; positions are bag indices; where bags < k the last entries are empty: position -1, value -inf. One answer
+        whatever the slicing. For trained models whose dim is a multiple of 4 and at most 512 the fused kernel fills a
+        slice of the bags in a workspace (about 32 MiB, independent of the corpus) and the two selection kernels merge it
+        into the result; otherwise slices of at most 2^16 bags go through bag_similarity_matrix_device's fallback into one
+        reused temporary and the same selection (last_query_bags_topk_kernel says which).
+        queries, rows, offsets, mode : as in bag_similarity_matrix_device
+        k : 1 .. 64 (QUERY_TOPK_MAX_K)
+        workspace : optional contiguous uint8 tensor on the same device, aligned to 8 bytes, of at least
+            self._impl.query_bags_topk_workspace_bytes(Q, bags, k, minimal=True) bytes, for the fused path: a call with it
+            allocates nothing but its two results. Its size decides the slicing, never the result.
+        One model, float32: no k > 64, no missing='skip', no reduction='chunked', no bfloat16 / float16, no ReadersUnion, no
+        ShardedReader.'''
+        import torch
+        code = pool_mode(mode)
+        k = topk_size(k)
+        index, device = self._norms_arguments(torch, rows)
+        queries, count, ld = self._topk_queries(torch, queries, index)
+        bags = self._bag_arguments(torch, rows, offsets, index, device)
+        if queries.device != device:
+            raise ValueError('queries and rows must be on cuda:{} (the device this reader is staged on), got {} and {}'.format(
+                self.device, queries.device, device))
+        flat = rows.reshape(-1)
+        values = torch.empty((count, k), dtype=torch.float32, device=device)
+        positions = torch.empty((count, k), dtype=torch.int64, device=device)
+        stream = _current_stream(torch, index)
+        fused = self._impl.query_bags_topk_kernel_name()
+        self._last_query_bags_topk_kernel = fused if count else ''
+        if count == 0:   # (nothing is launched)
+            return values, positions
+        if fused or bags == 0:
+            if not fused:   # (no bag: topk_merge alone fills the empty slots, whatever the model)
+                self._last_query_bags_topk_kernel = 'topk_merge'
+            if workspace is None:
+                workspace = torch.empty((self._impl.query_bags_topk_workspace_bytes(count, bags, k),), dtype=torch.uint8, device=device)
+            elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1
+                    or not workspace.is_contiguous() or workspace.device != device):
+                raise TypeError('workspace must be a contiguous uint8 tensor on cuda:{}'.format(index))
+            done = self._impl.query_bags_topk_to_device(
+                queries.data_ptr(), count, ld, flat.data_ptr(), flat.numel(), offsets.data_ptr(), bags, code, k,
+                values.data_ptr(), positions.data_ptr(), k, workspace.data_ptr() if workspace.numel() else 0,
+                workspace.numel(), stream)
+            assert done   # (bags == 0 is answered for every model)
+            return values, positions
+        width = min(bags, QUERY_BAGS_DEVICE_SLICE)
+        temporary = torch.empty((width, 2, self.dim), dtype=torch.float32, device=device)
+        matrix = torch.empty((count, width), dtype=torch.float32, device=device)
+        lists = torch.empty((topk_fallback_list_bytes(count, bags, k, QUERY_BAGS_DEVICE_SLICE),), dtype=torch.uint8, device=device)
+        for start in range(0, bags, QUERY_BAGS_DEVICE_SLICE):
+            stop = min(bags, start + QUERY_BAGS_DEVICE_SLICE)
+            self._bag_matrix_fallback(torch, queries, count, flat, offsets, start, stop, mode, temporary, matrix, None, None, stream)
+            _memb.dense_topk_to_device(
+                index, matrix.data_ptr(), count, stop - start, width, start, k, start > 0, values.data_ptr(), positions.data_ptr(),
+                k, lists.data_ptr(), lists.numel(), stream)
+        self._last_query_bags_topk_kernel = _memb.dense_pairs_kernel_name() + '+' + _memb.dense_topk_kernel_name()
+        return values, positions
+
+    def nearest_sentences_device(self, query_sentences, corpus_sentences, k=10, mode='mean'):
+        '''The k nearest sentences of a corpus for each query sentence, as pooled word vectors, left on the GPU: (values,
+        positions), a float32 (len(query_sentences), k) tensor of cosines and an int64 tensor of indices into
+        corpus_sentences, best first in similarity_topk_device's order. The queries are pooled by
+        sentences_embedding_device(query_sentences, mode); the corpus is flattened (flatten_sentences), resolved on the
+        device (resolve_rows_device) and never pooled into memory: the rest is bag_similarity_topk_device. An unknown word
+        is a zero row that counts; a sentence without words has cosine 0. Slots beyond len(corpus_sentences) are position
+        -1, value -inf.'''
+        import torch
+        pool_mode(mode)
+        k = topk_size(k)
+        index = self._impl.device()
+        if index == _memb.HOST_DEVICE:
+            raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
+        device = 'cuda:{}'.format(index)
+        queries = self.sentences_embedding_device(query_sentences, mode=mode)
+        words, offsets = flatten_sentences(corpus_sentences)
+        rows = self.resolve_rows_device(words) if words else torch.empty((0,), dtype=torch.int32, device=device)
+        on_device = torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).to(device)
+        return self.bag_similarity_topk_device(queries, rows, on_device, k, mode=mode)
+
+    def _host_bag_arguments(self, queries, rows, offsets):
+        queries = np.asarray(queries)
+        if queries.dtype != np.float32:
+            raise TypeError('queries must be a float32 array of shape (Q, dim) or (dim,)')
+        if queries.ndim == 1:
+            queries = queries[None, :]
+        if queries.ndim != 2 or queries.shape[1] != self.dim:
+            raise ValueError('queries must have shape (Q, {}) or ({},), got {}'.format(self.dim, self.dim, queries.shape))
+        rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        return np.ascontiguousarray(queries), rows, bag_offsets(offsets, rows.size)
+
+    def _host_bag_slices(self, rows, offsets, mean):
+        '''(start, stop, pooled rows of the bags [start, stop)) in slices of QUERY_BAGS_HOST_SLICE bags: bags_embedding's sums'''
+        bags = offsets.size - 1
+        for start in range(0, bags, QUERY_BAGS_HOST_SLICE):
+            stop = min(bags, start + QUERY_BAGS_HOST_SLICE)
+            cut = offsets[start:stop + 1]
+            first, last = int(cut[0]), int(cut[-1])
+            entries = rows[first:last]
+
+            def slice_values(begin, end):
+                yield self.rows_embedding(entries[begin:end])
+
+            pooled, _ = pool_slices_host(cut - first, last - first, self.dim, BAGS_HOST_CHUNK, mean, False, slice_values)
+            yield start, stop, pooled
+
+    def bag_similarity_matrix(self, queries, rows, offsets, mode='mean', return_dots=False, return_norms=False):
+        '''bag_similarity_matrix_device for host arrays: a numpy float32 (Q, dim) or (dim,) array of queries, numpy row ids
+        and bags + 1 offsets (bags_embedding's: ascending, within 0 .. len(rows)) in, a numpy float32 (Q, bags) array of
+        cosines out, or (cosines, dots, (query_norms, bag_norms)) with either flag (None where not asked for). A reader on
+        a GPU sends everything up and brings the matrix back; a device='cpu' reader evaluates the same contract in numpy
+        (pool_slices_host, pair_similarity_host) in bounded slices of bags, each pooled once for every query: the same bits.'''
+        code = pool_mode(mode)
+        queries, rows, offsets = self._host_bag_arguments(queries, rows, offsets)
+        count, bags = queries.shape[0], offsets.size - 1
+        if self._impl.device() != _memb.HOST_DEVICE:
+            import torch
+            device = 'cuda:{}'.format(self._impl.device())
+            result = self.bag_similarity_matrix_device(
+                torch.from_numpy(queries).to(device), torch.from_numpy(rows.view(np.int32)).to(device),
+                torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).to(device), mode=mode, return_dots=return_dots,
+                return_norms=return_norms)
+            if not (return_dots or return_norms):
+                return result.cpu().numpy()
+            cosines, dots, norms = result
+            return (cosines.cpu().numpy(), None if dots is None else dots.cpu().numpy(),
+                    None if norms is None else tuple(part.cpu().numpy() for part in norms))
+        cosines = np.zeros((count, bags), dtype=np.float32)
+        dots = np.zeros((count, bags), dtype=np.float32)
+        bag_norms = np.zeros(bags, dtype=np.float32)
+        for start, stop, pooled in self._host_bag_slices(rows, offsets, code == _memb.POOL_MEAN):
+            bag_norms[start:stop] = row_norms_host(pooled)
+            for q in range(count):
+                cosines[q, start:stop], dots[q, start:stop], _ = pair_similarity_host(np.broadcast_to(queries[q], pooled.shape), pooled)
+        if return_dots or return_norms:
+            return (cosines, dots if return_dots else None,
+                    (row_norms_host(queries) if count else np.zeros(0, dtype=np.float32), bag_norms) if return_norms else None)
+        return cosines
+
+    def bag_similarity_topk(self, queries, rows, offsets, k, mode='mean'):
+        '''bag_similarity_topk_device for host arrays: (values float32 (Q, k), positions int64 (Q, k)), positions being bag
+        indices. A reader on a GPU sends everything up and brings the result back; a device='cpu' reader takes
+        bag_similarity_matrix's slices one by one and selects by the same order in numpy (topk_host): the same bits.'''
+        code = pool_mode(mode)
+        queries, rows, offsets = self._host_bag_arguments(queries, rows, offsets)
+        k = topk_size(k)
+        count = queries.shape[0]
+        if self._impl.device() != _memb.HOST_DEVICE:
+            import torch
+            device = 'cuda:{}'.format(self._impl.device())
+            values, positions = self.bag_similarity_topk_device(
+                torch.from_numpy(queries).to(device), torch.from_numpy(rows.view(np.int32)).to(device),
+                torch.from_numpy(offsets.astype(np.uint32).view(np.int32)).to(device), k, mode=mode)
+            return values.cpu().numpy(), positions.cpu().numpy()
+        values = np.full((count, k), -np.inf, dtype=np.float32)
+        positions = np.full((count, k), -1, dtype=np.int64)
+        for start, stop, pooled in self._host_bag_slices(rows, offsets, code == _memb.POOL_MEAN):
+            matrix = np.zeros((count, stop - start), dtype=np.float32)
+            for q in range(count):
+                matrix[q] = pair_similarity_host(np.broadcast_to(queries[q], pooled.shape), pooled)[0]
             values, positions = topk_host(matrix, k, start, (values, positions))
         return values, positions
 
