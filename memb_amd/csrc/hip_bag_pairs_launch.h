@@ -2,60 +2,33 @@
 // memb_hip_bag_pairs.hip, which hands it over as an address (hip_bag_pairs.h), and the implementations of the entry points.
 //
 // Host code of libmemb_hip.so. Included by memb_hip.hip only, inside its anonymous namespace, after hip_pooled_launch.h
-// (the byte count of a pooled lookup) and hip_norms_launch.h (floatAligned).
+// (launchPooledKernel, the byte count of a pooled lookup) and hip_norms_launch.h (floatAligned), on hip_fused_launch.h's
+// model test and plan. bag_pairs_trained takes the models of FUSED_BAG_PAIRS: no two words per tile are needed.
 #pragma once
 
-// Whether bag_pairs_trained takes this model at all: pool_trained's register form, which needs no two words per tile.
-const char* fusedBagPairsRefusal(const memb_hip_ctx* ctx)
-{
-    if (ctx->storage != memb::wire::Storage_Trained) {
-        return "fused bag-pair kernel: trained storage only (pool the bags and use the dense pair entry point)";
-    }
-    if (ctx->dim % 4 != 0 || ctx->dim > memb_bag_pairs::TRAINED_MAX_DIM) {
-        return "fused bag-pair kernel: dim must be a multiple of 4 and at most 512 (pool the bags and use the dense pair entry point)";
-    }
-    return nullptr;
-}
-
-// bag_pairs_trained over the 2 * pairs bags of pairs >= 1 pairs, for a model fusedBagPairsRefusal lets through. Planned
-// like launchPooled plans pool_trained -- a decode of n rows by the one-tile kernel, whose LDS and block size the kernel
-// shares --, and a wavefront owns a run of consecutive whole bags (memb_pooled::pooledBagsPerWave, for the wavefronts the
-// kernel's registers let a CU hold) rounded up to an even count: a pair is never split.
+// bag_pairs_trained over the 2 * pairs bags of pairs >= 1 pairs and n >= 0 entries, for a model fusedRefusal lets through:
+// the fused plan (planFused), and a wavefront owns a run of consecutive whole bags (memb_pooled::pooledBagsPerWave, for the
+// wavefronts the kernel's registers let a CU hold) rounded up to an even count: a pair is never split.
 int launchBagPairsTrained(
     memb_hip_ctx* ctx, const uint32_t* rows, size_t n, memb_pooled::PoolParams pool, memb_bag_pairs::BagPairParams params,
     hipStream_t stream)
 {
-    Lookup planned = floatRows(rows, std::max<size_t>(n, 1), nullptr, ctx->dim, 0);
-    TrainedPlan plan;
-    const int code = planTrained(ctx, planned, 0, false, rowsUnordered(ctx, false), &plan);
+    FusedPlan plan;
+    const int code = planFused(ctx, floatRows(rows, n, nullptr, ctx->dim, 0), &plan);
     if (code != MEMB_HIP_OK) {
         return code;
     }
-    const TrainedGeometry geometry = plan.geometry;
-    if (!geometry.waves) {
-        return fail(MEMB_HIP_ERR_INVALID, "decode tables and bitstream slots do not fit into LDS");
-    }
-    TrainedParams trained = lookupParams(ctx);
-    trained.rows = rows;
-    trained.out = nullptr;
-    trained.n = n;
-    trained.ld = planned.ld;
-    trained.colOff = planned.colOff;
-    if (!lookupParamsConsistent(ctx, trained, geometry)) {
-        return fail(MEMB_HIP_ERR_INVALID, "internal error: inconsistent decode geometry");
-    }
-    const memb_bag_pairs::BagPairKernel kernel = memb_bag_pairs::trainedKernel(lookupHasSub(ctx), ctx->fast);
+    const memb::KernelHandle kernel = memb_bag_pairs::trainedKernel(lookupHasSub(ctx), ctx->fast);
     if (!kernel.address) {
         return fail(MEMB_HIP_ERR_INVALID, std::string("internal error: no ") + kernel.name + " kernel for this model");
     }
     static_assert(4 * memb_bag_pairs::TRAINED_WAVES_PER_SIMD == ONE_TILE_WAVES_PER_CU, "planned like pool_trained");
     const uint32_t owned = memb_pooled::pooledBagsPerWave(
-        ctx->switches.tilesPerWave, trained.wordsPerWave, n, pool.bags, ctx->cuCount, 4 * memb_bag_pairs::TRAINED_WAVES_PER_SIMD);
-    void* arguments[3] = {&trained, &pool, &params};
+        ctx->switches.tilesPerWave, plan.trained.wordsPerWave, n, pool.bags, ctx->cuCount,
+        4 * memb_bag_pairs::TRAINED_WAVES_PER_SIMD);
+    void* arguments[3] = {&plan.trained, &pool, &params};
     // (at most (1 << 16) + 1 before, even after)
-    return launchPooledKernel(
-        memb_pooled::PoolKernel{kernel.address, kernel.name}, geometry.waves, owned + (owned & 1u), geometry.ldsBytes, &pool,
-        arguments, stream);
+    return launchPooledKernel(kernel, plan.waves, owned + (owned & 1u), plan.ldsBytes, &pool, arguments, stream);
 }
 
 // memb_hip_bag_pair_similarity_device
@@ -81,8 +54,8 @@ int bag_pair_similarity_device_checked(
     if (pairs > (size_t(1) << 35) || n > (size_t(1) << 37)) {
         return fail(MEMB_HIP_ERR_INVALID, "batch too large");
     }
-    if (const char* refusal = fusedBagPairsRefusal(ctx)) {
-        return fail(MEMB_HIP_UNSUPPORTED, refusal);
+    if (const char* reason = fusedRefusal(ctx, FUSED_BAG_PAIRS)) {
+        return failFused(FUSED_BAG_PAIRS, reason);
     }
     if (pairs == 0) {
         return MEMB_HIP_OK;
@@ -97,7 +70,7 @@ int bag_pair_similarity_device_checked(
 // memb_hip_bag_pairs_kernel_name
 const char* bag_pairs_kernel_name(const memb_hip_ctx* ctx)
 {
-    return !ctx || fusedBagPairsRefusal(ctx) ? "" : memb_bag_pairs::trainedKernel(lookupHasSub(ctx), ctx->fast).name;
+    return !ctx || fusedRefusal(ctx, FUSED_BAG_PAIRS) ? "" : memb_bag_pairs::trainedKernel(lookupHasSub(ctx), ctx->fast).name;
 }
 
 // memb_hip_bag_pairs_algorithmic_bytes

@@ -2,94 +2,49 @@
 // hands them over as addresses (hip_norms.h), and the implementations of the entry points.
 //
 // Host code of libmemb_hip.so. Included by memb_hip.hip only, inside its anonymous namespace, after the other entry points
-// (hip_entry_points.h: the plain decode and its byte count are used here); see that file for the overview.
+// (hip_entry_points.h: the plain decode and its byte count are used here), on hip_fused_launch.h's model test, plan and
+// launch ends; see memb_hip.hip for the overview.
 #pragma once
 
-// Whether the fused kernels take this model at all: norms_trained's condition, and unit_trained's before alignment.
-const char* fusedNormsRefusal(const memb_hip_ctx* ctx)
-{
-    if (ctx->storage != memb::wire::Storage_Trained) {
-        return "fused norm kernels: trained storage only (decode the rows and use the dense entry points)";
-    }
-    if (ctx->dim % 4 != 0 || ctx->dim > memb_norms::TRAINED_MAX_DIM) {
-        return "fused norm kernels: dim must be a multiple of 4 and at most 512 (decode the rows and use the dense entry points)";
-    }
-    return nullptr;
-}
-
-// unit_trained stores 16-byte pieces: the aligned output of the decode's piece form.
+// unit_trained stores 16-byte pieces: a model the fused kernels take (fusedRefusal: norms_trained's only condition) and
+// the aligned output of the decode's piece form.
 bool unitRowsFused(const memb_hip_ctx* ctx, const void* out, size_t ld, size_t colOff)
 {
-    return !fusedNormsRefusal(ctx) && outputMode(ctx->dim, ld, colOff, out, 4, WAVE / ctx->lanesPerWord) != OUT_SCALAR;
+    return !fusedRefusal(ctx, FUSED_NORMS) && outputMode(ctx->dim, ld, colOff, out, 4, WAVE / ctx->lanesPerWord) != OUT_SCALAR;
 }
 
-// norms_trained (out null) or unit_trained over rows[0 .. n), n >= 1, for a model fusedNormsRefusal lets through. Planned
-// like launchPooled -- a decode of n rows by the one-tile kernel (planTrained, force = 0, usual index), whose LDS and block
-// size these kernels share -- and a wavefront owns a run of consecutive rows sized like a run of bags of one entry
+// norms_trained (out null) or unit_trained over rows[0 .. n), n >= 1, for a model fusedRefusal lets through: the fused
+// plan (planFused), and a wavefront owns a run of consecutive rows sized like a run of bags of one entry
 // (memb_pooled::pooledBagsPerWave).
 int launchNormsTrained(
     memb_hip_ctx* ctx, const uint32_t* rows, size_t n, float* out, size_t ld, size_t colOff, float* norms, hipStream_t stream)
 {
     const bool unit = out != nullptr;
-    Lookup planned = floatRows(rows, n, out, unit ? ld : ctx->dim, unit ? colOff : 0);
-    TrainedPlan plan;
-    const int code = planTrained(ctx, planned, 0, false, rowsUnordered(ctx, false), &plan);
+    FusedPlan plan;
+    const int code = planFused(ctx, floatRows(rows, n, out, unit ? ld : ctx->dim, unit ? colOff : 0), &plan);
     if (code != MEMB_HIP_OK) {
         return code;
     }
-    const TrainedGeometry geometry = plan.geometry;
-    if (!geometry.waves) {
-        return fail(MEMB_HIP_ERR_INVALID, "decode tables and bitstream slots do not fit into LDS");
-    }
-    TrainedParams trained = lookupParams(ctx);
-    trained.rows = rows;
-    trained.out = out;
-    trained.n = n;
-    trained.ld = planned.ld;
-    trained.colOff = planned.colOff;
-    if (!lookupParamsConsistent(ctx, trained, geometry) || planned.ld < planned.colOff + trained.dim) {
-        return fail(MEMB_HIP_ERR_INVALID, "internal error: inconsistent decode geometry");
-    }
-    const memb_norms::NormKernel kernel = memb_norms::trainedKernel(lookupHasSub(ctx), ctx->fast, unit);
+    const memb::KernelHandle kernel = memb_norms::trainedKernel(lookupHasSub(ctx), ctx->fast, unit);
     if (!kernel.address) {
         return fail(MEMB_HIP_ERR_INVALID, std::string("internal error: no ") + kernel.name + " kernel for this model");
     }
     memb_norms::NormParams params{};
     params.norms = norms;
     params.rowsPerWave = memb_pooled::pooledBagsPerWave(
-        ctx->switches.tilesPerWave, trained.wordsPerWave, n, n, ctx->cuCount, ONE_TILE_WAVES_PER_CU);
-    const uint64_t perBlock = uint64_t(geometry.waves) * params.rowsPerWave;
-    const uint64_t blocks = (n + perBlock - 1) / perBlock;
-    if (blocks >= 0x7FFFFFFFull) {
-        return fail(MEMB_HIP_ERR_INVALID, "batches too large for one launch");
-    }
-    void* arguments[2] = {&trained, &params};
-    const hipError_t status = launchKernelAddress(
-        kernel.address, dim3(static_cast<uint32_t>(blocks)), dim3(geometry.waves * WAVE), geometry.ldsBytes, stream, arguments);
-    if (status != hipSuccess) {
-        return fail(MEMB_HIP_ERR_DEVICE, std::string(kernel.name) + " launch: " + hipGetErrorString(status));
-    }
-    return MEMB_HIP_OK;
+        ctx->switches.tilesPerWave, plan.trained.wordsPerWave, n, n, ctx->cuCount, ONE_TILE_WAVES_PER_CU);
+    void* arguments[2] = {&plan.trained, &params};
+    return launchOwnedRuns(kernel, plan.waves, plan.ldsBytes, params.rowsPerWave, n, arguments, stream);
 }
 
 // norms_dense (params.out null) or unit_dense: one wavefront per row, params.n >= 1.
 int launchNormsDense(const memb_norms::DenseNormParams& dense, hipStream_t stream)
 {
     memb_norms::DenseNormParams params = dense;
-    const memb_norms::NormKernel kernel = memb_norms::denseKernel(params.out != nullptr);
-    const uint64_t blocks = (params.n + memb_norms::DENSE_WAVES - 1) / memb_norms::DENSE_WAVES;
-    if (blocks >= 0x7FFFFFFFull) {
-        return fail(MEMB_HIP_ERR_INVALID, "batches too large for one launch");
-    }
     void* arguments[1] = {&params};
-    // (no dynamic LDS: launched as it is, like the chunk kernels of hip_pooled_launch.h)
-    hipError_t status = hipLaunchKernel(
-        kernel.address, dim3(static_cast<uint32_t>(blocks)), dim3(memb_norms::DENSE_WAVES * WAVE), arguments, 0, stream);
-    status = status != hipSuccess ? status : hipGetLastError();
-    if (status != hipSuccess) {
-        return fail(MEMB_HIP_ERR_DEVICE, std::string(kernel.name) + " launch: " + hipGetErrorString(status));
-    }
-    return MEMB_HIP_OK;
+    return launchWithoutLds(
+        memb_norms::denseKernel(params.out != nullptr), memb::gridBlocks(memb_norms::DENSE_WAVES, 1, params.n),
+        memb_norms::DENSE_WAVES * WAVE, arguments, stream);
 }
 
 bool floatAligned(const void* pointer)
@@ -106,8 +61,8 @@ int row_norms_device_checked(memb_hip_ctx* ctx, const uint32_t* rows, size_t n, 
     if (!floatAligned(norms) || !floatAligned(rows)) {
         return fail(MEMB_HIP_ERR_INVALID, "rows and norms must be aligned to 4 bytes");
     }
-    if (const char* refusal = fusedNormsRefusal(ctx)) {
-        return fail(MEMB_HIP_UNSUPPORTED, refusal);
+    if (const char* reason = fusedRefusal(ctx, FUSED_NORMS)) {
+        return failFused(FUSED_NORMS, reason);
     }
     if (n == 0) {
         return MEMB_HIP_OK;
@@ -206,7 +161,7 @@ const char* norms_kernel_name(const memb_hip_ctx* ctx, bool unit, const void* ou
         return memb_norms::denseKernel(unit).name;
     }
     if (!unit) {
-        return fusedNormsRefusal(ctx) ? "" : memb_norms::trainedKernel(lookupHasSub(ctx), ctx->fast, false).name;
+        return fusedRefusal(ctx, FUSED_NORMS) ? "" : memb_norms::trainedKernel(lookupHasSub(ctx), ctx->fast, false).name;
     }
     return unitRowsFused(ctx, out, ld, colOff) ? memb_norms::trainedKernel(lookupHasSub(ctx), ctx->fast, true).name
                                               : memb_norms::denseKernel(true).name;

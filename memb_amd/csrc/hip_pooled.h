@@ -7,6 +7,8 @@
 
 #include <cstdint>
 
+#include "hip_kernel_handle.h"
+
 namespace memb_pooled {
 
 struct PoolParams {
@@ -43,12 +45,8 @@ inline uint32_t pooledBagsPerWave(
 
 enum class PoolStorage { Trained, Uniform, Full };
 
-struct PoolKernel {
-    const void* address;   // null where no instance exists: HAS_SUB with FAST, an outType that is no MEMB_HIP_OUT_*
-    const char* name;      // the kernel family, for error messages
-};
-
-// The kernel of a pooled lookup. known: the family that leaves a bag's unknown entries out and counts the others.
+// The kernel of a pooled lookup (address null where no instance exists: HAS_SUB with FAST, an outType that is no
+// MEMB_HIP_OUT_*; name: the kernel family). known: the family that leaves a bag's unknown entries out and counts the others.
 //   Trained   pool_trained<HAS_SUB, FAST, VEC4> (fp32), pool_trained_narrow<HAS_SUB, FAST, VEC4, OUT> (bf16 / fp16),
 //             pool_known_trained<HAS_SUB, FAST, VEC4, OUT>. vec4: register accumulators of pieces of four elements (dim a
 //             multiple of 4 and at most TRAINED_VEC4_MAX_DIM, out / ld / colOff aligned to a piece), else the column form
@@ -57,6 +55,6 @@ struct PoolKernel {
 //   Uniform   pool_uniform, pool_uniform_narrow<OUT>, pool_known_uniform<OUT>   } one wavefront per bag, blocks of
 //   Full      pool_full, pool_full_narrow<OUT>, pool_known_full<OUT>            } ROWWISE_WAVES wavefronts
 // (hasSub, fast, vec4: trained only)
-PoolKernel pooledKernel(PoolStorage storage, bool hasSub, bool fast, bool vec4, int outType, bool known);
+memb::KernelHandle pooledKernel(PoolStorage storage, bool hasSub, bool fast, bool vec4, int outType, bool known);
 
 }  // namespace memb_pooled

@@ -3,36 +3,25 @@
 // entry points with the argument check they share.
 //
 // Host code of libmemb_hip.so. Included by memb_hip.hip only, inside its anonymous namespace, after the plans
-// (hip_decode_plan.h); see that file for the overview.
+// (hip_decode_plan.h) and the fused launches' shared part (hip_fused_launch.h); see that file for the overview.
 #pragma once
 
-// The end of every sequential pooled launch: a grid of blocks of `waves` wavefronts that own bagsPerWave bags each -- which
-// the kernel reads from `pool`, its second argument.
+// The end of every sequential pooled launch (launchOwnedRuns): a wavefront owns bagsPerWave bags, which the kernel reads
+// from `pool`, its second argument.
 int launchPooledKernel(
-    const memb_pooled::PoolKernel& kernel, uint32_t waves, uint32_t bagsPerWave, uint32_t ldsBytes, memb_pooled::PoolParams* pool,
+    const memb::KernelHandle& kernel, uint32_t waves, uint32_t bagsPerWave, uint32_t ldsBytes, memb_pooled::PoolParams* pool,
     void** arguments, hipStream_t stream)
 {
     pool->bagsPerWave = bagsPerWave;
-    const uint64_t perBlock = uint64_t(waves) * bagsPerWave;
-    const uint64_t blocks = (pool->bags + perBlock - 1) / perBlock;
-    if (blocks >= 0x7FFFFFFFull) {
-        return fail(MEMB_HIP_ERR_INVALID, "batches too large for one launch");
-    }
-    const hipError_t status =
-        launchKernelAddress(kernel.address, dim3(static_cast<uint32_t>(blocks)), dim3(waves * WAVE), ldsBytes, stream, arguments);
-    if (status != hipSuccess) {
-        return fail(MEMB_HIP_ERR_DEVICE, std::string(kernel.name) + " launch: " + hipGetErrorString(status));
-    }
-    return MEMB_HIP_OK;
+    return launchOwnedRuns(kernel, waves, ldsBytes, bagsPerWave, pool->bags, arguments, stream);
 }
 
 // A pooled lookup (include/memb_hip_pooled.h): `lookup` describes the ENTRIES (rows, n) and the bags' rows (out, ld, colOff),
 // `pool` the bags, both checked by the caller (PooledCall::check: at least one bag, neither count beyond a launch). One kernel of
 // memb_hip_pooled.hip, whatever the storage, the element and `known` (memb_pooled::pooledKernel of hip_pooled.h).
-// Trained: planned like a decode of n rows by the one-tile kernel (planTrained, force = 0, usual index) -- pool_trained is
-// that kernel up to the symbol tile -- and a wavefront owns a run of consecutive whole bags (memb_pooled::pooledBagsPerWave).
-// Bags' rows of a narrow outType run the bf16 / fp16 kernels on the same plan: they add fp32 centroids, so LDS is planned
-// for an fp32 codebook whatever the element, and only the choice of the piece form follows it.
+// Trained: the fused plan (planFused) -- pool_trained is the one-tile decode up to the symbol tile -- and a wavefront owns
+// a run of consecutive whole bags (memb_pooled::pooledBagsPerWave). Bags' rows of a narrow outType run the bf16 / fp16
+// kernels on the same plan, and only the choice of the piece form follows the element.
 // Uniform, full: one wavefront per bag, blocks of ROWWISE_WAVES.
 // known (include/memb_hip_pooled_known.h): the pool_known_* kernels, which leave a bag's unknown entries out and take the
 // counts as a third parameter -- the same plan, the same geometry.
@@ -44,7 +33,7 @@ int launchPooled(
     bool vec4 = false;
     memb_pooled::KnownParams counted = known ? *known : memb_pooled::KnownParams{};
     void* arguments[3] = {nullptr, &pool, &counted};   // (the third: the pool_known_* kernels only)
-    TrainedParams trained;
+    FusedPlan fused;
     UniformParams uniform;
     FullParams full;
     uint32_t waves = memb_pooled::ROWWISE_WAVES;
@@ -53,35 +42,19 @@ int launchPooled(
     switch (ctx->storage) {
         case memb::wire::Storage_Trained: {
             storage = memb_pooled::PoolStorage::Trained;
-            Lookup planned = lookup;
-            planned.n = std::max<size_t>(lookup.n, 1);
-            planned.outType = MEMB_HIP_OUT_F32;
-            TrainedPlan plan;
-            const int code = planTrained(ctx, planned, 0, false, rowsUnordered(ctx, false), &plan);
+            const int code = planFused(ctx, lookup, &fused);
             if (code != MEMB_HIP_OK) {
                 return code;
             }
-            const TrainedGeometry geometry = plan.geometry;
-            if (!geometry.waves) {
-                return fail(MEMB_HIP_ERR_INVALID, "decode tables and bitstream slots do not fit into LDS");
-            }
-            trained = lookupParams(ctx);
-            trained.rows = lookup.rows;
-            trained.out = static_cast<float*>(lookup.out);
-            trained.n = lookup.n;
-            trained.ld = lookup.ld;
-            trained.colOff = lookup.colOff;
-            if (!lookupParamsConsistent(ctx, trained, geometry) || lookup.ld < lookup.colOff + trained.dim) {
-                return fail(MEMB_HIP_ERR_INVALID, "internal error: inconsistent decode geometry");
-            }
+            const uint32_t wordsPerWave = fused.trained.wordsPerWave;
             const bool pieces =
-                outputMode(ctx->dim, lookup.ld, lookup.colOff, lookup.out, lookup.elementBytes(), trained.wordsPerWave) != OUT_SCALAR;
+                outputMode(ctx->dim, lookup.ld, lookup.colOff, lookup.out, lookup.elementBytes(), wordsPerWave) != OUT_SCALAR;
             vec4 = pieces && ctx->dim <= memb_pooled::TRAINED_VEC4_MAX_DIM;
-            waves = geometry.waves;
-            ldsBytes = geometry.ldsBytes;
+            waves = fused.waves;
+            ldsBytes = fused.ldsBytes;
             bagsPerWave = memb_pooled::pooledBagsPerWave(
-                ctx->switches.tilesPerWave, trained.wordsPerWave, lookup.n, pool.bags, ctx->cuCount, ONE_TILE_WAVES_PER_CU);
-            arguments[0] = &trained;
+                ctx->switches.tilesPerWave, wordsPerWave, lookup.n, pool.bags, ctx->cuCount, ONE_TILE_WAVES_PER_CU);
+            arguments[0] = &fused.trained;
             break;
         }
         case memb::wire::Storage_Uniform:
@@ -101,7 +74,7 @@ int launchPooled(
         default:
             return fail(MEMB_HIP_ERR_INVALID, "context has no storage");
     }
-    const memb_pooled::PoolKernel kernel =
+    const memb::KernelHandle kernel =
         memb_pooled::pooledKernel(storage, lookupHasSub(ctx), ctx->fast, vec4, lookup.outType, known != nullptr);
     if (!kernel.address) {
         return fail(MEMB_HIP_ERR_INVALID, std::string("internal error: no ") + kernel.name + " kernel for this output");
@@ -135,7 +108,7 @@ int launchPooledUnion(
     params.rowPieces = first->dim / 4;
     params.rowMagic = magicFor(params.rowPieces, uint64_t(plan.wordsPerWave) * params.rowPieces);
     layOutUnionWave(ctxs, count, plan.wordsPerWave, &params);
-    const memb_pooled::PoolKernel kernel =
+    const memb::KernelHandle kernel =
         memb_pooled::pooledUnionKernel(plan.hasSub && !plan.allFast, plan.allFast, static_cast<int>(count), outType);
     if (!kernel.address) {
         return fail(MEMB_HIP_ERR_INVALID, std::string("internal error: no ") + kernel.name + " kernel for this output");
@@ -163,7 +136,7 @@ int launchPooledUnion(
 // (memb_pooled::pooledDenseKernel), one wavefront per bag.
 int launchPooledDense(memb_pooled::DenseParams params, memb_pooled::PoolParams pool, int outType, hipStream_t stream)
 {
-    const memb_pooled::PoolKernel kernel = memb_pooled::pooledDenseKernel(outType);
+    const memb::KernelHandle kernel = memb_pooled::pooledDenseKernel(outType);
     if (!kernel.address) {
         return fail(MEMB_HIP_ERR_INVALID, std::string("internal error: no ") + kernel.name + " kernel for this output");
     }
@@ -347,15 +320,11 @@ int pool_rows_chunked_checked(
     plan.bagStart = reinterpret_cast<uint32_t*>(base + layout.bagStart);
     plan.derived = derived;
     void* planArguments[] = {&plan};
+    // (no dynamic LDS, and the scan kernels have static LDS of their own: launchWithoutLds. Every count here is at least 1
+    // and, by maxChunks' bound above, fits a launch.)
     const auto enqueue = [&](const char* name, const void* kernel, uint64_t blocks, void** arguments) {
-        // (no dynamic LDS: launched as they are, not through launchKernelAddress, which raises a kernel's dynamic LDS limit
-        // to the whole 160 KiB -- refused for a kernel that has static LDS of its own, as the scan kernels have)
-        hipError_t status = !kernel ? hipErrorInvalidDeviceFunction
-                                    : hipLaunchKernel(kernel, dim3(static_cast<uint32_t>(blocks)), dim3(memb_pooled::PLAN_THREADS),
-                                                      arguments, 0, queue);
-        status = status != hipSuccess ? status : hipGetLastError();
-        return status == hipSuccess ? MEMB_HIP_OK
-                                    : fail(MEMB_HIP_ERR_DEVICE, std::string(name) + " launch: " + hipGetErrorString(status));
+        return launchWithoutLds(
+            memb::KernelHandle{kernel, name}, static_cast<uint32_t>(blocks), memb_pooled::PLAN_THREADS, arguments, queue);
     };
     int code = MEMB_HIP_OK;
     if (layout.planBlocks > 1) {   // (one block: its bags' starts need no other block's sum)
@@ -400,12 +369,10 @@ int pool_rows_chunked_checked(
     sums.dim = ctx->dim;
     sums.mean = checked.pool.mean;
     const uint64_t waves = uint64_t(bags) * ((ctx->dim + WAVE - 1) / WAVE);
-    const uint64_t blocks = (waves + memb_pooled::PLAN_THREADS / WAVE - 1) / (memb_pooled::PLAN_THREADS / WAVE);
-    if (blocks >= 0x7FFFFFFFull) {
-        return fail(MEMB_HIP_ERR_INVALID, "batches too large for one launch");
-    }
     void* sumArguments[] = {&sums};
-    return enqueue("pool_chunks", memb_pooled::poolChunksKernel(outType), blocks, sumArguments);
+    return enqueue(
+        "pool_chunks", memb_pooled::poolChunksKernel(outType), memb::gridBlocks(memb_pooled::PLAN_THREADS / WAVE, 1, waves),
+        sumArguments);
 }
 
 int pooled_algorithmic_bytes_checked(

@@ -31,9 +31,9 @@ struct DenseParams {
 // pool_trained_union<HAS_SUB, FAST, COUNT, OUT>: COUNT trained models of one geometry (launchTrainedUnion's conditions),
 // register accumulators of 16-byte pieces (dim a multiple of 4 and at most TRAINED_VEC4_MAX_DIM, out / ld / colOff aligned
 // to a piece). address is null where no instance exists: a count outside 2 .. 4, HAS_SUB with FAST, an unknown outType.
-PoolKernel pooledUnionKernel(bool hasSub, bool fast, int count, int outType);
+memb::KernelHandle pooledUnionKernel(bool hasSub, bool fast, int count, int outType);
 
 // pool_dense<OUT>: one wavefront per bag, blocks of ROWWISE_WAVES wavefronts, any dim and alignment.
-PoolKernel pooledDenseKernel(int outType);
+memb::KernelHandle pooledDenseKernel(int outType);
 
 }  // namespace memb_pooled

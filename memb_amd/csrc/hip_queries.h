@@ -1,13 +1,14 @@
 // The kernel of memb_hip_queries.hip (include/memb_hip_queries.h: the cosine, the dot product and the row norm of every
 // candidate row of a group against that group's fp32 query vector, from the compressed rows of a trained model) as
-// memb_hip.hip launches it (hip_queries_launch.h): host addresses for hipLaunchKernel, in the style of hip_pairs.h. The
+// memb_hip.hip launches it (hip_queries_launch.h): host addresses for hipLaunchKernel, as memb::KernelHandle. The
 // first parameter of the kernel is the TrainedParams of hip_trained_kernels.h -- rows[0 .. n) are the ENTRIES, the
 // candidates of every group one after the other; out / ld / colOff are not used --, its second the QueryParams below.
 #pragma once
 
 #include <cstdint>
 
-#include "hip_pairs.h"
+#include "hip_pairs.h"    // (the unit builds on pairs_trained's device code, which takes the PairParams)
+#include "hip_pooled.h"   // (pooledBagsPerWave: the run a wavefront owns, hip_queries_launch.h)
 
 namespace memb_queries {
 
@@ -22,15 +23,13 @@ struct QueryParams {
     uint32_t entriesPerWave;       // consecutive entries a wavefront owns (launch geometry, never the result)
 };
 
-constexpr uint32_t TRAINED_MAX_DIM = memb_pairs::TRAINED_MAX_DIM;   // two pieces per lane: the contract's layout
 // Wavefronts per SIMD the kernel's registers allow (tests/test_queries_isa.py): what the launch
 // plans its grid for.
 constexpr uint32_t TRAINED_WAVES_PER_SIMD = 7;
 
-using QueryKernel = memb_pairs::PairKernel;   // address (null where no instance exists: HAS_SUB with FAST) and family name
-
-// query_trained<HAS_SUB, FAST>: dim a multiple of 4 and at most TRAINED_MAX_DIM, any words per wavefront. LDS and block
-// size are pool_trained's (an fp32 codebook).
-QueryKernel trainedKernel(bool hasSub, bool fast);
+// query_trained<HAS_SUB, FAST>: dim a multiple of 4 and at most memb_pooled::TRAINED_VEC4_MAX_DIM, any words per
+// wavefront. LDS and block size are pool_trained's (an fp32 codebook). address: null where no instance exists, HAS_SUB
+// with FAST.
+memb::KernelHandle trainedKernel(bool hasSub, bool fast);
 
 }  // namespace memb_queries

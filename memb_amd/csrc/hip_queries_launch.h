@@ -3,10 +3,10 @@
 // its launch and the implementations of the entry points.
 //
 // Host code of libmemb_hip.so. Included by memb_hip.hip only, inside its anonymous namespace, after hip_pooled_launch.h
-// (the byte count of a pooled lookup), hip_norms_launch.h and hip_pairs_launch.h. The first part -- what a call is refused
-// for, how its entries are spread over wavefronts and blocks, how many entries lie in a group -- needs neither a context nor
-// the HIP runtime: tests/cpp/queries_planning_main.cpp includes this file with MEMB_HIP_QUERIES_PLANNING_ONLY defined and
-// runs that part alone under the host sanitizers.
+// (the byte count of a pooled lookup), on hip_fused_launch.h's model test, plan and launch ends. The first part -- what a
+// call is refused for, how its entries are spread over wavefronts and blocks (memb::gridBlocks of hip_kernel_handle.h), how
+// many entries lie in a group -- needs neither a context nor the HIP runtime: tests/cpp/queries_planning_main.cpp includes
+// this file with MEMB_HIP_QUERIES_PLANNING_ONLY defined and runs that part alone under the host sanitizers.
 #pragma once
 
 // What memb_hip_query_similarity_device refuses before it looks at the model, or null. dim: the model's.
@@ -51,9 +51,7 @@ inline QueryGrid planQueryGrid(uint32_t tilesPerWaveSwitch, uint32_t wordsPerWav
     QueryGrid grid{};
     grid.entriesPerWave = memb_pooled::pooledBagsPerWave(
         tilesPerWaveSwitch, wordsPerWave, n, n, cuCount, 4 * memb_queries::TRAINED_WAVES_PER_SIMD);
-    const uint64_t perBlock = uint64_t(waves ? waves : 1) * grid.entriesPerWave;
-    const uint64_t blocks = (n + perBlock - 1) / perBlock;
-    grid.blocks = blocks >= 0x7FFFFFFFull ? 0 : static_cast<uint32_t>(blocks);
+    grid.blocks = memb::gridBlocks(waves, grid.entriesPerWave, n);
     return grid;
 }
 
@@ -84,58 +82,27 @@ inline uint64_t queryBytes(
 
 #ifndef MEMB_HIP_QUERIES_PLANNING_ONLY
 
-// Whether query_trained takes this model at all: bag_pairs_trained's models, one word per wavefront included.
-const char* fusedQueriesRefusal(const memb_hip_ctx* ctx)
-{
-    if (ctx->storage != memb::wire::Storage_Trained) {
-        return "fused query kernel: trained storage only (decode the candidates and use the dense pair entry point)";
-    }
-    if (ctx->dim % 4 != 0 || ctx->dim > memb_queries::TRAINED_MAX_DIM) {
-        return "fused query kernel: dim must be a multiple of 4 and at most 512 (decode the candidates and use the dense pair entry point)";
-    }
-    return nullptr;
-}
-
-// query_trained over n >= 1 entries of groups >= 1 groups, for a model fusedQueriesRefusal lets through. Planned like
-// launchPairsTrained -- a decode of n rows by the one-tile kernel, whose LDS and block size the kernel shares.
+// query_trained over n >= 1 entries of groups >= 1 groups, for a model fusedRefusal lets through (FUSED_QUERIES: one word
+// per wavefront included): the fused plan (planFused) and planQueryGrid's run.
 int launchQueriesTrained(memb_hip_ctx* ctx, const uint32_t* rows, size_t n, memb_queries::QueryParams params, hipStream_t stream)
 {
-    Lookup planned = floatRows(rows, n, nullptr, ctx->dim, 0);
-    TrainedPlan plan;
-    const int code = planTrained(ctx, planned, 0, false, rowsUnordered(ctx, false), &plan);
+    FusedPlan plan;
+    const int code = planFused(ctx, floatRows(rows, n, nullptr, ctx->dim, 0), &plan);
     if (code != MEMB_HIP_OK) {
         return code;
     }
-    const TrainedGeometry geometry = plan.geometry;
-    if (!geometry.waves) {
-        return fail(MEMB_HIP_ERR_INVALID, "decode tables and bitstream slots do not fit into LDS");
+    if (plan.trained.wordsPerWave < 1 || plan.trained.wordsPerWave > WAVE) {
+        return inconsistentGeometry();
     }
-    TrainedParams trained = lookupParams(ctx);
-    trained.rows = rows;
-    trained.out = nullptr;
-    trained.n = n;
-    trained.ld = planned.ld;
-    trained.colOff = planned.colOff;
-    if (!lookupParamsConsistent(ctx, trained, geometry) || trained.wordsPerWave < 1 || trained.wordsPerWave > WAVE) {
-        return fail(MEMB_HIP_ERR_INVALID, "internal error: inconsistent decode geometry");
-    }
-    const memb_queries::QueryKernel kernel = memb_queries::trainedKernel(lookupHasSub(ctx), ctx->fast);
+    const memb::KernelHandle kernel = memb_queries::trainedKernel(lookupHasSub(ctx), ctx->fast);
     if (!kernel.address) {
         return fail(MEMB_HIP_ERR_INVALID, std::string("internal error: no ") + kernel.name + " kernel for this model");
     }
     static_assert(4 * memb_queries::TRAINED_WAVES_PER_SIMD == ONE_TILE_WAVES_PER_CU, "planned like pairs_trained");
-    const QueryGrid grid = planQueryGrid(ctx->switches.tilesPerWave, trained.wordsPerWave, n, ctx->cuCount, geometry.waves);
-    if (!grid.blocks) {
-        return fail(MEMB_HIP_ERR_INVALID, "batches too large for one launch");
-    }
-    params.entriesPerWave = grid.entriesPerWave;
-    void* arguments[2] = {&trained, &params};
-    const hipError_t status = launchKernelAddress(
-        kernel.address, dim3(grid.blocks), dim3(geometry.waves * WAVE), geometry.ldsBytes, stream, arguments);
-    if (status != hipSuccess) {
-        return fail(MEMB_HIP_ERR_DEVICE, std::string(kernel.name) + " launch: " + hipGetErrorString(status));
-    }
-    return MEMB_HIP_OK;
+    params.entriesPerWave =
+        planQueryGrid(ctx->switches.tilesPerWave, plan.trained.wordsPerWave, n, ctx->cuCount, plan.waves).entriesPerWave;
+    void* arguments[2] = {&plan.trained, &params};
+    return launchOwnedRuns(kernel, plan.waves, plan.ldsBytes, params.entriesPerWave, n, arguments, stream);
 }
 
 // memb_hip_query_similarity_device
@@ -152,8 +119,8 @@ int query_similarity_device_checked(
     if (n == 0 || groups == 0) {   // a no-op for every model, as the header says
         return MEMB_HIP_OK;
     }
-    if (const char* refusal = fusedQueriesRefusal(ctx)) {
-        return fail(MEMB_HIP_UNSUPPORTED, refusal);
+    if (const char* reason = fusedRefusal(ctx, FUSED_QUERIES)) {
+        return failFused(FUSED_QUERIES, reason);
     }
     DeviceScope deviceScope(ctx->device);
     HIP_TRY(deviceScope.status());
@@ -171,7 +138,7 @@ int query_similarity_device_checked(
 // memb_hip_query_kernel_name
 const char* query_kernel_name(const memb_hip_ctx* ctx)
 {
-    return !ctx || fusedQueriesRefusal(ctx) ? "" : memb_queries::trainedKernel(lookupHasSub(ctx), ctx->fast).name;
+    return !ctx || fusedRefusal(ctx, FUSED_QUERIES) ? "" : memb_queries::trainedKernel(lookupHasSub(ctx), ctx->fast).name;
 }
 
 // memb_hip_query_algorithmic_bytes

@@ -4,7 +4,8 @@
 // points.
 //
 // Host code of libmemb_hip.so. Included by memb_hip.hip only, inside its anonymous namespace, after hip_query_topk_launch.h
-// (planTopkSlice, queryTopkListBytes, launchTopk) and hip_pooled_launch.h (launchPooledKernel). The first part needs
+// (planTopkSlice, queryTopkListBytes, launchTopk) and hip_pooled_launch.h (launchPooledKernel), on hip_fused_launch.h's
+// model test and plan. The first part needs
 // neither a context nor the HIP runtime: tests/cpp/query_bags_planning_main.cpp includes this file behind
 // hip_query_topk_launch.h with MEMB_HIP_QUERIES_PLANNING_ONLY defined and runs that part alone under the host sanitizers.
 #pragma once
@@ -112,54 +113,29 @@ inline const char* queryBagsTopkArgumentsRefusal(
 
 #ifndef MEMB_HIP_QUERIES_PLANNING_ONLY
 
-// Whether query_bags_trained takes this model at all: bag_pairs_trained's models, pool_trained's register form.
-const char* fusedQueryBagsRefusal(const memb_hip_ctx* ctx)
-{
-    if (ctx->storage != memb::wire::Storage_Trained) {
-        return "fused query-bags kernel: trained storage only (pool the bags and use the dense pair entry point)";
-    }
-    if (ctx->dim % 4 != 0 || ctx->dim > memb_query_bags::TRAINED_MAX_DIM) {
-        return "fused query-bags kernel: dim must be a multiple of 4 and at most 512 (pool the bags and use the dense pair entry point)";
-    }
-    return nullptr;
-}
-
-// query_bags_trained over bags >= 1 bags and nQueries >= 1 queries, for a model fusedQueryBagsRefusal lets through.
-// Planned like launchBagPairsTrained: a decode of n rows by the one-tile kernel, whose LDS and block size the kernel
-// shares.
+// query_bags_trained over bags >= 1 bags of n >= 0 entries and nQueries >= 1 queries, for a model fusedRefusal lets through
+// (FUSED_QUERY_BAGS: bag_pairs_trained's models): the fused plan (planFused) and planQueryBagsPerWave's run.
 int launchQueryBagsTrained(
     memb_hip_ctx* ctx, const uint32_t* rows, size_t n, memb_pooled::PoolParams pool, memb_query_matrix::QueryMatrixParams params,
     hipStream_t stream)
 {
-    Lookup planned = floatRows(rows, std::max<size_t>(n, 1), nullptr, ctx->dim, 0);
-    TrainedPlan plan;
-    const int code = planTrained(ctx, planned, 0, false, rowsUnordered(ctx, false), &plan);
+    FusedPlan plan;
+    const int code = planFused(ctx, floatRows(rows, n, nullptr, ctx->dim, 0), &plan);
     if (code != MEMB_HIP_OK) {
         return code;
     }
-    const TrainedGeometry geometry = plan.geometry;
-    if (!geometry.waves) {
-        return fail(MEMB_HIP_ERR_INVALID, "decode tables and bitstream slots do not fit into LDS");
+    if (plan.trained.wordsPerWave < 1 || plan.trained.wordsPerWave > WAVE) {
+        return inconsistentGeometry();
     }
-    TrainedParams trained = lookupParams(ctx);
-    trained.rows = rows;
-    trained.out = nullptr;
-    trained.n = n;
-    trained.ld = planned.ld;
-    trained.colOff = planned.colOff;
-    if (!lookupParamsConsistent(ctx, trained, geometry) || trained.wordsPerWave < 1 || trained.wordsPerWave > WAVE) {
-        return fail(MEMB_HIP_ERR_INVALID, "internal error: inconsistent decode geometry");
-    }
-    const memb_query_bags::QueryBagsKernel kernel = memb_query_bags::trainedKernel(lookupHasSub(ctx), ctx->fast);
+    const memb::KernelHandle kernel = memb_query_bags::trainedKernel(lookupHasSub(ctx), ctx->fast);
     if (!kernel.address) {
         return fail(MEMB_HIP_ERR_INVALID, std::string("internal error: no ") + kernel.name + " kernel for this model");
     }
     const uint32_t owned = planQueryBagsPerWave(
-        ctx->switches.tilesPerWave, trained.wordsPerWave, n, pool.bags, params.nQueries, ctx->cuCount,
+        ctx->switches.tilesPerWave, plan.trained.wordsPerWave, n, pool.bags, params.nQueries, ctx->cuCount,
         4 * memb_query_bags::TRAINED_WAVES_PER_SIMD);
-    void* arguments[3] = {&trained, &pool, &params};
-    return launchPooledKernel(
-        memb_pooled::PoolKernel{kernel.address, kernel.name}, geometry.waves, owned, geometry.ldsBytes, &pool, arguments, stream);
+    void* arguments[3] = {&plan.trained, &pool, &params};
+    return launchPooledKernel(kernel, plan.waves, owned, plan.ldsBytes, &pool, arguments, stream);
 }
 
 // memb_hip_query_bags_device
@@ -177,8 +153,8 @@ int query_bags_device_checked(
     if (bags == 0 || nQueries == 0) {   // a no-op for every model, as the header says
         return MEMB_HIP_OK;
     }
-    if (const char* refusal = fusedQueryBagsRefusal(ctx)) {
-        return fail(MEMB_HIP_UNSUPPORTED, refusal);
+    if (const char* reason = fusedRefusal(ctx, FUSED_QUERY_BAGS)) {
+        return failFused(FUSED_QUERY_BAGS, reason);
     }
     DeviceScope deviceScope(ctx->device);
     HIP_TRY(deviceScope.status());
@@ -197,7 +173,7 @@ int query_bags_device_checked(
 // memb_hip_query_bags_kernel_name
 const char* query_bags_kernel_name(const memb_hip_ctx* ctx)
 {
-    return !ctx || fusedQueryBagsRefusal(ctx) ? "" : memb_query_bags::trainedKernel(lookupHasSub(ctx), ctx->fast).name;
+    return !ctx || fusedRefusal(ctx, FUSED_QUERY_BAGS) ? "" : memb_query_bags::trainedKernel(lookupHasSub(ctx), ctx->fast).name;
 }
 
 // memb_hip_query_bags_algorithmic_bytes
@@ -239,8 +215,9 @@ int query_bags_topk_device_checked(
     if (nQueries == 0) {
         return MEMB_HIP_OK;
     }
-    if (bags && fusedQueryBagsRefusal(ctx)) {   // (bags == 0 fills the empty slots for every model)
-        return fail(MEMB_HIP_UNSUPPORTED, fusedQueryBagsRefusal(ctx));
+    const char* reason = bags ? fusedRefusal(ctx, FUSED_QUERY_BAGS) : nullptr;   // (bags == 0 fills the empty slots for every model)
+    if (reason) {
+        return failFused(FUSED_QUERY_BAGS, reason);
     }
     DeviceScope deviceScope(ctx->device);
     HIP_TRY(deviceScope.status());
@@ -276,7 +253,7 @@ size_t query_bags_topk_workspace_bytes(const memb_hip_ctx* ctx, size_t nQueries,
 // memb_hip_query_bags_topk_kernel_name
 const char* query_bags_topk_kernel_name(const memb_hip_ctx* ctx)
 {
-    return !ctx || fusedQueryBagsRefusal(ctx) ? "" : "query_bags_trained+topk_select+topk_merge";
+    return !ctx || fusedRefusal(ctx, FUSED_QUERY_BAGS) ? "" : "query_bags_trained+topk_select+topk_merge";
 }
 
 #endif  // MEMB_HIP_QUERIES_PLANNING_ONLY

@@ -4,7 +4,8 @@
 // the entry points.
 //
 // Host code of libmemb_hip.so. Included by memb_hip.hip only, inside its anonymous namespace, after hip_queries_launch.h
-// (planQueryGrid, fusedQueriesRefusal). The first part -- what a call is refused for, what it counts as moved, how its
+// (planQueryGrid), on hip_fused_launch.h's model test (query_trained's models: FUSED_QUERIES), plan and launch ends. The
+// first part -- what a call is refused for, what it counts as moved, how its
 // candidates are spread over wavefronts and blocks -- needs neither a context nor the HIP runtime:
 // tests/cpp/query_matrix_planning_main.cpp includes this file behind hip_queries_launch.h with
 // MEMB_HIP_QUERIES_PLANNING_ONLY defined and runs that part alone under the host sanitizers.
@@ -66,56 +67,34 @@ inline QueryGrid planQueryMatrixGrid(
     const bool oneBlock = nQueries <= std::min<uint64_t>(memb_query_matrix::QUERY_BLOCK, perStore);
     const uint64_t shared = grid.entriesPerWave / (nQueries ? nQueries : 1);
     grid.entriesPerWave = oneBlock ? static_cast<uint32_t>(std::max<uint64_t>(tile, shared)) : tile;
-    const uint64_t perBlock = uint64_t(waves ? waves : 1) * grid.entriesPerWave;
-    const uint64_t blocks = (n + perBlock - 1) / perBlock;
-    grid.blocks = blocks >= 0x7FFFFFFFull ? 0 : static_cast<uint32_t>(blocks);
+    grid.blocks = memb::gridBlocks(waves, grid.entriesPerWave, n);
     return grid;
 }
 
 #ifndef MEMB_HIP_QUERIES_PLANNING_ONLY
 
-// query_matrix_trained over n >= 1 candidates and nQueries >= 1 queries, for a model fusedQueriesRefusal lets through.
-// Planned like launchQueriesTrained -- a decode of n rows by the one-tile kernel, whose LDS and block size the kernel shares.
+// query_matrix_trained over n >= 1 candidates and nQueries >= 1 queries, for a model fusedRefusal lets through
+// (FUSED_QUERIES): the fused plan (planFused) and planQueryMatrixGrid's run.
 int launchQueryMatrixTrained(
     memb_hip_ctx* ctx, const uint32_t* rows, size_t n, memb_query_matrix::QueryMatrixParams params, hipStream_t stream)
 {
-    Lookup planned = floatRows(rows, n, nullptr, ctx->dim, 0);
-    TrainedPlan plan;
-    const int code = planTrained(ctx, planned, 0, false, rowsUnordered(ctx, false), &plan);
+    FusedPlan plan;
+    const int code = planFused(ctx, floatRows(rows, n, nullptr, ctx->dim, 0), &plan);
     if (code != MEMB_HIP_OK) {
         return code;
     }
-    const TrainedGeometry geometry = plan.geometry;
-    if (!geometry.waves) {
-        return fail(MEMB_HIP_ERR_INVALID, "decode tables and bitstream slots do not fit into LDS");
+    if (plan.trained.wordsPerWave < 1 || plan.trained.wordsPerWave > WAVE) {
+        return inconsistentGeometry();
     }
-    TrainedParams trained = lookupParams(ctx);
-    trained.rows = rows;
-    trained.out = nullptr;
-    trained.n = n;
-    trained.ld = planned.ld;
-    trained.colOff = planned.colOff;
-    if (!lookupParamsConsistent(ctx, trained, geometry) || trained.wordsPerWave < 1 || trained.wordsPerWave > WAVE) {
-        return fail(MEMB_HIP_ERR_INVALID, "internal error: inconsistent decode geometry");
-    }
-    const memb_query_matrix::QueryMatrixKernel kernel = memb_query_matrix::trainedKernel(lookupHasSub(ctx), ctx->fast);
+    const memb::KernelHandle kernel = memb_query_matrix::trainedKernel(lookupHasSub(ctx), ctx->fast);
     if (!kernel.address) {
         return fail(MEMB_HIP_ERR_INVALID, std::string("internal error: no ") + kernel.name + " kernel for this model");
     }
     static_assert(memb_query_matrix::TRAINED_WAVES_PER_SIMD == memb_queries::TRAINED_WAVES_PER_SIMD, "planned from planQueryGrid");
-    const QueryGrid grid = planQueryMatrixGrid(
-        ctx->switches.tilesPerWave, trained.wordsPerWave, n, params.nQueries, ctx->cuCount, geometry.waves);
-    if (!grid.blocks) {
-        return fail(MEMB_HIP_ERR_INVALID, "batches too large for one launch");
-    }
-    params.entriesPerWave = grid.entriesPerWave;
-    void* arguments[2] = {&trained, &params};
-    const hipError_t status = launchKernelAddress(
-        kernel.address, dim3(grid.blocks), dim3(geometry.waves * WAVE), geometry.ldsBytes, stream, arguments);
-    if (status != hipSuccess) {
-        return fail(MEMB_HIP_ERR_DEVICE, std::string(kernel.name) + " launch: " + hipGetErrorString(status));
-    }
-    return MEMB_HIP_OK;
+    params.entriesPerWave = planQueryMatrixGrid(
+        ctx->switches.tilesPerWave, plan.trained.wordsPerWave, n, params.nQueries, ctx->cuCount, plan.waves).entriesPerWave;
+    void* arguments[2] = {&plan.trained, &params};
+    return launchOwnedRuns(kernel, plan.waves, plan.ldsBytes, params.entriesPerWave, n, arguments, stream);
 }
 
 // memb_hip_query_matrix_device
@@ -132,8 +111,8 @@ int query_matrix_device_checked(
     if (n == 0 || nQueries == 0) {   // a no-op for every model, as the header says
         return MEMB_HIP_OK;
     }
-    if (const char* refusal = fusedQueriesRefusal(ctx)) {   // (query_trained's models)
-        return fail(MEMB_HIP_UNSUPPORTED, refusal);
+    if (const char* reason = fusedRefusal(ctx, FUSED_QUERIES)) {   // (query_trained's models)
+        return failFused(FUSED_QUERIES, reason);
     }
     DeviceScope deviceScope(ctx->device);
     HIP_TRY(deviceScope.status());
@@ -151,7 +130,7 @@ int query_matrix_device_checked(
 // memb_hip_query_matrix_kernel_name
 const char* query_matrix_kernel_name(const memb_hip_ctx* ctx)
 {
-    return !ctx || fusedQueriesRefusal(ctx) ? "" : memb_query_matrix::trainedKernel(lookupHasSub(ctx), ctx->fast).name;
+    return !ctx || fusedRefusal(ctx, FUSED_QUERIES) ? "" : memb_query_matrix::trainedKernel(lookupHasSub(ctx), ctx->fast).name;
 }
 
 // memb_hip_query_matrix_algorithmic_bytes

@@ -1,11 +1,11 @@
 // The kernels of memb_hip_query_topk.hip (include/memb_hip_query_topk.h: the k best columns of every row of a dense fp32
 // matrix, by the total order of that header) as memb_hip.hip launches them (hip_query_topk_launch.h): host addresses for
-// hipLaunchKernel, in the style of hip_query_matrix.h. Both kernels take ONE parameter, the TopkParams below.
+// hipLaunchKernel, as memb::KernelHandle. Both kernels take ONE parameter, the TopkParams below.
 #pragma once
 
 #include <cstdint>
 
-#include "hip_query_matrix.h"
+#include "hip_query_matrix.h"   // (MAX_QUERIES: the workspace of memb_hip_query_topk_device, hip_query_topk_launch.h)
 
 namespace memb_query_topk {
 
@@ -46,13 +46,11 @@ constexpr uint64_t SLICE_MATRIX_BYTES = 32ull << 20;
 constexpr uint64_t MIN_SLICE = 64;
 constexpr uint64_t MAX_SLICE = 1ull << 30;
 
-using TopkKernel = memb_query_matrix::QueryMatrixKernel;   // address and family name
-
 // topk_select: one wavefront per (row, segment) writes its sorted list to the workspace. Grid: ceil(nRows * segments /
 // WAVES_PER_BLOCK) blocks of WAVES_PER_BLOCK wavefronts. No LDS.
-TopkKernel selectKernel();
+memb::KernelHandle selectKernel();
 // topk_merge: one wavefront per row merges the row's lists and, with `merge`, what the output holds, and writes the
 // output. Grid: ceil(nRows / WAVES_PER_BLOCK) blocks. No LDS.
-TopkKernel mergeKernel();
+memb::KernelHandle mergeKernel();
 
 }  // namespace memb_query_topk

@@ -4,7 +4,8 @@
 // the entry points.
 //
 // Host code of libmemb_hip.so. Included by memb_hip.hip only, inside its anonymous namespace, after
-// hip_query_matrix_launch.h (query_matrix_device_checked, queryMatrixArgumentsRefusal). The first part needs neither a
+// hip_query_matrix_launch.h (query_matrix_device_checked, queryMatrixArgumentsRefusal), on hip_fused_launch.h's model
+// test (FUSED_QUERIES) and launchWithoutLds. The first part needs neither a
 // context nor the HIP runtime: tests/cpp/query_topk_planning_main.cpp includes this file behind hip_query_matrix_launch.h
 // with MEMB_HIP_QUERIES_PLANNING_ONLY defined and runs that part alone under the host sanitizers.
 #pragma once
@@ -175,19 +176,18 @@ int launchTopk(
     params.segmentLength = plan.segmentLength;
     params.merge = merge ? 1 : 0;
     void* arguments[1] = {&params};
-    const dim3 block(memb_query_topk::WAVES_PER_BLOCK * WAVE);
-    const memb_query_topk::TopkKernel kernels[2] = {memb_query_topk::selectKernel(), memb_query_topk::mergeKernel()};
+    const memb::KernelHandle kernels[2] = {memb_query_topk::selectKernel(), memb_query_topk::mergeKernel()};
     const uint64_t waves[2] = {uint64_t(nRows) * plan.segments, nRows};
     for (int stage = 0; stage < 2; ++stage) {
         if (!waves[stage]) {   // (no column: topk_merge alone)
             continue;
         }
-        const uint64_t blocks = (waves[stage] + memb_query_topk::WAVES_PER_BLOCK - 1) / memb_query_topk::WAVES_PER_BLOCK;
-        // (no dynamic LDS: launched as it is, like pairs_dense)
-        hipError_t status = hipLaunchKernel(kernels[stage].address, dim3(static_cast<uint32_t>(blocks)), block, arguments, 0, stream);
-        status = status != hipSuccess ? status : hipGetLastError();
-        if (status != hipSuccess) {
-            return fail(MEMB_HIP_ERR_DEVICE, std::string(kernels[stage].name) + " launch: " + hipGetErrorString(status));
+        // (at most MAX_ROWS * MAX_SEGMENTS wavefronts: they fit a launch)
+        const int code = launchWithoutLds(
+            kernels[stage], memb::gridBlocks(memb_query_topk::WAVES_PER_BLOCK, 1, waves[stage]),
+            memb_query_topk::WAVES_PER_BLOCK * WAVE, arguments, stream);
+        if (code != MEMB_HIP_OK) {
+            return code;
         }
     }
     return MEMB_HIP_OK;
@@ -224,8 +224,9 @@ int query_topk_device_checked(
     if (nQueries == 0) {
         return MEMB_HIP_OK;
     }
-    if (n && fusedQueriesRefusal(ctx)) {   // (n == 0 fills the empty slots for every model)
-        return fail(MEMB_HIP_UNSUPPORTED, fusedQueriesRefusal(ctx));
+    const char* reason = n ? fusedRefusal(ctx, FUSED_QUERIES) : nullptr;   // (n == 0 fills the empty slots for every model)
+    if (reason) {
+        return failFused(FUSED_QUERIES, reason);
     }
     DeviceScope deviceScope(ctx->device);
     HIP_TRY(deviceScope.status());
@@ -262,7 +263,7 @@ const char* query_topk_kernel_name(const memb_hip_ctx* ctx)
     if (!ctx) {
         return "topk_select+topk_merge";
     }
-    return fusedQueriesRefusal(ctx) ? "" : "query_matrix_trained+topk_select+topk_merge";
+    return fusedRefusal(ctx, FUSED_QUERIES) ? "" : "query_matrix_trained+topk_select+topk_merge";
 }
 
 // memb_hip_query_topk_algorithmic_bytes

@@ -33,8 +33,10 @@
 // dependency order, each a header of its own: hip_context.h -- the context, its switches, device allocation and
 // teardown; hip_kernel_table.h -- the decode kernel table and the one kernel launch helper; hip_decode_plan.h -- every
 // launch-geometry rule (which kernel a batch runs, with what block size and LDS), nothing that enqueues work;
-// hip_decode_launch.h -- the decode launches; hip_pooled_launch.h -- the pooled launches and the entry points above
-// them; hip_host_path.h -- how rows reach host buffers (pinned ring, copy threads, centroid indices over PCIe);
+// hip_decode_launch.h -- the decode launches; hip_fused_launch.h -- what the decode-fused families of the other
+// units share: the models they take, the one plan (planFused) and the two launch ends, for every kernel handed over as a
+// memb::KernelHandle (hip_kernel_handle.h, which also sizes their grids); hip_pooled_launch.h -- the pooled launches and
+// the entry points above them; hip_host_path.h -- how rows reach host buffers (pinned ring, copy threads, centroid indices over PCIe);
 // hip_staging.h -- staging of a model to HBM (context creation); hip_encoder.h, hip_words.h -- the write side and
 // word -> row on the device; hip_entry_points.h -- the implementations of the other entry points;
 // memb_hip_narrow.hip -- the bf16 / fp16 kernels, a translation unit of its own
@@ -138,6 +140,7 @@ namespace {
 #include "hip_kernel_table.h"
 #include "hip_decode_plan.h"
 #include "hip_decode_launch.h"
+#include "hip_fused_launch.h"
 #include "hip_pooled_launch.h"
 #include "hip_host_path.h"
 #include "hip_staging.h"
@@ -313,7 +316,7 @@ const char* memb_hip_pool_union_kernel_name(const memb_hip_ctx* first)
 
 const char* memb_hip_pool_dense_kernel_name(int out_type)
 {
-    const memb_pooled::PoolKernel kernel = memb_pooled::pooledDenseKernel(out_type);
+    const memb::KernelHandle kernel = memb_pooled::pooledDenseKernel(out_type);
     return kernel.address ? kernel.name : "";
 }
 

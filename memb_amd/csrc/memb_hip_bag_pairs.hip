@@ -63,10 +63,10 @@ struct BagPairTable {
 
 namespace memb_bag_pairs {
 
-BagPairKernel trainedKernel(bool hasSub, bool fast)
+memb::KernelHandle trainedKernel(bool hasSub, bool fast)
 {
     static const BagPairTable table;
-    return BagPairKernel{table.trained[hasSub][fast], "bag_pairs_trained"};
+    return memb::KernelHandle{table.trained[hasSub][fast], "bag_pairs_trained"};
 }
 
 }  // namespace memb_bag_pairs

@@ -85,16 +85,16 @@ private:
 
 namespace memb_norms {
 
-NormKernel trainedKernel(bool hasSub, bool fast, bool unit)
+memb::KernelHandle trainedKernel(bool hasSub, bool fast, bool unit)
 {
     static const NormTable table;
-    return NormKernel{table.trained[hasSub][fast][unit], unit ? "unit_trained" : "norms_trained"};
+    return memb::KernelHandle{table.trained[hasSub][fast][unit], unit ? "unit_trained" : "norms_trained"};
 }
 
-NormKernel denseKernel(bool unit)
+memb::KernelHandle denseKernel(bool unit)
 {
-    return unit ? NormKernel{reinterpret_cast<const void*>(&unit_dense), "unit_dense"}
-                : NormKernel{reinterpret_cast<const void*>(&norms_dense), "norms_dense"};
+    return unit ? memb::KernelHandle{reinterpret_cast<const void*>(&unit_dense), "unit_dense"}
+                : memb::KernelHandle{reinterpret_cast<const void*>(&norms_dense), "norms_dense"};
 }
 
 }  // namespace memb_norms

@@ -64,15 +64,15 @@ struct PairTable {
 
 namespace memb_pairs {
 
-PairKernel trainedKernel(bool hasSub, bool fast)
+memb::KernelHandle trainedKernel(bool hasSub, bool fast)
 {
     static const PairTable table;
-    return PairKernel{table.trained[hasSub][fast], "pairs_trained"};
+    return memb::KernelHandle{table.trained[hasSub][fast], "pairs_trained"};
 }
 
-PairKernel denseKernel()
+memb::KernelHandle denseKernel()
 {
-    return PairKernel{reinterpret_cast<const void*>(&pairs_dense), "pairs_dense"};
+    return memb::KernelHandle{reinterpret_cast<const void*>(&pairs_dense), "pairs_dense"};
 }
 
 }  // namespace memb_pairs

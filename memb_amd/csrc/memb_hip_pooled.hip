@@ -480,11 +480,11 @@ const void* kernelOf(memb_pooled::PoolStorage storage, bool hasSub, bool fast, b
 
 namespace memb_pooled {
 
-PoolKernel pooledKernel(PoolStorage storage, bool hasSub, bool fast, bool vec4, int outType, bool known)
+memb::KernelHandle pooledKernel(PoolStorage storage, bool hasSub, bool fast, bool vec4, int outType, bool known)
 {
     static const char* const names[2][3] = {{"pool_trained", "pool_uniform", "pool_full"},
                                             {"pool_known_trained", "pool_known_uniform", "pool_known_full"}};
-    PoolKernel kernel{nullptr, names[known][static_cast<int>(storage)]};
+    memb::KernelHandle kernel{nullptr, names[known][static_cast<int>(storage)]};
     if (outType >= 0 && outType < OUT_TYPES) {
         kernel.address = known ? kernelOf<true>(storage, hasSub, fast, vec4, outType) : kernelOf<false>(storage, hasSub, fast, vec4, outType);
     }

@@ -284,22 +284,22 @@ const UnionPoolTable& unionPoolTable()
 
 namespace memb_pooled {
 
-PoolKernel pooledUnionKernel(bool hasSub, bool fast, int count, int outType)
+memb::KernelHandle pooledUnionKernel(bool hasSub, bool fast, int count, int outType)
 {
     if (count < 2 || count > UNION_MAX_MODELS || outType < 0 || outType >= OUT_TYPES) {
-        return PoolKernel{nullptr, "pool_trained_union"};
+        return memb::KernelHandle{nullptr, "pool_trained_union"};
     }
     const Instance& instance = unionPoolTable().trained[hasSub][fast][count][outType];
-    return PoolKernel{instance.address, instance.address ? instance.name.c_str() : "pool_trained_union"};
+    return memb::KernelHandle{instance.address, instance.address ? instance.name.c_str() : "pool_trained_union"};
 }
 
-PoolKernel pooledDenseKernel(int outType)
+memb::KernelHandle pooledDenseKernel(int outType)
 {
     if (outType < 0 || outType >= OUT_TYPES) {
-        return PoolKernel{nullptr, "pool_dense"};
+        return memb::KernelHandle{nullptr, "pool_dense"};
     }
     const Instance& instance = unionPoolTable().dense[outType];
-    return PoolKernel{instance.address, instance.name.c_str()};
+    return memb::KernelHandle{instance.address, instance.name.c_str()};
 }
 
 }  // namespace memb_pooled

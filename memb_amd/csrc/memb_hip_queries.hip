@@ -62,10 +62,10 @@ struct QueryTable {
 
 namespace memb_queries {
 
-QueryKernel trainedKernel(bool hasSub, bool fast)
+memb::KernelHandle trainedKernel(bool hasSub, bool fast)
 {
     static const QueryTable table;
-    return QueryKernel{table.trained[hasSub][fast], "query_trained"};
+    return memb::KernelHandle{table.trained[hasSub][fast], "query_trained"};
 }
 
 }  // namespace memb_queries

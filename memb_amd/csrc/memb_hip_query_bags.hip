@@ -68,10 +68,10 @@ struct QueryBagsTable {
 
 namespace memb_query_bags {
 
-QueryBagsKernel trainedKernel(bool hasSub, bool fast)
+memb::KernelHandle trainedKernel(bool hasSub, bool fast)
 {
     static const QueryBagsTable table;
-    return QueryBagsKernel{table.trained[hasSub][fast], "query_bags_trained"};
+    return memb::KernelHandle{table.trained[hasSub][fast], "query_bags_trained"};
 }
 
 }  // namespace memb_query_bags

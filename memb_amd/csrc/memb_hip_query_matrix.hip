@@ -66,10 +66,10 @@ struct QueryMatrixTable {
 
 namespace memb_query_matrix {
 
-QueryMatrixKernel trainedKernel(bool hasSub, bool fast)
+memb::KernelHandle trainedKernel(bool hasSub, bool fast)
 {
     static const QueryMatrixTable table;
-    return QueryMatrixKernel{table.trained[hasSub][fast], "query_matrix_trained"};
+    return memb::KernelHandle{table.trained[hasSub][fast], "query_matrix_trained"};
 }
 
 }  // namespace memb_query_matrix

@@ -39,14 +39,14 @@ __global__ __launch_bounds__(memb_query_topk::WAVES_PER_BLOCK * WAVE) void topk_
 
 namespace memb_query_topk {
 
-TopkKernel selectKernel()
+memb::KernelHandle selectKernel()
 {
-    return TopkKernel{reinterpret_cast<const void*>(&topk_select), "topk_select"};
+    return memb::KernelHandle{reinterpret_cast<const void*>(&topk_select), "topk_select"};
 }
 
-TopkKernel mergeKernel()
+memb::KernelHandle mergeKernel()
 {
-    return TopkKernel{reinterpret_cast<const void*>(&topk_merge), "topk_merge"};
+    return memb::KernelHandle{reinterpret_cast<const void*>(&topk_merge), "topk_merge"};
 }
 
 }  // namespace memb_query_topk

@@ -114,6 +114,29 @@ void grids()
     expect(spread.blocks == 1250 && spread.entriesPerWave == 1, "5 000 entries spread", spread.blocks, spread.entriesPerWave);
 }
 
+// memb::gridBlocks (hip_kernel_handle.h), which every launch whose wavefronts own a run of items sizes its grid with:
+// ceil(count / (waves * perWave)) blocks, 0 from 0x7FFFFFFF blocks on.
+void blockCounts()
+{
+    expect(memb::gridBlocks(4, 1, 1) == 1, "one item: one block");
+    expect(memb::gridBlocks(16, 65536, 1) == 1, "one item under the longest run: one block");
+    expect(memb::gridBlocks(4, 6, 24 * 10) == 10, "whole blocks", memb::gridBlocks(4, 6, 24 * 10));
+    expect(memb::gridBlocks(4, 6, 24 * 10 + 1) == 11, "one item more: one block more", memb::gridBlocks(4, 6, 24 * 10 + 1));
+    expect(memb::gridBlocks(4, 6, 24 * 10 - 1) == 10, "one item fewer: the last block is not full");
+    expect(memb::gridBlocks(0, 0, 5) == 5, "0 counts as 1 in either factor");
+    // the limit: 0x7FFFFFFE blocks still fit one launch, 0x7FFFFFFF do not
+    const uint64_t perBlock = 4 * 3;
+    const uint64_t fits = 0x7FFFFFFEull * perBlock;   // the largest count of 0x7FFFFFFE blocks
+    expect(memb::gridBlocks(4, 3, fits) == 0x7FFFFFFEu, "the largest count that fits", memb::gridBlocks(4, 3, fits));
+    expect(memb::gridBlocks(4, 3, fits + 1) == 0, "the smallest count that does not");
+    expect(memb::gridBlocks(1, 1, 0x7FFFFFFEull) == 0x7FFFFFFEu && memb::gridBlocks(1, 1, 0x7FFFFFFFull) == 0, "blocks of one item");
+    expect(memb::gridBlocks(4, 1, 1ull << 37) == 0, "far beyond the limit");
+    // planQueryGrid sizes its grid with it
+    const QueryGrid grid = planQueryGrid(0, 8, 50000, 256, 4);
+    expect(grid.blocks == memb::gridBlocks(4, grid.entriesPerWave, 50000) && grid.blocks == 2084, "planQueryGrid's blocks", grid.blocks);
+    expect(planQueryGrid(0, 8, 1ull << 36, 1, 1).blocks == 0, "planQueryGrid: too many blocks");
+}
+
 void countedEntries()
 {
     uint64_t entries = 0, nonEmpty = 0;
@@ -168,6 +191,7 @@ int main()
 {
     argumentChecks();
     grids();
+    blockCounts();
     countedEntries();
     countedBytes();
     if (failures) {
