@@ -70,6 +70,7 @@ def build_hip_library(force=False, extra_flags=()):
             os.path.join(CSRC, 'memb_hip_pairs.hip'), os.path.join(CSRC, 'memb_hip_bag_pairs.hip'),
             os.path.join(CSRC, 'memb_hip_queries.hip'), os.path.join(CSRC, 'memb_hip_query_matrix.hip'),
             os.path.join(CSRC, 'memb_hip_query_topk.hip'), os.path.join(CSRC, 'memb_hip_query_bags.hip'),
+            os.path.join(CSRC, 'memb_hip_analogies.hip'),
         ])
     return HIP_LIBRARY
 

@@ -52,7 +52,7 @@ except ImportError as error:  # fail loudly: nothing here works without the nati
         'Build it with `python build_native.py` (needs hipcc).'.format(error)) from error
 
 from .builder import Builder
-from .reader import POOL_CHUNK, Reader
+from .reader import POOL_CHUNK, QUERY_TOPK_MAX_EXCLUDED, Reader
 from .readers_union import POOLED_HOST_CHUNK, ReadersUnion
 from .sharding import ShardedReader
 
@@ -61,4 +61,4 @@ hip_device_count = _memb.hip_device_count
 
 HIP_LIBRARY_PATH = _os.path.join(_os.path.dirname(_os.path.abspath(__file__)), 'libmemb_hip.so')
 
-__all__ = ['Builder', 'POOLED_HOST_CHUNK', 'POOL_CHUNK', 'Reader', 'ReadersUnion', 'ShardedReader', 'available_compression_strategies', 'hip_device_count']
+__all__ = ['Builder', 'POOLED_HOST_CHUNK', 'POOL_CHUNK', 'QUERY_TOPK_MAX_EXCLUDED', 'Reader', 'ReadersUnion', 'ShardedReader', 'available_compression_strategies', 'hip_device_count']

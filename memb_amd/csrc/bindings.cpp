@@ -15,6 +15,7 @@
 #include "../../include/memb_hip_query_matrix.h"
 #include "hip_query_matrix.h"
 #include "../../include/memb_hip_query_topk.h"
+#include "../../include/memb_hip_analogies.h"
 #include "hip_query_topk.h"
 #include "../../include/memb_hip_query_bags.h"
 #include "hip_query_bags.h"
@@ -1351,6 +1352,50 @@ PYBIND11_MODULE(_memb, m) {
             py::arg("workspace_ptr"),
             py::arg("workspace_bytes"),
             py::arg("stream") = 0)
+        // include/memb_hip_analogies.h: query_topk_to_device with a (n_queries, width) int64 device matrix of excluded
+        // positions, rows ld_excluded entries apart (0 / 0 / 0: none). False likewise: the caller takes the matrix in slices
+        // and calls dense_topk_excluding_to_device with merge.
+        .def(
+            "query_topk_excluding_to_device",
+            [](memb::Reader& reader, uintptr_t queries, size_t nQueries, size_t ldQueries, uintptr_t rows, size_t n, uint32_t k,
+               uintptr_t excluded, size_t width, size_t ldExcluded, uintptr_t values, uintptr_t positions, size_t ldOut,
+               uintptr_t workspace, size_t workspaceBytes, uintptr_t stream)
+            {
+                const int code = memb_hip_query_excluding_topk_device(
+                    reader.deviceContext(), reinterpret_cast<const float*>(queries), nQueries, ldQueries,
+                    reinterpret_cast<const uint32_t*>(rows), n, k, reinterpret_cast<const int64_t*>(excluded), width, ldExcluded,
+                    reinterpret_cast<float*>(values), reinterpret_cast<int64_t*>(positions), ldOut,
+                    reinterpret_cast<void*>(workspace), workspaceBytes, reinterpret_cast<void*>(stream));
+                if (code == MEMB_HIP_UNSUPPORTED) {
+                    return false;
+                }
+                if (code != MEMB_HIP_OK) {
+                    throw std::runtime_error(std::string("memb_hip_query_excluding_topk_device: ") + memb_hip_last_error());
+                }
+                return true;
+            },
+            py::arg("queries_ptr"),
+            py::arg("n_queries"),
+            py::arg("ld_queries"),
+            py::arg("rows_ptr"),
+            py::arg("n"),
+            py::arg("k"),
+            py::arg("excluded_ptr"),
+            py::arg("width"),
+            py::arg("ld_excluded"),
+            py::arg("values_ptr"),
+            py::arg("positions_ptr"),
+            py::arg("ld_out"),
+            py::arg("workspace_ptr"),
+            py::arg("workspace_bytes"),
+            py::arg("stream") = 0)
+        // the kernel families query_topk_excluding_to_device launches, '' where it returns False
+        .def(
+            "query_topk_excluding_kernel_name",
+            [](memb::Reader& reader) {
+                memb_hip_ctx* ctx = reader.deviceContext();
+                return std::string(ctx ? memb_hip_query_excluding_topk_kernel_name(ctx) : "");
+            })
         .def(
             "query_topk_workspace_bytes",
             [](memb::Reader& reader, size_t nQueries, size_t n, uint32_t k, bool minimal) {
@@ -1523,6 +1568,65 @@ PYBIND11_MODULE(_memb, m) {
         py::arg("ld_out"),
         py::arg("workspace_ptr"),
         py::arg("workspace_bytes"),
+        py::arg("stream") = 0);
+    // include/memb_hip_analogies.h: dense_topk_to_device with a (n_rows, width) int64 device matrix of excluded positions
+    // (base + column), rows ld_excluded entries apart; the same workspace.
+    m.def(
+        "dense_topk_excluding_to_device",
+        [](int device, uintptr_t matrix, size_t nRows, size_t n, size_t ld, int64_t base, uint32_t k, bool merge,
+           uintptr_t excluded, size_t width, size_t ldExcluded, uintptr_t values, uintptr_t positions, size_t ldOut,
+           uintptr_t workspace, size_t workspaceBytes, uintptr_t stream)
+        {
+            if (memb_hip_dense_excluding_topk_device(
+                    device, reinterpret_cast<const float*>(matrix), nRows, n, ld, base, k, merge ? 1 : 0,
+                    reinterpret_cast<const int64_t*>(excluded), width, ldExcluded, reinterpret_cast<float*>(values),
+                    reinterpret_cast<int64_t*>(positions), ldOut, reinterpret_cast<void*>(workspace), workspaceBytes,
+                    reinterpret_cast<void*>(stream)) != MEMB_HIP_OK) {
+                throw std::runtime_error(std::string("memb_hip_dense_excluding_topk_device: ") + memb_hip_last_error());
+            }
+        },
+        py::arg("device"),
+        py::arg("matrix_ptr"),
+        py::arg("n_rows"),
+        py::arg("n"),
+        py::arg("ld"),
+        py::arg("base"),
+        py::arg("k"),
+        py::arg("merge"),
+        py::arg("excluded_ptr"),
+        py::arg("width"),
+        py::arg("ld_excluded"),
+        py::arg("values_ptr"),
+        py::arg("positions_ptr"),
+        py::arg("ld_out"),
+        py::arg("workspace_ptr"),
+        py::arg("workspace_bytes"),
+        py::arg("stream") = 0);
+    m.def("dense_topk_excluding_kernel_name", []() { return std::string(memb_hip_query_excluding_topk_kernel_name(nullptr)); });
+    m.attr("QUERY_TOPK_MAX_EXCLUDED") = MEMB_HIP_MAX_EXCLUDED;
+    // include/memb_hip_analogies.h: sums of weighted rows of any fp32 device matrix in entry order; offsets: n_sums + 1
+    // uint32 on the device, weights: one float32 per entry (0: all +1).
+    m.def(
+        "weighted_rows_sum_to_device",
+        [](int device, uintptr_t matrix, size_t ld, uintptr_t weights, uintptr_t offsets, size_t nSums, size_t dim, uintptr_t out,
+           size_t ldOut, uintptr_t stream)
+        {
+            if (memb_hip_weighted_rows_sum_device(
+                    device, reinterpret_cast<const float*>(matrix), ld, reinterpret_cast<const float*>(weights),
+                    reinterpret_cast<const uint32_t*>(offsets), nSums, dim, reinterpret_cast<float*>(out), ldOut,
+                    reinterpret_cast<void*>(stream)) != MEMB_HIP_OK) {
+                throw std::runtime_error(std::string("memb_hip_weighted_rows_sum_device: ") + memb_hip_last_error());
+            }
+        },
+        py::arg("device"),
+        py::arg("matrix_ptr"),
+        py::arg("ld"),
+        py::arg("weights_ptr"),
+        py::arg("offsets_ptr"),
+        py::arg("n_sums"),
+        py::arg("dim"),
+        py::arg("out_ptr"),
+        py::arg("ld_out"),
         py::arg("stream") = 0);
     m.def("dense_topk_workspace_bytes", &memb_hip_dense_topk_workspace_bytes, py::arg("n_rows"), py::arg("n"), py::arg("k"));
     m.def("dense_topk_kernel_name", []() { return std::string(memb_hip_query_topk_kernel_name(nullptr)); });

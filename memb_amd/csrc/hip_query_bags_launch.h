@@ -222,7 +222,7 @@ int query_bags_topk_device_checked(
     DeviceScope deviceScope(ctx->device);
     HIP_TRY(deviceScope.status());
     if (bags == 0) {
-        return launchTopk(nullptr, nQueries, 0, 0, 0, k, false, values, positions, ldOut, nullptr, static_cast<hipStream_t>(stream));
+        return launchTopk(plainTopkSelection(), nullptr, nQueries, 0, 0, 0, k, false, values, positions, ldOut, nullptr, static_cast<hipStream_t>(stream));
     }
     const size_t slice = planTopkSlice(nQueries, bags, k, workspaceBytes);
     float* matrix = reinterpret_cast<float*>(static_cast<char*>(workspace) + queryTopkListBytes(nQueries, k));
@@ -235,7 +235,7 @@ int query_bags_topk_device_checked(
             return code;
         }
         code = launchTopk(
-            matrix, nQueries, count, slice, static_cast<int64_t>(start), k, start != 0, values, positions, ldOut, workspace,
+            plainTopkSelection(), matrix, nQueries, count, slice, static_cast<int64_t>(start), k, start != 0, values, positions, ldOut, workspace,
             static_cast<hipStream_t>(stream));
         if (code != MEMB_HIP_OK) {
             return code;

@@ -153,11 +153,23 @@ inline uint64_t queryTopkBytes(uint64_t withoutMatrix, uint64_t nQueries, uint64
 
 #ifndef MEMB_HIP_QUERIES_PLANNING_ONLY
 
-// topk_select over the n >= 0 columns of nRows >= 1 rows into `lists`, then topk_merge into the outputs. The current
+// The selection stage of launchTopk: topk_select, or a kernel of another unit that takes the same TopkParams first and one
+// parameter of its own behind them (hip_analogies_launch.h: topk_select_excluding and its list).
+struct TopkSelection {
+    memb::KernelHandle kernel;
+    void* second;   // the kernel's second parameter; null: it has none
+};
+
+TopkSelection plainTopkSelection()
+{
+    return TopkSelection{memb_query_topk::selectKernel(), nullptr};
+}
+
+// The selection over the n >= 0 columns of nRows >= 1 rows into `lists`, then topk_merge into the outputs. The current
 // device is the matrix's. Arguments as denseTopkArgumentsRefusal let them through.
 int launchTopk(
-    const float* matrix, size_t nRows, size_t n, size_t ld, int64_t base, uint32_t k, bool merge, float* values,
-    int64_t* positions, size_t ldOut, void* lists, hipStream_t stream)
+    const TopkSelection& selection, const float* matrix, size_t nRows, size_t n, size_t ld, int64_t base, uint32_t k, bool merge,
+    float* values, int64_t* positions, size_t ldOut, void* lists, hipStream_t stream)
 {
     const TopkSegments plan = planTopkSegments(nRows, n);
     memb_query_topk::TopkParams params{};
@@ -175,8 +187,8 @@ int launchTopk(
     params.segments = plan.segments;
     params.segmentLength = plan.segmentLength;
     params.merge = merge ? 1 : 0;
-    void* arguments[1] = {&params};
-    const memb::KernelHandle kernels[2] = {memb_query_topk::selectKernel(), memb_query_topk::mergeKernel()};
+    void* arguments[2] = {&params, selection.second};   // (topk_merge and topk_select take the first alone)
+    const memb::KernelHandle kernels[2] = {selection.kernel, memb_query_topk::mergeKernel()};
     const uint64_t waves[2] = {uint64_t(nRows) * plan.segments, nRows};
     for (int stage = 0; stage < 2; ++stage) {
         if (!waves[stage]) {   // (no column: topk_merge alone)
@@ -193,10 +205,11 @@ int launchTopk(
     return MEMB_HIP_OK;
 }
 
-// memb_hip_dense_topk_device
+// memb_hip_dense_topk_device; with another selection: memb_hip_dense_topk_excluding_device behind its own checks
 int dense_topk_device_checked(
     int device, const float* matrix, size_t nRows, size_t n, size_t ld, int64_t base, uint32_t k, bool merge, float* values,
-    int64_t* positions, size_t ldOut, void* workspace, size_t workspaceBytes, void* stream)
+    int64_t* positions, size_t ldOut, void* workspace, size_t workspaceBytes, void* stream,
+    const TopkSelection& selection = plainTopkSelection())
 {
     if (const char* refusal = denseTopkArgumentsRefusal(device, matrix, nRows, n, ld, base, k, values, positions, ldOut, workspace, workspaceBytes)) {
         return fail(MEMB_HIP_ERR_INVALID, refusal);
@@ -206,13 +219,15 @@ int dense_topk_device_checked(
     }
     DeviceScope deviceScope(device);
     HIP_TRY(deviceScope.status());
-    return launchTopk(matrix, nRows, n, ld, base, k, merge, values, positions, ldOut, workspace, static_cast<hipStream_t>(stream));
+    return launchTopk(selection, matrix, nRows, n, ld, base, k, merge, values, positions, ldOut, workspace, static_cast<hipStream_t>(stream));
 }
 
-// memb_hip_query_topk_device
+// memb_hip_query_topk_device; with another selection: memb_hip_query_topk_excluding_device behind its own checks -- the
+// one loop over the slices
 int query_topk_device_checked(
     memb_hip_ctx* ctx, const float* queries, size_t nQueries, size_t ldQueries, const uint32_t* rows, size_t n, uint32_t k,
-    float* values, int64_t* positions, size_t ldOut, void* workspace, size_t workspaceBytes, void* stream)
+    float* values, int64_t* positions, size_t ldOut, void* workspace, size_t workspaceBytes, void* stream,
+    const TopkSelection& selection = plainTopkSelection())
 {
     if (!ctx) {
         return fail(MEMB_HIP_ERR_INVALID, "null argument: ctx");
@@ -231,7 +246,7 @@ int query_topk_device_checked(
     DeviceScope deviceScope(ctx->device);
     HIP_TRY(deviceScope.status());
     if (n == 0) {
-        return launchTopk(nullptr, nQueries, 0, 0, 0, k, false, values, positions, ldOut, nullptr, static_cast<hipStream_t>(stream));
+        return launchTopk(selection, nullptr, nQueries, 0, 0, 0, k, false, values, positions, ldOut, nullptr, static_cast<hipStream_t>(stream));
     }
     const size_t slice = planTopkSlice(nQueries, n, k, workspaceBytes);
     float* matrix = reinterpret_cast<float*>(static_cast<char*>(workspace) + queryTopkListBytes(nQueries, k));
@@ -242,7 +257,7 @@ int query_topk_device_checked(
             return code;
         }
         code = launchTopk(
-            matrix, nQueries, count, slice, static_cast<int64_t>(start), k, start != 0, values, positions, ldOut, workspace,
+            selection, matrix, nQueries, count, slice, static_cast<int64_t>(start), k, start != 0, values, positions, ldOut, workspace,
             static_cast<hipStream_t>(stream));
         if (code != MEMB_HIP_OK) {
             return code;

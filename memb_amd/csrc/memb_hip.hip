@@ -53,7 +53,9 @@
 // (hip_query_matrix.h), launched by hip_query_matrix_launch.h; memb_hip_query_topk.hip -- the k best columns of every row
 // of a matrix (hip_query_topk.h), launched by hip_query_topk_launch.h, slice after slice of the query matrix;
 // memb_hip_query_bags.hip -- that of every query against every pooled bag of rows (hip_query_bags.h), launched by
-// hip_query_bags_launch.h, as a matrix or slice after slice in front of the same selection.
+// hip_query_bags_launch.h, as a matrix or slice after slice in front of the same selection; memb_hip_analogies.hip -- the
+// selection with a list of excluded positions per row and sums of weighted rows (hip_analogies.h), launched by
+// hip_analogies_launch.h through hip_query_topk_launch.h's launches and slice loop.
 #include <hip/hip_runtime.h>
 
 #include "../../include/memb_hip.h"
@@ -69,6 +71,7 @@
 #include "../../include/memb_hip_query_matrix.h"
 #include "../../include/memb_hip_query_topk.h"
 #include "../../include/memb_hip_query_bags.h"
+#include "../../include/memb_hip_analogies.h"
 #include "codec.h"
 #include "hip_narrow.h"
 #include "hip_pooled.h"
@@ -81,6 +84,7 @@
 #include "hip_query_matrix.h"
 #include "hip_query_topk.h"
 #include "hip_query_bags.h"
+#include "hip_analogies.h"
 #include "wire.h"
 #include "worker_pool.h"
 
@@ -160,6 +164,7 @@ namespace {
 #include "hip_query_matrix_launch.h"
 #include "hip_query_topk_launch.h"
 #include "hip_query_bags_launch.h"
+#include "hip_analogies_launch.h"
 
 // No C++ exception leaves the library: allocation failures and the like become error codes.
 template <typename Call>
@@ -569,6 +574,44 @@ size_t memb_hip_query_bags_topk_workspace_bytes(const memb_hip_ctx* ctx, size_t 
 const char* memb_hip_query_bags_topk_kernel_name(const memb_hip_ctx* ctx)
 {
     return query_bags_topk_kernel_name(ctx);
+}
+
+int memb_hip_dense_excluding_topk_device(
+    int device, const float* matrix, size_t n_rows, size_t n, size_t ld, int64_t base, uint32_t k, int merge,
+    const int64_t* excluded, size_t width, size_t ld_excluded, float* values, int64_t* positions, size_t ld_out, void* workspace,
+    size_t workspace_bytes, void* stream)
+{
+    return guarded([&] {
+        return dense_topk_excluding_device_checked(
+            device, matrix, n_rows, n, ld, base, k, merge != 0, excluded, width, ld_excluded, values, positions, ld_out, workspace,
+            workspace_bytes, stream);
+    });
+}
+
+int memb_hip_query_excluding_topk_device(
+    memb_hip_ctx* ctx, const float* queries, size_t n_queries, size_t ld_queries, const uint32_t* rows, size_t n, uint32_t k,
+    const int64_t* excluded, size_t width, size_t ld_excluded, float* values, int64_t* positions, size_t ld_out, void* workspace,
+    size_t workspace_bytes, void* stream)
+{
+    return guarded([&] {
+        return query_topk_excluding_device_checked(
+            ctx, queries, n_queries, ld_queries, rows, n, k, excluded, width, ld_excluded, values, positions, ld_out, workspace,
+            workspace_bytes, stream);
+    });
+}
+
+const char* memb_hip_query_excluding_topk_kernel_name(const memb_hip_ctx* ctx)
+{
+    return query_topk_excluding_kernel_name(ctx);
+}
+
+int memb_hip_weighted_rows_sum_device(
+    int device, const float* matrix, size_t ld, const float* weights, const uint32_t* offsets, size_t n_sums, size_t dim,
+    float* out, size_t ld_out, void* stream)
+{
+    return guarded([&] {
+        return weighted_rows_sum_device_checked(device, matrix, ld, weights, offsets, n_sums, dim, out, ld_out, stream);
+    });
 }
 
 int memb_hip_decode_batches_device(memb_hip_ctx* ctx, const memb_hip_batch* batches, size_t count, void* stream)

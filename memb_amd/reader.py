@@ -344,9 +344,27 @@ def unit_rows_host(values, norms=None):
         return values / np.where(norms < UNIT_EPS, UNIT_EPS, norms)[:, None]
 
 
+def weighted_rows_sum_host(values, weights, offsets):
+    """The sums of include/memb_hip_analogies.h in numpy: for sum q over the entries offsets[q] .. offsets[q + 1] of the
+    float32 (n, dim) matrix, in that order, from +0.0: out[q] = out[q] + (weights[e] * values[e]), the product and the sum
+    each one float32 operation. weights: float32 (n,), None: all +1. Returns the float32 (Q, dim) sums."""
+    values = np.ascontiguousarray(values, dtype=np.float32)
+    offsets = np.asarray(offsets, dtype=np.int64)
+    weights = np.ones(values.shape[0], dtype=np.float32) if weights is None else np.ascontiguousarray(weights, dtype=np.float32)
+    begins, lengths = offsets[:-1], offsets[1:] - offsets[:-1]
+    out = np.zeros((begins.size, values.shape[1]), dtype=np.float32)
+    with np.errstate(over='ignore', under='ignore', invalid='ignore'):
+        for step in range(int(lengths.max()) if lengths.size else 0):
+            sums = np.nonzero(lengths > step)[0]
+            entries = begins[sums] + step
+            out[sums] = out[sums] + weights[entries, None] * values[entries]
+    return out
+
+
 QUERY_BAGS_DEVICE_SLICE = 1 << 16   # bags bag_similarity_matrix_device pools into a temporary at a time where no fused kernel exists
 QUERY_BAGS_HOST_SLICE = 1 << 12     # bags bag_similarity_matrix of a device='cpu' reader pools at a time
 QUERY_TOPK_MAX_K = _memb.QUERY_TOPK_MAX_K   # one rank per lane of a wavefront (MEMB_HIP_TOPK_MAX_K)
+QUERY_TOPK_MAX_EXCLUDED = _memb.QUERY_TOPK_MAX_EXCLUDED   # excluded positions per query, one per lane (MEMB_HIP_MAX_EXCLUDED)
 
 
 def topk_size(k, spare=0):
@@ -379,15 +397,21 @@ def topk_keys(values):
     return np.where((bits & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000), np.uint32(0xFFFFFFFF), keys).astype(np.uint32)
 
 
-def topk_host(matrix, k, base=0, held=None):
+def topk_host(matrix, k, base=0, held=None, exclude=None):
     """The contract of include/memb_hip_query_topk.h in numpy: (values float32 (Q, k), positions int64 (Q, k)) of the
     float32 (Q, n) matrix, positions as base + column; held: a (values, positions) pair of an earlier call whose entries
-    (position -1: empty) take part, their positions outside [base, base + n)."""
+    (position -1: empty) take part, their positions outside [base, base + n). exclude: include/memb_hip_analogies.h's
+    list, an integer (Q, E) array of positions that are no candidates of their row; an entry outside [base, base + n) is
+    ignored."""
     matrix = np.ascontiguousarray(matrix, dtype=np.float32)
     count, n = matrix.shape
     bits = matrix.view(np.uint32)
     positions = np.broadcast_to(base + np.arange(n, dtype=np.int64), (count, n))
     keys = topk_keys(matrix).astype(np.int64)
+    if exclude is not None:
+        columns = np.asarray(exclude, dtype=np.int64).reshape(count, -1) - base
+        named = (columns >= 0) & (columns < n)
+        keys[np.nonzero(named)[0], columns[named]] = 0   # (an empty entry: behind every real one, stored as empty)
     if held is not None:
         bits = np.concatenate([held[0].view(np.uint32), bits], axis=1)
         keys = np.concatenate([np.where(held[1] < 0, 0, topk_keys(held[0]).astype(np.int64)), keys], axis=1)
@@ -1473,7 +1497,24 @@ class Reader(BaseReader):
             self._all_rows = torch.arange(len(self), dtype=torch.int32, device='cuda:{}'.format(index))
         return self._all_rows
 
-    def similarity_topk_device(self, queries, rows, k, *, workspace=None):
+    def _topk_exclude(self, torch, exclude, count, device):
+        """the checks of similarity_topk_device on its exclusion list: (pointer, E, row stride in entries)"""
+        if not isinstance(exclude, torch.Tensor) or exclude.dtype != torch.int64:
+            raise TypeError('exclude must be an int64 tensor of shape (Q, E)')
+        if exclude.device.type != 'cuda':
+            raise TypeError('exclude must be on the GPU')
+        if exclude.dim() != 2 or exclude.shape[0] != count:
+            raise ValueError('exclude must have shape (Q, E) = ({}, E), got {}'.format(count, tuple(exclude.shape)))
+        width = exclude.shape[1]
+        if width > QUERY_TOPK_MAX_EXCLUDED:
+            raise ValueError('exclude names at most {} positions per query, got {}'.format(QUERY_TOPK_MAX_EXCLUDED, width))
+        if (width > 1 and exclude.stride(1) != 1) or (count > 1 and exclude.stride(0) < width):
+            raise ValueError('exclude must have a contiguous last dimension and a row stride of at least E')
+        if exclude.device != device:
+            raise ValueError('exclude must be on {} (the device this reader is staged on), got {}'.format(device, exclude.device))
+        return exclude.data_ptr() if width and count else 0, width, exclude.stride(0) if count > 1 else width
+
+    def similarity_topk_device(self, queries, rows, k, *, workspace=None, exclude=None):
         '''The k most similar candidates of EVERY query, left on the GPU, WITHOUT the (Q, n) matrix of
         similarity_matrix_device in device memory: (values, positions), a float32 (Q, k) and an int64 (Q, k) tensor.
         Row q of similarity_matrix_device(queries, rows) ordered by a stable descending sort -- a greater cosine first, NaN
@@ -1493,7 +1534,14 @@ class Reader(BaseReader):
         workspace : optional contiguous uint8 tensor on the same device, aligned to 8 bytes, of at least
             self._impl.query_topk_workspace_bytes(Q, n, k, minimal=True) bytes, for the fused path: a call with it allocates
             nothing but its two results. Its size decides the slicing, never the result.
-        One model, float32: no k > 64, no bfloat16 / float16, no ReadersUnion, no ShardedReader, no exclusion list.'''
+        exclude : optional int64 (Q, E) tensor on the same device, E <= 64 (QUERY_TOPK_MAX_EXCLUDED), with a contiguous last
+            dimension and a row stride of at least E: positions (indices into `rows`) that are NO candidates of their query
+            (include/memb_hip_analogies.h). Row q of the matrix without those columns is sorted and cut to k; the positions
+            returned are still the original ones, and only n minus the distinct excluded positions can be filled. Entries
+            may repeat and come in any order; a negative one or one beyond n is ignored (-1 pads a row). None: the call as
+            it always was, the same kernels. With a list the selection kernel is topk_select_excluding
+            (last_query_topk_kernel names it).
+        One model, float32: no k > 64, no bfloat16 / float16, no ReadersUnion, no ShardedReader, no more than 64 exclusions.'''
         import torch
         index = self._impl.device()
         if index == _memb.HOST_DEVICE:
@@ -1512,7 +1560,8 @@ class Reader(BaseReader):
         values = torch.empty((count, k), dtype=torch.float32, device=device)
         positions = torch.empty((count, k), dtype=torch.int64, device=device)
         stream = _current_stream(torch, index)
-        fused = self._impl.query_topk_kernel_name()
+        excluded = None if exclude is None else self._topk_exclude(torch, exclude, count, device)
+        fused = self._impl.query_topk_kernel_name() if excluded is None else self._impl.query_topk_excluding_kernel_name()
         self._last_query_topk_kernel = fused if count else ''
         if count == 0:   # (nothing is launched)
             return values, positions
@@ -1524,9 +1573,14 @@ class Reader(BaseReader):
             elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1
                     or not workspace.is_contiguous() or workspace.device != device):
                 raise TypeError('workspace must be a contiguous uint8 tensor on cuda:{}'.format(index))
-            done = self._impl.query_topk_to_device(
-                queries.data_ptr(), count, ld, rows.data_ptr(), n, k, values.data_ptr(), positions.data_ptr(), k,
-                workspace.data_ptr() if workspace.numel() else 0, workspace.numel(), stream)
+            if excluded is None:
+                done = self._impl.query_topk_to_device(
+                    queries.data_ptr(), count, ld, rows.data_ptr(), n, k, values.data_ptr(), positions.data_ptr(), k,
+                    workspace.data_ptr() if workspace.numel() else 0, workspace.numel(), stream)
+            else:
+                done = self._impl.query_topk_excluding_to_device(
+                    queries.data_ptr(), count, ld, rows.data_ptr(), n, k, *excluded, values.data_ptr(), positions.data_ptr(), k,
+                    workspace.data_ptr() if workspace.numel() else 0, workspace.numel(), stream)
             assert done   # (n == 0 is answered for every model)
             return values, positions
         width = min(n, QUERY_DEVICE_SLICE)
@@ -1535,10 +1589,16 @@ class Reader(BaseReader):
         for start in range(0, n, QUERY_DEVICE_SLICE):
             size = min(n, start + QUERY_DEVICE_SLICE) - start
             self.similarity_matrix_device(queries, rows[start:start + size], out=temporary[:, :size])
-            _memb.dense_topk_to_device(
-                index, temporary.data_ptr(), count, size, width, start, k, start > 0, values.data_ptr(), positions.data_ptr(), k,
-                lists.data_ptr(), lists.numel(), stream)
-        self._last_query_topk_kernel = self._last_query_matrix_kernel + '+' + _memb.dense_topk_kernel_name()
+            if excluded is None:
+                _memb.dense_topk_to_device(
+                    index, temporary.data_ptr(), count, size, width, start, k, start > 0, values.data_ptr(), positions.data_ptr(), k,
+                    lists.data_ptr(), lists.numel(), stream)
+            else:
+                _memb.dense_topk_excluding_to_device(
+                    index, temporary.data_ptr(), count, size, width, start, k, start > 0, *excluded, values.data_ptr(),
+                    positions.data_ptr(), k, lists.data_ptr(), lists.numel(), stream)
+        self._last_query_topk_kernel = self._last_query_matrix_kernel + '+' + (
+            _memb.dense_topk_kernel_name() if excluded is None else _memb.dense_topk_excluding_kernel_name())
         return values, positions
 
     def most_similar_device(self, words, k=10, *, exclude_self=True):
@@ -1588,11 +1648,12 @@ class Reader(BaseReader):
         vocabulary = self.keys()
         return [[(vocabulary[row], float(value)) for value, row in zip(values[i], positions[i]) if row >= 0] for i in range(len(words))]
 
-    def similarity_topk(self, queries, rows, k):
+    def similarity_topk(self, queries, rows, k, exclude=None):
         '''similarity_topk_device for host arrays: a numpy float32 (Q, dim) or (dim,) array of queries and numpy row ids
         (None: every row of the model) in, (values float32 (Q, k), positions int64 (Q, k)) out. A reader on a GPU sends
         everything up and brings the result back; a device='cpu' reader takes similarity_matrix chunk by chunk and selects
-        by the same order in numpy (topk_host): the same bits.'''
+        by the same order in numpy (topk_host): the same bits. exclude: similarity_topk_device's list as an integer (Q, E)
+        array, E <= 64.'''
         queries = np.asarray(queries)
         if queries.dtype != np.float32:
             raise TypeError('queries must be a float32 array of shape (Q, dim) or (dim,)')
@@ -1603,18 +1664,167 @@ class Reader(BaseReader):
         k = topk_size(k)
         queries = np.ascontiguousarray(queries)
         rows = np.arange(len(self), dtype=np.uint32) if rows is None else np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        if exclude is not None:
+            exclude = np.asarray(exclude)
+            if exclude.dtype.kind not in 'iu':
+                raise TypeError('exclude must be an integer array of shape (Q, E)')
+            if exclude.ndim != 2 or exclude.shape[0] != queries.shape[0]:
+                raise ValueError('exclude must have shape (Q, E) = ({}, E), got {}'.format(queries.shape[0], exclude.shape))
+            if exclude.shape[1] > QUERY_TOPK_MAX_EXCLUDED:
+                raise ValueError('exclude names at most {} positions per query, got {}'.format(QUERY_TOPK_MAX_EXCLUDED, exclude.shape[1]))
+            exclude = np.ascontiguousarray(exclude, dtype=np.int64)
         if self._impl.device() != _memb.HOST_DEVICE:
             import torch
             device = 'cuda:{}'.format(self._impl.device())
             values, positions = self.similarity_topk_device(
-                torch.from_numpy(queries).to(device), torch.from_numpy(rows.view(np.int32)).to(device), k)
+                torch.from_numpy(queries).to(device), torch.from_numpy(rows.view(np.int32)).to(device), k,
+                exclude=None if exclude is None else torch.from_numpy(exclude).to(device))
             return values.cpu().numpy(), positions.cpu().numpy()
         values = np.full((queries.shape[0], k), -np.inf, dtype=np.float32)
         positions = np.full((queries.shape[0], k), -1, dtype=np.int64)
         for start in range(0, rows.size, NORMS_HOST_CHUNK):
             matrix = self.similarity_matrix(queries, rows[start:start + NORMS_HOST_CHUNK])
-            values, positions = topk_host(matrix, k, start, (values, positions))
+            values, positions = topk_host(matrix, k, start, (values, positions), exclude)
         return values, positions
+
+    # ---- analogies: signed word queries and the top-k without their own words (include/memb_hip_analogies.h) ----
+
+    def compose_queries_device(self, rows, offsets, weights=None):
+        '''Query vectors built from several rows each, left on the GPU: a float32 (Q, dim) tensor. Query q is the sum over
+        the entries offsets[q] .. offsets[q + 1] of weights[e] * unit row of rows[e], added in entry order from +0.0, the
+        product and the sum each one float32 operation (include/memb_hip_analogies.h) -- so the bits are the same on every
+        path, which a segmented sum in torch (index_add_) does not promise. The unit rows are
+        unit_rows_embedding_device(rows) in a temporary of (entries, dim) floats, summed by one more kernel
+        (weighted_rows_sum): not fused with the decode. A row that is not in the model is a zero row; a query without
+        entries is +0.0.
+        rows : as in rows_embedding_device, the entries of all queries
+        offsets : contiguous int32 / uint32 tensor of Q + 1 ascending entries on the same device; an offset beyond
+            len(rows) is clamped to it
+        weights : optional contiguous float32 tensor of len(rows) entries on the same device; None: all +1'''
+        import torch
+        index, device = self._norms_arguments(torch, rows)
+        count = self._bag_arguments(torch, rows, offsets, index, device)
+        rows = rows.reshape(-1)
+        n = rows.numel()
+        if weights is not None:
+            if (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or weights.device != device
+                    or not weights.is_contiguous() or weights.numel() != n):
+                raise TypeError('weights must be a contiguous float32 tensor of len(rows) entries on {}'.format(device))
+        dim = self.dim
+        unit = self.unit_rows_embedding_device(rows) if n else None
+        # (the kernel trusts its offsets: none may point past the unit rows)
+        offsets = torch.clamp(offsets.view(torch.int32).to(torch.int64) & 0xFFFFFFFF, max=n).to(torch.int32)
+        out = torch.empty((count, dim), dtype=torch.float32, device=device)
+        _memb.weighted_rows_sum_to_device(
+            index, unit.data_ptr() if n else 0, dim, weights.data_ptr() if n and weights is not None else 0, offsets.data_ptr(),
+            count, dim, out.data_ptr(), dim, _current_stream(torch, index))
+        return out
+
+    def compose_queries(self, rows, offsets, weights=None):
+        '''compose_queries_device for host arrays: numpy row ids, offsets (Q + 1 ascending integers within 0 .. len(rows))
+        and optional float32 weights in, a numpy float32 (Q, dim) matrix out. A reader on a GPU sends everything up and
+        brings the queries back; a device='cpu' reader adds its unit_rows_embedding in numpy in the same order
+        (weighted_rows_sum_host): the same bits.'''
+        rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        offsets = bag_offsets(offsets, rows.size)
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+            if weights.size != rows.size:
+                raise ValueError('weights needs one entry per row, got {} for {}'.format(weights.size, rows.size))
+        if self._impl.device() != _memb.HOST_DEVICE:
+            import torch
+            device = 'cuda:{}'.format(self._impl.device())
+            return self.compose_queries_device(
+                torch.from_numpy(rows.view(np.int32)).to(device), torch.from_numpy(offsets.astype(np.int32)).to(device),
+                None if weights is None else torch.from_numpy(weights).to(device)).cpu().numpy()
+        return weighted_rows_sum_host(self.unit_rows_embedding(rows), weights, offsets)
+
+    @staticmethod
+    def _analogy_entries(positive, negative):
+        """The entries of analogies: (words, weights float32, offsets int64 (Q + 1), members int64 (Q, E)) -- per query its
+        positive entries, then its negative ones, each in the order given, a bare word weighing +1 among the positive and
+        -1 among the negative; members[q]: the indices of query q's entries in `words`, -1 behind them."""
+        positive = [list(entries) for entries in positive]
+        negative = [[] for _ in positive] if negative is None else [list(entries) for entries in negative]
+        if len(negative) != len(positive):
+            raise ValueError('positive and negative must hold one list per query, got {} and {}'.format(len(positive), len(negative)))
+        words, weights, offsets = [], [], [0]
+        for plus, minus in zip(positive, negative):
+            for entries, default in ((plus, 1.0), (minus, -1.0)):
+                for entry in entries:
+                    word, weight = (entry, default) if isinstance(entry, (str, bytes)) else entry
+                    words.append(word)
+                    weights.append(weight)
+            if len(words) - offsets[-1] > QUERY_TOPK_MAX_EXCLUDED:
+                raise ValueError('a query takes at most {} words (each is excluded from its answer), got {}'.format(
+                    QUERY_TOPK_MAX_EXCLUDED, len(words) - offsets[-1]))
+            offsets.append(len(words))
+        offsets = np.array(offsets, dtype=np.int64)
+        lengths = offsets[1:] - offsets[:-1]
+        width = int(lengths.max()) if lengths.size else 0
+        steps = np.arange(width, dtype=np.int64)[None, :]
+        members = np.where(steps < lengths[:, None], offsets[:-1, None] + steps, -1)
+        return words, np.array(weights, dtype=np.float32), offsets, members
+
+    def analogies_device(self, positive, negative=None, k=10):
+        '''The k nearest words of signed word queries over the WHOLE vocabulary, left on the GPU -- king - man + woman is
+        positive=[['king', 'woman']], negative=[['man']], gensim's most_similar(positive=, negative=): (values, rows), a
+        float32 (Q, k) tensor of cosines and an int64 (Q, k) tensor of row ids (positions in keys()), best first in
+        similarity_topk_device's order.
+        positive, negative : one list per query of words or (word, weight) pairs; a bare word weighs +1 in positive and -1
+            in negative. negative=None: no negative words. At most 64 words per query (ValueError beyond).
+        The query is compose_queries_device over a query's positive entries, then its negative ones, each in the order
+        given: the sum of weighted UNIT rows, which is gensim's query up to a scale the cosine does not see. The candidates
+        are every row of the model, and the rows of ALL of a query's words are excluded (similarity_topk_device's exclude),
+        so no input word appears in its answer and none costs a rank: k goes up to 64. A query with a word the model lacks,
+        or without any word, gives a row of empty slots: row id -1, value -inf. Cosine addition only: no 3CosMul.'''
+        import torch
+        index = self._impl.device()
+        if index == _memb.HOST_DEVICE:
+            raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
+        k = topk_size(k)
+        device = 'cuda:{}'.format(index)
+        words, weights, offsets, members = self._analogy_entries(positive, negative)
+        count = offsets.size - 1
+        if count == 0:
+            return torch.empty((0, k), dtype=torch.float32, device=device), torch.empty((0, k), dtype=torch.int64, device=device)
+        own = self.resolve_rows_device(words)
+        queries = self.compose_queries_device(
+            own, torch.from_numpy(offsets.astype(np.int32)).to(device), torch.from_numpy(weights).to(device))
+        members = torch.from_numpy(members).to(device)
+        padded = torch.cat([own.to(torch.int64), torch.full((1,), -1, dtype=torch.int64, device=device)])   # (a missing word is -1)
+        exclude = padded[members]   # (members == -1 reads the -1 at the end)
+        values, positions = self.similarity_topk_device(queries, None, k, exclude=exclude)
+        unanswered = ((members >= 0) & (exclude < 0)).any(dim=1) | torch.from_numpy(offsets[1:] == offsets[:-1]).to(device)
+        unanswered = unanswered.unsqueeze(1)
+        return (torch.where(unanswered, torch.full_like(values, float('-inf')), values),
+                torch.where(unanswered, torch.full_like(positions, -1), positions))
+
+    def analogies(self, positive, negative=None, k=10):
+        '''analogies_device on the host: one list of (word, cosine) pairs per query, best first, none of the query's own
+        words among them; [] for a query with a word the model lacks or without any word. analogies_device on a GPU reader;
+        compose_queries and similarity_topk with the same exclusion on a device='cpu' reader: the same pairs.'''
+        k = topk_size(k)
+        if self._impl.device() != _memb.HOST_DEVICE:
+            values, positions = (part.cpu().numpy() for part in self.analogies_device(positive, negative, k))
+        else:
+            words, weights, offsets, members = self._analogy_entries(positive, negative)
+            if offsets.size == 1:
+                return []
+            own = self.resolve_rows(words)
+            rows = np.concatenate([np.where(own == 0xFFFFFFFF, -1, own.astype(np.int64)), [-1]])
+            exclude = rows[members]
+            values, positions = self.similarity_topk(self.compose_queries(own, offsets, weights), None, k, exclude=exclude)
+            unanswered = ((members >= 0) & (exclude < 0)).any(axis=1) | (offsets[1:] == offsets[:-1])
+            positions = np.where(unanswered[:, None], -1, positions)
+        vocabulary = self.keys()
+        return [[(vocabulary[row], float(value)) for value, row in zip(values[i], positions[i]) if row >= 0]
+                for i in range(values.shape[0])]
+
+    def analogy(self, a, b, c, k=1):
+        '''a is to b as c is to ...: the k nearest words of b - a + c as (word, cosine) pairs, a, b and c left out;
+        analogies([[b, c]], [[a]], k)[0].'''
+        return self.analogies([[b, c]], [[a]], k)[0]
 
     # ---- every query against every pooled bag of rows, matrix and top-k (include/memb_hip_query_bags.h) ----
 

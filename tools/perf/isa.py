@@ -2,7 +2,7 @@
 registers, scratch and LDS, read from the device assembly (no GPU needed).
 
     python tools/perf/isa.py [substring of the demangled kernel name] [-- extra hipcc flags]
-    python tools/perf/isa.py --digests     one line per kernel of every translation unit of libmemb_hip.so (WITH_QUERY_BAGS),
+    python tools/perf/isa.py --digests     one line per kernel of every translation unit of libmemb_hip.so (WITH_ANALOGIES),
                                            instruction digest and resources: run it on two commits and diff the listings
                                            to see which kernels a change touched
 
@@ -47,9 +47,14 @@ WHOLE_LIBRARY = EVERY_SOURCE + (QUERY_MATRIX_SOURCE,)
 QUERY_TOPK_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_query_topk.hip')
 WITH_QUERY_TOPK = WHOLE_LIBRARY + (QUERY_TOPK_SOURCE,)
 # the query-bags kernel's unit, kept out of WITH_QUERY_TOPK likewise (tests/test_query_topk_isa.py pins it); WITH_QUERY_BAGS
-# is every translation unit of the library today, and what --digests lists
+# is every translation unit of the library before the analogies unit
 QUERY_BAGS_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_query_bags.hip')
 WITH_QUERY_BAGS = WITH_QUERY_TOPK + (QUERY_BAGS_SOURCE,)
+# the unit of the selection with exclusion lists and of the weighted sums, kept out of WITH_QUERY_BAGS likewise
+# (tests/test_query_bags_isa.py pins it); WITH_ANALOGIES is every translation unit of the library today, and what --digests
+# lists
+ANALOGIES_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_analogies.hip')
+WITH_ANALOGIES = WITH_QUERY_BAGS + (ANALOGIES_SOURCE,)
 # the flags of build_native.build_hip_library
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt',
          '-Wno-unused-value', '-Wno-align-mismatch', '-Wno-pass-failed', '-Wno-unused-command-line-argument']
@@ -83,7 +88,7 @@ def _instructions(code, symbol):
 def kernel_table(extra_flags=(), source=SOURCE):
     """{demangled kernel name: facts} for every kernel of one translation unit of libmemb_hip.so (default memb_hip.hip;
     NARROW_SOURCE: the bf16 / fp16 decode kernels; POOLED_SOURCE: every sequential pooled kernel; POOLED_CHUNKED_SOURCE: the
-    chunked order's; POOLED_UNION_SOURCE: the pooled kernels of averaged unions and of dense rows; NORMS_SOURCE: row norms and unit rows; PAIRS_SOURCE: the cosine of row pairs; BAG_PAIRS_SOURCE: the cosine of pairs of pooled bags; QUERIES_SOURCE: the cosine of query vectors against groups of rows; QUERY_MATRIX_SOURCE: the cosine of every query against one shared list of rows; QUERY_TOPK_SOURCE: the k best columns of every row of a matrix; QUERY_BAGS_SOURCE: the cosine of every query against every pooled bag of rows; or any other path, such as a unit of another checkout)"""
+    chunked order's; POOLED_UNION_SOURCE: the pooled kernels of averaged unions and of dense rows; NORMS_SOURCE: row norms and unit rows; PAIRS_SOURCE: the cosine of row pairs; BAG_PAIRS_SOURCE: the cosine of pairs of pooled bags; QUERIES_SOURCE: the cosine of query vectors against groups of rows; QUERY_MATRIX_SOURCE: the cosine of every query against one shared list of rows; QUERY_TOPK_SOURCE: the k best columns of every row of a matrix; QUERY_BAGS_SOURCE: the cosine of every query against every pooled bag of rows; ANALOGIES_SOURCE: the selection with exclusion lists and sums of weighted rows; or any other path, such as a unit of another checkout)"""
     text = device_assembly(extra_flags, source)
     names = re.findall(r'^\s*\.amdhsa_kernel (\S+)$', text, flags=re.M)
     demangled = subprocess.run([_tool('c++filt')], input='\n'.join(names), stdout=subprocess.PIPE, text=True,
@@ -158,7 +163,7 @@ if __name__ == '__main__':
         extra = arguments[arguments.index('--') + 1:]
         arguments = arguments[:arguments.index('--')]
     if arguments[:1] == ['--digests']:   # one line per kernel, to diff against another commit's; [units of that commit]
-        for pretty, facts in sorted(kernel_digests(arguments[1:] or WITH_QUERY_BAGS).items()):
+        for pretty, facts in sorted(kernel_digests(arguments[1:] or WITH_ANALOGIES).items()):
             print(pretty.replace('(anonymous namespace)::', '').split('(')[0], *facts)
         sys.exit(0)
     needle = arguments[0] if arguments else ''
