@@ -77,11 +77,11 @@ def build_hip_library(force=False, extra_flags=()):
 
 def build_extension(force=False):
     import pybind11
-    names = ('bindings.cpp', 'reader.cpp', 'builder.cpp', 'compression_strategy.cpp')
+    names = ('bindings.cpp', 'bindings_words.cpp', 'bindings_decode.cpp', 'bindings_pooled.cpp', 'bindings_pairs.cpp',
+             'bindings_queries.cpp', 'reader.cpp', 'builder.cpp', 'compression_strategy.cpp')
     sources = [os.path.join(CSRC, name) for name in names]
-    headers = [os.path.join(CSRC, name) for name in
-               ('reader.h', 'builder.h', 'compression_strategy.h', 'worker_pool.h', 'codec.h', 'wire.h')]
-    headers += glob.glob(os.path.join(INCLUDE, '*.h'))
+    # every header beside the sources and every ABI header: the bindings export constants of hip_query_*.h too
+    headers = glob.glob(os.path.join(CSRC, '*.h')) + glob.glob(os.path.join(INCLUDE, '*.h'))
     build_hip_library(force)
     if force or _newer(EXTENSION, sources + headers + [HIP_LIBRARY]):
         _run([
