@@ -46,13 +46,14 @@ HIP_RUNTIME_PRELOADED = _preload_hip_runtime()
 
 try:
     from . import _memb
+    from . import _memb_cosmul   # noqa: F401  (the 3CosMul entries, a module of its own beside _memb)
 except ImportError as error:  # fail loudly: nothing here works without the native code
     raise ImportError(
-        'memb_amd: the native extension (_memb / libmemb_hip.so) is missing or does not load ({}). '
+        'memb_amd: the native extension (_memb / _memb_cosmul / libmemb_hip.so) is missing or does not load ({}). '
         'Build it with `python build_native.py` (needs hipcc).'.format(error)) from error
 
 from .builder import Builder
-from .reader import POOL_CHUNK, QUERY_TOPK_MAX_EXCLUDED, Reader
+from .reader import COSMUL_MAX_TERMS, POOL_CHUNK, QUERY_TOPK_MAX_EXCLUDED, Reader
 from .readers_union import POOLED_HOST_CHUNK, ReadersUnion
 from .sharding import ShardedReader
 
@@ -61,4 +62,4 @@ hip_device_count = _memb.hip_device_count
 
 HIP_LIBRARY_PATH = _os.path.join(_os.path.dirname(_os.path.abspath(__file__)), 'libmemb_hip.so')
 
-__all__ = ['Builder', 'POOLED_HOST_CHUNK', 'POOL_CHUNK', 'QUERY_TOPK_MAX_EXCLUDED', 'Reader', 'ReadersUnion', 'ShardedReader', 'available_compression_strategies', 'hip_device_count']
+__all__ = ['Builder', 'COSMUL_MAX_TERMS', 'POOLED_HOST_CHUNK', 'POOL_CHUNK', 'QUERY_TOPK_MAX_EXCLUDED', 'Reader', 'ReadersUnion', 'ShardedReader', 'available_compression_strategies', 'hip_device_count']

@@ -55,7 +55,9 @@
 // memb_hip_query_bags.hip -- that of every query against every pooled bag of rows (hip_query_bags.h), launched by
 // hip_query_bags_launch.h, as a matrix or slice after slice in front of the same selection; memb_hip_analogies.hip -- the
 // selection with a list of excluded positions per row and sums of weighted rows (hip_analogies.h), launched by
-// hip_analogies_launch.h through hip_query_topk_launch.h's launches and slice loop.
+// hip_analogies_launch.h through hip_query_topk_launch.h's launches and slice loop; memb_hip_cosmul.hip -- the 3CosMul
+// score of every (question, candidate) from the cosines of the question's terms (hip_cosmul.h), launched by
+// hip_cosmul_launch.h alone or between the query matrix and that selection, slice after slice.
 #include <hip/hip_runtime.h>
 
 #include "../../include/memb_hip.h"
@@ -72,6 +74,7 @@
 #include "../../include/memb_hip_query_topk.h"
 #include "../../include/memb_hip_query_bags.h"
 #include "../../include/memb_hip_analogies.h"
+#include "../../include/memb_hip_cosmul.h"
 #include "codec.h"
 #include "hip_narrow.h"
 #include "hip_pooled.h"
@@ -85,6 +88,7 @@
 #include "hip_query_topk.h"
 #include "hip_query_bags.h"
 #include "hip_analogies.h"
+#include "hip_cosmul.h"
 #include "wire.h"
 #include "worker_pool.h"
 
@@ -165,6 +169,7 @@ namespace {
 #include "hip_query_topk_launch.h"
 #include "hip_query_bags_launch.h"
 #include "hip_analogies_launch.h"
+#include "hip_cosmul_launch.h"
 
 // No C++ exception leaves the library: allocation failures and the like become error codes.
 template <typename Call>
@@ -612,6 +617,38 @@ int memb_hip_weighted_rows_sum_device(
     return guarded([&] {
         return weighted_rows_sum_device_checked(device, matrix, ld, weights, offsets, n_sums, dim, out, ld_out, stream);
     });
+}
+
+int memb_hip_cosmul_scores_device(
+    int device, const float* cosines, size_t ld, const uint32_t* offsets, const uint32_t* negatives_from, size_t n_questions,
+    size_t n, float* scores, size_t ld_scores, void* stream)
+{
+    return guarded([&] {
+        return cosmul_scores_device_checked(device, cosines, ld, offsets, negatives_from, n_questions, n, scores, ld_scores, stream);
+    });
+}
+
+int memb_hip_query_cosmul_nearest_device(
+    memb_hip_ctx* ctx, const float* terms, size_t n_terms, size_t ld_terms, const uint32_t* offsets, const uint32_t* negatives_from,
+    size_t n_questions, const uint32_t* rows, size_t n, uint32_t k, const int64_t* excluded, size_t width, size_t ld_excluded,
+    float* values, int64_t* positions, size_t ld_out, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return guarded([&] {
+        return query_cosmul_nearest_device_checked(
+            ctx, terms, n_terms, ld_terms, offsets, negatives_from, n_questions, rows, n, k, excluded, width, ld_excluded, values,
+            positions, ld_out, workspace, workspace_bytes, stream);
+    });
+}
+
+size_t memb_hip_query_cosmul_workspace_bytes(
+    const memb_hip_ctx* ctx, size_t n_terms, size_t n_questions, size_t n, uint32_t k, int minimal)
+{
+    return query_cosmul_workspace_bytes(ctx, n_terms, n_questions, n, k, minimal != 0);
+}
+
+const char* memb_hip_query_cosmul_kernel_name(const memb_hip_ctx* ctx)
+{
+    return query_cosmul_kernel_name(ctx);
 }
 
 int memb_hip_decode_batches_device(memb_hip_ctx* ctx, const memb_hip_batch* batches, size_t count, void* stream)

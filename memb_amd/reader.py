@@ -10,6 +10,7 @@ from abc import ABC, abstractmethod
 import numpy as np
 
 from . import _memb
+from . import _memb_cosmul
 
 
 class BaseReader(ABC):
@@ -361,8 +362,51 @@ def weighted_rows_sum_host(values, weights, offsets):
     return out
 
 
+def cosmul_questions(offsets, negatives_from, n_terms):
+    """The questions of include/memb_hip_cosmul.h checked on the host: (offsets int64 (Q + 1), negatives_from int64 (Q)).
+    ValueError unless the offsets ascend within 0 .. n_terms, offsets[q] <= negatives_from[q] <= offsets[q + 1] and no
+    question has more than COSMUL_MAX_TERMS terms."""
+    offsets = np.asarray(offsets)
+    negatives_from = np.asarray(negatives_from)
+    if (offsets.size and offsets.dtype.kind not in 'iu') or (negatives_from.size and negatives_from.dtype.kind not in 'iu'):
+        raise TypeError('offsets and negatives_from must be integer arrays')
+    offsets = offsets.astype(np.int64).reshape(-1)
+    negatives_from = negatives_from.astype(np.int64).reshape(-1)
+    if offsets.size != negatives_from.size + 1:
+        raise ValueError('offsets needs Q + 1 entries and negatives_from Q, got {} and {}'.format(offsets.size, negatives_from.size))
+    if offsets[0] < 0 or offsets[-1] > n_terms or (offsets[1:] < offsets[:-1]).any():
+        raise ValueError('offsets must ascend within 0 .. {} (the number of terms)'.format(n_terms))
+    if (negatives_from < offsets[:-1]).any() or (negatives_from > offsets[1:]).any():
+        raise ValueError('negatives_from[q] must lie within offsets[q] .. offsets[q + 1]')
+    if negatives_from.size and int((offsets[1:] - offsets[:-1]).max()) > COSMUL_MAX_TERMS:
+        raise ValueError('a question takes at most {} terms, got {}'.format(COSMUL_MAX_TERMS, int((offsets[1:] - offsets[:-1]).max())))
+    return offsets, negatives_from
+
+
+def cosmul_scores_host(cosines, offsets, negatives_from):
+    """The 3CosMul scores of include/memb_hip_cosmul.h in numpy: for question q over the rows offsets[q] .. offsets[q + 1] of
+    the float32 (T, n) matrix of cosines, the rows before negatives_from[q] positive and the others negative, each group in
+    order: num = num * ((1 + c) * 0.5) from 1, den likewise, score = num / (den + 1e-6), every operation one float32
+    operation. Returns the float32 (Q, n) scores."""
+    cosines = np.ascontiguousarray(cosines, dtype=np.float32)
+    offsets, negatives_from = cosmul_questions(offsets, negatives_from, cosines.shape[0])
+    one, half, eps = np.float32(1), np.float32(0.5), np.float32(0.000001)
+    num = np.ones((negatives_from.size, cosines.shape[1]), dtype=np.float32)
+    den = np.ones_like(num)
+    with np.errstate(over='ignore', under='ignore', invalid='ignore', divide='ignore'):
+        for q in range(negatives_from.size):
+            for term in range(int(offsets[q]), int(offsets[q + 1])):
+                shifted = (one + cosines[term]) * half
+                if term < negatives_from[q]:
+                    num[q] = num[q] * shifted
+                else:
+                    den[q] = den[q] * shifted
+        return num / (den + eps)
+
+
 QUERY_BAGS_DEVICE_SLICE = 1 << 16   # bags bag_similarity_matrix_device pools into a temporary at a time where no fused kernel exists
 QUERY_BAGS_HOST_SLICE = 1 << 12     # bags bag_similarity_matrix of a device='cpu' reader pools at a time
+COSMUL_MAX_TERMS = _memb_cosmul.COSMUL_MAX_TERMS   # terms per 3CosMul question (MEMB_HIP_COSMUL_MAX_TERMS)
 QUERY_TOPK_MAX_K = _memb.QUERY_TOPK_MAX_K   # one rank per lane of a wavefront (MEMB_HIP_TOPK_MAX_K)
 QUERY_TOPK_MAX_EXCLUDED = _memb.QUERY_TOPK_MAX_EXCLUDED   # excluded positions per query, one per lane (MEMB_HIP_MAX_EXCLUDED)
 
@@ -485,6 +529,7 @@ class Reader(BaseReader):
         self._last_query_kernel = ''
         self._last_query_matrix_kernel = ''
         self._last_query_topk_kernel = ''
+        self._last_cosmul_kernel = ''
         self._last_query_bags_kernel = ''
         self._last_query_bags_topk_kernel = ''
         self._all_rows = None              # every row id in order on the device, of similarity_topk_device(rows=None)
@@ -1777,7 +1822,8 @@ class Reader(BaseReader):
         given: the sum of weighted UNIT rows, which is gensim's query up to a scale the cosine does not see. The candidates
         are every row of the model, and the rows of ALL of a query's words are excluded (similarity_topk_device's exclude),
         so no input word appears in its answer and none costs a rank: k goes up to 64. A query with a word the model lacks,
-        or without any word, gives a row of empty slots: row id -1, value -inf. Cosine addition only: no 3CosMul.'''
+        or without any word, gives a row of empty slots: row id -1, value -inf. Cosine addition only: 3CosMul is
+        analogies_cosmul_device.'''
         import torch
         index = self._impl.device()
         if index == _memb.HOST_DEVICE:
@@ -1825,6 +1871,232 @@ class Reader(BaseReader):
         '''a is to b as c is to ...: the k nearest words of b - a + c as (word, cosine) pairs, a, b and c left out;
         analogies([[b, c]], [[a]], k)[0].'''
         return self.analogies([[b, c]], [[a]], k)[0]
+
+    # ---- 3CosMul: the multiplicative analogy score and the top-k by it (include/memb_hip_cosmul.h) ----
+
+    @property
+    def last_cosmul_kernel(self):
+        '''The kernel families of the last cosmul_topk_device call, joined by '+':
+        'query_matrix_trained+cosmul_scores+topk_select_excluding+topk_merge' (slices of the fused matrix kernel in a
+        workspace, scored and selected there), or 'pairs_dense+cosmul_scores+topk_select_excluding+topk_merge' where the
+        cosines of a slice come from similarity_matrix_device's fallback -- uniform and full storage, dims that are no
+        multiple of 4 or beyond 512; 'topk_merge' where such a model is asked with no candidate at all. '' before any call
+        and after a call without questions, which launches nothing. Informational: the bits are the same.'''
+        return self._last_cosmul_kernel
+
+    def cosmul_topk_device(self, terms, offsets, negatives_from, rows, k, *, exclude=None, workspace=None):
+        '''The k best candidates of EVERY question by the 3CosMul score (Levy & Goldberg; gensim's most_similar_cosmul),
+        left on the GPU, without the (T, n) matrix of cosines or the (Q, n) matrix of scores in device memory: (values,
+        positions), a float32 (Q, k) and an int64 (Q, k) tensor in similarity_topk_device's order and with its empty slots.
+        For a candidate with the cosines c of similarity_matrix_device(terms, rows) against a question's terms:
+        num = product of (1 + c) * 0.5 over its positive terms, den likewise over its negative ones, score = num / (den +
+        1e-6), every operation one float32 operation in the order of the terms (include/memb_hip_cosmul.h), so the bits
+        are the same on every path. For trained models whose dim is a multiple of 4 and at most 512 the matrix kernel
+        fills a slice of the candidates in a workspace, cosmul_scores turns it into scores and two selection kernels merge
+        them into the result; otherwise slices of at most 2^19 candidates go through similarity_matrix_device,
+        cosmul_scores and the same selection (last_cosmul_kernel says which).
+        terms : float32 (T, dim) tensor on this reader's device, as the queries of similarity_matrix_device
+        offsets : Q + 1 ascending host integers within 0 .. T: question q takes the terms offsets[q] .. offsets[q + 1], at
+            most 64 (COSMUL_MAX_TERMS) of them
+        negatives_from : Q host integers, offsets[q] <= negatives_from[q] <= offsets[q + 1]: the terms before it are
+            positive, those from it on negative. Both arrays are checked on the host (ValueError) and uploaded by the call.
+        rows : as in similarity_topk_device; None: every row of the model in order
+        k : 1 .. 64
+        exclude : as in similarity_topk_device, one row per question
+        workspace : optional contiguous uint8 tensor on the same device, aligned to 8 bytes, of at least
+            _memb_cosmul.query_cosmul_workspace_bytes(self._impl.context_handle(), T, Q, n, k, minimal=True) bytes, for the
+            fused path. Its size decides the slicing, never the result.
+        One model, float32: no weights, no k > 64, no more than 64 terms, no bfloat16 / float16, no ReadersUnion, no
+        ShardedReader, no pooled-bag candidates.'''
+        import torch
+        index = self._impl.device()
+        if index == _memb.HOST_DEVICE:
+            raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
+        k = topk_size(k)
+        if rows is None:
+            rows = self._all_rows_device(torch, index)
+        self._norms_arguments(torch, rows)
+        if isinstance(terms, torch.Tensor) and terms.dim() != 2:
+            raise ValueError('terms must have shape (T, {}), got {}'.format(self.dim, tuple(terms.shape)))
+        terms, n_terms, ld = self._topk_queries(torch, terms, index)
+        offsets, negatives_from = cosmul_questions(offsets, negatives_from, n_terms)
+        count = negatives_from.size
+        device = rows.device
+        if device.index != index:
+            raise ValueError('terms and rows must be on cuda:{} (the device this reader is staged on), got {} and {}'.format(
+                self.device, terms.device, device))
+        rows = rows.reshape(-1)
+        n = rows.numel()
+        values = torch.empty((count, k), dtype=torch.float32, device=device)
+        positions = torch.empty((count, k), dtype=torch.int64, device=device)
+        stream = _current_stream(torch, index)
+        excluded = (0, 0, 0) if exclude is None else self._topk_exclude(torch, exclude, count, device)
+        context = self._impl.context_handle()
+        fused = _memb_cosmul.query_cosmul_kernel_name(context)
+        self._last_cosmul_kernel = fused if count else ''
+        if count == 0:   # (nothing is launched)
+            return values, positions
+        questions = torch.from_numpy(np.concatenate([offsets, negatives_from]).astype(np.int32)).to(device)
+        offsets_ptr, negatives_ptr = questions.data_ptr(), questions[count + 1:].data_ptr() if count else 0
+        if fused or n == 0:
+            if not fused:   # (no candidate: topk_merge alone fills the empty slots, whatever the model)
+                self._last_cosmul_kernel = 'topk_merge'
+            if workspace is None:
+                workspace = torch.empty((_memb_cosmul.query_cosmul_workspace_bytes(context, n_terms, count, n, k),), dtype=torch.uint8, device=device)
+            elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1
+                    or not workspace.is_contiguous() or workspace.device != device):
+                raise TypeError('workspace must be a contiguous uint8 tensor on cuda:{}'.format(index))
+            done = _memb_cosmul.query_cosmul_nearest_to_device(
+                context, terms.data_ptr(), n_terms, ld, offsets_ptr, negatives_ptr, count, rows.data_ptr(), n, k, *excluded,
+                values.data_ptr(), positions.data_ptr(), k, workspace.data_ptr() if workspace.numel() else 0, workspace.numel(),
+                stream)
+            assert done   # (n == 0 is answered for every model)
+            return values, positions
+        width = min(n, QUERY_DEVICE_SLICE)
+        cosines = torch.empty((max(n_terms, 1), width), dtype=torch.float32, device=device)   # (a row where no term exists: a pointer to hand over)
+        scores = torch.empty((count, width), dtype=torch.float32, device=device)
+        lists = torch.empty((topk_fallback_list_bytes(count, n, k, QUERY_DEVICE_SLICE),), dtype=torch.uint8, device=device)
+        for start in range(0, n, QUERY_DEVICE_SLICE):
+            size = min(n, start + QUERY_DEVICE_SLICE) - start
+            if n_terms:
+                self.similarity_matrix_device(terms, rows[start:start + size], out=cosines[:n_terms, :size])
+            _memb_cosmul.cosmul_scores_to_device(
+                index, cosines.data_ptr(), width, offsets_ptr, negatives_ptr, count, size, scores.data_ptr(), width, stream)
+            _memb.dense_topk_excluding_to_device(
+                index, scores.data_ptr(), count, size, width, start, k, start > 0, *excluded, values.data_ptr(),
+                positions.data_ptr(), k, lists.data_ptr(), lists.numel(), stream)
+        matrix = self._last_query_matrix_kernel if n_terms else ''
+        self._last_cosmul_kernel = '+'.join(
+            part for part in (matrix, _memb_cosmul.cosmul_scores_kernel_name(), _memb.dense_topk_excluding_kernel_name()) if part)
+        return values, positions
+
+    def cosmul_topk(self, terms, offsets, negatives_from, rows, k, exclude=None):
+        '''cosmul_topk_device for host arrays: a numpy float32 (T, dim) array of terms, the questions and numpy row ids (None:
+        every row of the model) in, (values float32 (Q, k), positions int64 (Q, k)) out. A reader on a GPU sends everything
+        up and brings the result back; a device='cpu' reader takes similarity_matrix chunk by chunk, scores it in numpy
+        (cosmul_scores_host) and selects by the same order (topk_host): the same bits. exclude: an integer (Q, E) array,
+        E <= 64.'''
+        terms = np.asarray(terms)
+        if terms.dtype != np.float32:
+            raise TypeError('terms must be a float32 array of shape (T, dim)')
+        if terms.ndim != 2 or terms.shape[1] != self.dim:
+            raise ValueError('terms must have shape (T, {}), got {}'.format(self.dim, terms.shape))
+        k = topk_size(k)
+        terms = np.ascontiguousarray(terms)
+        offsets, negatives_from = cosmul_questions(offsets, negatives_from, terms.shape[0])
+        count = negatives_from.size
+        rows = np.arange(len(self), dtype=np.uint32) if rows is None else np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        if exclude is not None:
+            exclude = np.asarray(exclude)
+            if exclude.dtype.kind not in 'iu':
+                raise TypeError('exclude must be an integer array of shape (Q, E)')
+            if exclude.ndim != 2 or exclude.shape[0] != count:
+                raise ValueError('exclude must have shape (Q, E) = ({}, E), got {}'.format(count, exclude.shape))
+            if exclude.shape[1] > QUERY_TOPK_MAX_EXCLUDED:
+                raise ValueError('exclude names at most {} positions per query, got {}'.format(QUERY_TOPK_MAX_EXCLUDED, exclude.shape[1]))
+            exclude = np.ascontiguousarray(exclude, dtype=np.int64)
+        if self._impl.device() != _memb.HOST_DEVICE:
+            import torch
+            device = 'cuda:{}'.format(self._impl.device())
+            values, positions = self.cosmul_topk_device(
+                torch.from_numpy(terms).to(device), offsets, negatives_from, torch.from_numpy(rows.view(np.int32)).to(device), k,
+                exclude=None if exclude is None else torch.from_numpy(exclude).to(device))
+            return values.cpu().numpy(), positions.cpu().numpy()
+        values = np.full((count, k), -np.inf, dtype=np.float32)
+        positions = np.full((count, k), -1, dtype=np.int64)
+        for start in range(0, rows.size, NORMS_HOST_CHUNK):
+            scores = cosmul_scores_host(self.similarity_matrix(terms, rows[start:start + NORMS_HOST_CHUNK]), offsets, negatives_from)
+            values, positions = topk_host(scores, k, start, (values, positions), exclude)
+        return values, positions
+
+    @staticmethod
+    def _cosmul_entries(positive, negative):
+        '''The entries of analogies_cosmul: (words, offsets int64 (Q + 1), negatives_from int64 (Q), members int64 (Q, E)) --
+        per question its positive words, then its negative ones, each in the order given; members as in _analogy_entries.'''
+        positive = [list(entries) for entries in positive]
+        negative = [[] for _ in positive] if negative is None else [list(entries) for entries in negative]
+        if len(negative) != len(positive):
+            raise ValueError('positive and negative must hold one list per query, got {} and {}'.format(len(positive), len(negative)))
+        words, offsets, negatives_from = [], [0], []
+        for plus, minus in zip(positive, negative):
+            for entry in plus + minus:
+                if not isinstance(entry, (str, bytes)):
+                    raise TypeError('3CosMul takes bare words: it has no weights, got {!r}'.format(entry))
+            words.extend(plus)
+            negatives_from.append(len(words))
+            words.extend(minus)
+            if len(words) - offsets[-1] > COSMUL_MAX_TERMS:
+                raise ValueError('a question takes at most {} words (each is excluded from its answer), got {}'.format(
+                    COSMUL_MAX_TERMS, len(words) - offsets[-1]))
+            offsets.append(len(words))
+        offsets = np.array(offsets, dtype=np.int64)
+        lengths = offsets[1:] - offsets[:-1]
+        width = int(lengths.max()) if lengths.size else 0
+        steps = np.arange(width, dtype=np.int64)[None, :]
+        members = np.where(steps < lengths[:, None], offsets[:-1, None] + steps, -1)
+        return words, offsets, np.array(negatives_from, dtype=np.int64), members
+
+    def analogies_cosmul_device(self, positive, negative=None, k=10):
+        '''analogies_device by the 3CosMul score instead of the cosine of a summed query -- gensim's
+        most_similar_cosmul(positive=, negative=) -- over the WHOLE vocabulary, left on the GPU: (values, rows), a float32
+        (Q, k) tensor of scores and an int64 (Q, k) tensor of row ids (positions in keys()), best first.
+        positive, negative : one list of bare words per question; a (word, weight) pair is a TypeError, since 3CosMul has no
+            weights. negative=None: no negative words. At most 64 words per question (ValueError beyond).
+        The terms are unit_rows_embedding_device of the resolved words, the rest is cosmul_topk_device over every row of the
+        model with the rows of ALL of a question's words excluded, so k goes up to 64. A question with a word the model
+        lacks, or without any word, gives a row of empty slots: row id -1, value -inf.'''
+        import torch
+        index = self._impl.device()
+        if index == _memb.HOST_DEVICE:
+            raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
+        k = topk_size(k)
+        device = 'cuda:{}'.format(index)
+        words, offsets, negatives_from, members = self._cosmul_entries(positive, negative)
+        count = offsets.size - 1
+        if count == 0:
+            return torch.empty((0, k), dtype=torch.float32, device=device), torch.empty((0, k), dtype=torch.int64, device=device)
+        if words:
+            own = self.resolve_rows_device(words)
+            terms = self.unit_rows_embedding_device(own)
+        else:
+            own = torch.empty((0,), dtype=torch.int32, device=device)
+            terms = torch.empty((0, self.dim), dtype=torch.float32, device=device)
+        members = torch.from_numpy(members).to(device)
+        padded = torch.cat([own.to(torch.int64), torch.full((1,), -1, dtype=torch.int64, device=device)])   # (a missing word is -1)
+        exclude = padded[members]   # (members == -1 reads the -1 at the end)
+        values, positions = self.cosmul_topk_device(terms, offsets, negatives_from, None, k, exclude=exclude)
+        unanswered = ((members >= 0) & (exclude < 0)).any(dim=1) | torch.from_numpy(offsets[1:] == offsets[:-1]).to(device)
+        unanswered = unanswered.unsqueeze(1)
+        return (torch.where(unanswered, torch.full_like(values, float('-inf')), values),
+                torch.where(unanswered, torch.full_like(positions, -1), positions))
+
+    def analogies_cosmul(self, positive, negative=None, k=10):
+        '''analogies_cosmul_device on the host: one list of (word, score) pairs per question, best first, none of the
+        question's own words among them; [] for a question with a word the model lacks or without any word.
+        analogies_cosmul_device on a GPU reader; unit_rows_embedding and cosmul_topk with the same exclusion on a
+        device='cpu' reader: the same pairs.'''
+        k = topk_size(k)
+        if self._impl.device() != _memb.HOST_DEVICE:
+            values, positions = (part.cpu().numpy() for part in self.analogies_cosmul_device(positive, negative, k))
+        else:
+            words, offsets, negatives_from, members = self._cosmul_entries(positive, negative)
+            if offsets.size == 1:
+                return []
+            own = self.resolve_rows(words) if words else np.zeros(0, dtype=np.uint32)
+            terms = self.unit_rows_embedding(own) if words else np.zeros((0, self.dim), dtype=np.float32)
+            rows = np.concatenate([np.where(own == 0xFFFFFFFF, -1, own.astype(np.int64)), [-1]])
+            exclude = rows[members]
+            values, positions = self.cosmul_topk(terms, offsets, negatives_from, None, k, exclude=exclude)
+            unanswered = ((members >= 0) & (exclude < 0)).any(axis=1) | (offsets[1:] == offsets[:-1])
+            positions = np.where(unanswered[:, None], -1, positions)
+        vocabulary = self.keys()
+        return [[(vocabulary[row], float(value)) for value, row in zip(values[i], positions[i]) if row >= 0]
+                for i in range(values.shape[0])]
+
+    def analogy_cosmul(self, a, b, c, k=1):
+        '''a is to b as c is to ... by 3CosMul: the k best words as (word, score) pairs, a, b and c left out;
+        analogies_cosmul([[b, c]], [[a]], k)[0].'''
+        return self.analogies_cosmul([[b, c]], [[a]], k)[0]
 
     # ---- every query against every pooled bag of rows, matrix and top-k (include/memb_hip_query_bags.h) ----
 
