@@ -3,6 +3,7 @@
     libmemb_hip.so   HIP kernels + C ABI (include/memb_hip.h), hipcc, gfx950 only
     _memb.*.so       pybind11 module: C++ Reader / Builder on top of the C ABI
     _memb_cosmul.*   pybind11 module: the 3CosMul entry points of the C ABI, by context handle
+    _memb_ranks.*    pybind11 module: the rank-count entry points of the C ABI, likewise
     oracle/...       the CPU checker used by tests (see oracle/README.md)
 
 Everything is built next to its sources so the binaries travel with the tree.
@@ -25,6 +26,7 @@ REFERENCE_SRC = '/root/reference/src'
 HIP_LIBRARY = os.path.join(PACKAGE_DIR, 'libmemb_hip.so')
 EXTENSION = os.path.join(PACKAGE_DIR, '_memb' + sysconfig.get_config_var('EXT_SUFFIX'))
 COSMUL_EXTENSION = os.path.join(PACKAGE_DIR, '_memb_cosmul' + sysconfig.get_config_var('EXT_SUFFIX'))
+RANKS_EXTENSION = os.path.join(PACKAGE_DIR, '_memb_ranks' + sysconfig.get_config_var('EXT_SUFFIX'))
 ORACLE_LIBRARY = os.path.join(ORACLE_DIR, 'libmemb_oracle.so')
 UNIFORM_EXPR_LIBRARY = os.path.join(ORACLE_DIR, 'libmemb_uniform_expr.so')
 REFERENCE_LIBRARY = os.path.join(ORACLE_DIR, '_ref', 'libmemb_ref.so')
@@ -73,6 +75,7 @@ def build_hip_library(force=False, extra_flags=()):
             os.path.join(CSRC, 'memb_hip_queries.hip'), os.path.join(CSRC, 'memb_hip_query_matrix.hip'),
             os.path.join(CSRC, 'memb_hip_query_topk.hip'), os.path.join(CSRC, 'memb_hip_query_bags.hip'),
             os.path.join(CSRC, 'memb_hip_analogies.hip'), os.path.join(CSRC, 'memb_hip_cosmul.hip'),
+            os.path.join(CSRC, 'memb_hip_ranks.hip'),
         ])
     return HIP_LIBRARY
 
@@ -94,17 +97,18 @@ def build_extension(force=False):
             '-L' + PACKAGE_DIR, '-lmemb_hip', '-Wl,-rpath,$ORIGIN',
             '-o', EXTENSION,
         ])
-    # the 3CosMul entries: a module of its own (the surface of _memb is pinned), on the C ABI alone
-    cosmul = os.path.join(CSRC, 'bindings_cosmul.cpp')
-    if force or _newer(COSMUL_EXTENSION, [cosmul] + headers + [HIP_LIBRARY]):
-        _run([
-            'g++', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden', '-pthread',
-            '-Wall', '-ffp-contract=off',
-            '-I' + pybind11.get_include(), '-I' + sysconfig.get_paths()['include'],
-            cosmul,
-            '-L' + PACKAGE_DIR, '-lmemb_hip', '-Wl,-rpath,$ORIGIN',
-            '-o', COSMUL_EXTENSION,
-        ])
+    # the 3CosMul and the rank-count entries: a module of its own each (the surface of _memb is pinned), on the C ABI alone
+    for name, target in (('bindings_cosmul.cpp', COSMUL_EXTENSION), ('bindings_ranks.cpp', RANKS_EXTENSION)):
+        source = os.path.join(CSRC, name)
+        if force or _newer(target, [source] + headers + [HIP_LIBRARY]):
+            _run([
+                'g++', '-O3', '-std=c++17', '-fPIC', '-shared', '-fvisibility=hidden', '-pthread',
+                '-Wall', '-ffp-contract=off',
+                '-I' + pybind11.get_include(), '-I' + sysconfig.get_paths()['include'],
+                source,
+                '-L' + PACKAGE_DIR, '-lmemb_hip', '-Wl,-rpath,$ORIGIN',
+                '-o', target,
+            ])
     return EXTENSION
 
 

@@ -57,7 +57,9 @@
 // selection with a list of excluded positions per row and sums of weighted rows (hip_analogies.h), launched by
 // hip_analogies_launch.h through hip_query_topk_launch.h's launches and slice loop; memb_hip_cosmul.hip -- the 3CosMul
 // score of every (question, candidate) from the cosines of the question's terms (hip_cosmul.h), launched by
-// hip_cosmul_launch.h alone or between the query matrix and that selection, slice after slice.
+// hip_cosmul_launch.h alone or between the query matrix and that selection, slice after slice; memb_hip_ranks.hip -- per
+// row the number of candidates that precede a mark in the selection's order (hip_ranks.h), launched by hip_ranks_launch.h
+// alone or behind the query matrix, slice after slice.
 #include <hip/hip_runtime.h>
 
 #include "../../include/memb_hip.h"
@@ -75,6 +77,7 @@
 #include "../../include/memb_hip_query_bags.h"
 #include "../../include/memb_hip_analogies.h"
 #include "../../include/memb_hip_cosmul.h"
+#include "../../include/memb_hip_ranks.h"
 #include "codec.h"
 #include "hip_narrow.h"
 #include "hip_pooled.h"
@@ -89,6 +92,7 @@
 #include "hip_query_bags.h"
 #include "hip_analogies.h"
 #include "hip_cosmul.h"
+#include "hip_ranks.h"
 #include "wire.h"
 #include "worker_pool.h"
 
@@ -170,6 +174,7 @@ namespace {
 #include "hip_query_bags_launch.h"
 #include "hip_analogies_launch.h"
 #include "hip_cosmul_launch.h"
+#include "hip_ranks_launch.h"
 
 // No C++ exception leaves the library: allocation failures and the like become error codes.
 template <typename Call>
@@ -649,6 +654,45 @@ size_t memb_hip_query_cosmul_workspace_bytes(
 const char* memb_hip_query_cosmul_kernel_name(const memb_hip_ctx* ctx)
 {
     return query_cosmul_kernel_name(ctx);
+}
+
+int memb_hip_dense_ranks_device(
+    int device, const float* matrix, size_t n_rows, size_t n, size_t ld, int64_t base, const float* thresholds, const int64_t* marks,
+    const int64_t* excluded, size_t width, size_t ld_excluded, int accumulate, int64_t* counts, void* workspace,
+    size_t workspace_bytes, void* stream)
+{
+    return guarded([&] {
+        return dense_ranks_device_checked(
+            device, matrix, n_rows, n, ld, base, thresholds, marks, excluded, width, ld_excluded, accumulate != 0, counts, workspace,
+            workspace_bytes, stream);
+    });
+}
+
+size_t memb_hip_dense_ranks_workspace_bytes(size_t n_rows, size_t n)
+{
+    return static_cast<size_t>(denseRanksWorkspaceBytes(n_rows, n));
+}
+
+int memb_hip_query_ranks_device(
+    memb_hip_ctx* ctx, const float* queries, size_t n_queries, size_t ld_queries, const uint32_t* rows, size_t n,
+    const float* thresholds, const int64_t* marks, const int64_t* excluded, size_t width, size_t ld_excluded, int64_t* counts,
+    void* workspace, size_t workspace_bytes, void* stream)
+{
+    return guarded([&] {
+        return query_ranks_device_checked(
+            ctx, queries, n_queries, ld_queries, rows, n, thresholds, marks, excluded, width, ld_excluded, counts, workspace,
+            workspace_bytes, stream);
+    });
+}
+
+size_t memb_hip_query_ranks_workspace_bytes(const memb_hip_ctx* ctx, size_t n_queries, size_t n, int minimal)
+{
+    return query_ranks_workspace_bytes(ctx, n_queries, n, minimal != 0);
+}
+
+const char* memb_hip_query_ranks_kernel_name(const memb_hip_ctx* ctx)
+{
+    return query_ranks_kernel_name(ctx);
 }
 
 int memb_hip_decode_batches_device(memb_hip_ctx* ctx, const memb_hip_batch* batches, size_t count, void* stream)

@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _memb
 from . import _memb_cosmul
+from . import _memb_ranks
 
 
 class BaseReader(ABC):
@@ -404,6 +405,45 @@ def cosmul_scores_host(cosines, offsets, negatives_from):
         return num / (den + eps)
 
 
+def rank_marks(thresholds, marks, count):
+    """The marks of include/memb_hip_ranks.h checked on the host: (thresholds float32 (count,), marks int64 (count,));
+    marks=None: all -1."""
+    thresholds = np.asarray(thresholds)
+    if thresholds.dtype != np.float32:
+        raise TypeError('thresholds must be a float32 array of shape (Q,)')
+    if thresholds.shape != (count,):
+        raise ValueError('thresholds must have shape (Q,) = ({},), got {}'.format(count, thresholds.shape))
+    if marks is None:
+        marks = np.full(count, -1, dtype=np.int64)
+    marks = np.asarray(marks)
+    if marks.dtype.kind not in 'iu':
+        raise TypeError('marks must be an integer array of shape (Q,)')
+    if marks.shape != (count,):
+        raise ValueError('marks must have shape (Q,) = ({},), got {}'.format(count, marks.shape))
+    return np.ascontiguousarray(thresholds), np.ascontiguousarray(marks, dtype=np.int64)
+
+
+def ranks_host(matrix, thresholds, marks, base=0, exclude=None):
+    """The contract of include/memb_hip_ranks.h in numpy: the int64 (Q,) counts of the float32 (Q, n) matrix -- how many
+    columns of row q precede the mark (thresholds[q], marks[q]), a column c being the position base + c: those whose key
+    (topk_keys) is greater than the threshold's, and those with an equal key and a position below marks[q]. exclude:
+    the list of non-candidates, an integer (Q, E) array of positions that are not counted; an entry outside
+    [base, base + n) is ignored, repeats count once. Counts of slices of a matrix, each with its base, add up to the count
+    of the whole."""
+    matrix = np.ascontiguousarray(matrix, dtype=np.float32)
+    count, n = matrix.shape
+    thresholds, marks = rank_marks(thresholds, marks, count)
+    keys = topk_keys(matrix)
+    mark_keys = topk_keys(thresholds)[:, None]
+    positions = base + np.arange(n, dtype=np.int64)
+    precedes = (keys > mark_keys) | ((keys == mark_keys) & (positions[None, :] < marks[:, None]))
+    if exclude is not None:
+        exclude = np.asarray(exclude, dtype=np.int64).reshape(count, -1)
+        named = (exclude >= base) & (exclude < base + n)
+        precedes[np.nonzero(named)[0], (exclude - np.where(named, base, exclude))[named]] = False
+    return precedes.sum(axis=1, dtype=np.int64)
+
+
 QUERY_BAGS_DEVICE_SLICE = 1 << 16   # bags bag_similarity_matrix_device pools into a temporary at a time where no fused kernel exists
 QUERY_BAGS_HOST_SLICE = 1 << 12     # bags bag_similarity_matrix of a device='cpu' reader pools at a time
 COSMUL_MAX_TERMS = _memb_cosmul.COSMUL_MAX_TERMS   # terms per 3CosMul question (MEMB_HIP_COSMUL_MAX_TERMS)
@@ -530,6 +570,7 @@ class Reader(BaseReader):
         self._last_query_matrix_kernel = ''
         self._last_query_topk_kernel = ''
         self._last_cosmul_kernel = ''
+        self._last_ranks_kernel = ''
         self._last_query_bags_kernel = ''
         self._last_query_bags_topk_kernel = ''
         self._all_rows = None              # every row id in order on the device, of similarity_topk_device(rows=None)
@@ -2097,6 +2138,277 @@ class Reader(BaseReader):
         '''a is to b as c is to ... by 3CosMul: the k best words as (word, score) pairs, a, b and c left out;
         analogies_cosmul([[b, c]], [[a]], k)[0].'''
         return self.analogies_cosmul([[b, c]], [[a]], k)[0]
+
+    # ---- the rank of a given candidate: how many candidates precede a mark (include/memb_hip_ranks.h) ----
+
+    @property
+    def last_ranks_kernel(self):
+        '''The kernel families of the last similarity_ranks_device call, joined by '+':
+        'query_matrix_trained+rank_count+rank_fold' (slices of the fused matrix kernel in a workspace, counted there), or
+        'pairs_dense+rank_count+rank_fold' where the cosines of a slice come from similarity_matrix_device's fallback --
+        uniform and full storage, dims that are no multiple of 4 or beyond 512; 'rank_fold' where such a model is asked
+        with no candidate at all. '' before any call and after a call without queries, which launches nothing.
+        Informational: the counts are the same.'''
+        return self._last_ranks_kernel
+
+    def similarity_ranks_device(self, queries, rows, thresholds, marks=None, *, exclude=None, workspace=None):
+        '''Where a mark stands among ALL candidates of every query, left on the GPU, without the (Q, n) matrix of
+        similarity_matrix_device in device memory: an int64 (Q,) tensor, counts[q] the number of candidates of row q of
+        that matrix that PRECEDE the mark (thresholds[q], marks[q]) in similarity_topk_device's order -- a candidate at
+        position c (an index into `rows`) with cosine v precedes it where v is greater than thresholds[q] (NaN above every
+        number, -0.0 equal to +0.0), or equal and c < marks[q] (include/memb_hip_ranks.h). marks[q] = -1 counts the
+        strictly greater cosines, the largest int64 the greater-or-equal ones; with marks[q] the position of a candidate
+        and thresholds[q] the matrix's bits there, counts[q] is that candidate's 0-based rank: the slot it takes in
+        similarity_topk_device's output. No k, no limit of 64. For trained models whose dim is a multiple of 4 and at most
+        512 the matrix kernel fills a slice of the candidates in a workspace (about 32 MiB, independent of n) and two
+        kernels (rank_count, rank_fold) count it; otherwise slices of at most 2^19 candidates go through
+        similarity_matrix_device into one reused temporary and the same kernels (last_ranks_kernel says which).
+        queries : as in similarity_matrix_device
+        rows : as in similarity_topk_device; None: every row of the model in order, so positions are row ids
+        thresholds : contiguous float32 (Q,) tensor on the same device
+        marks : contiguous int64 (Q,) tensor on the same device; None: all -1
+        exclude : as in similarity_topk_device: positions that are no candidates of their query and are not counted
+        workspace : optional contiguous uint8 tensor on the same device, aligned to 8 bytes, of at least
+            _memb_ranks.query_ranks_workspace_bytes(self._impl.context_handle(), Q, n, minimal=True) bytes, for the fused
+            path: a call with it allocates nothing but its result (and the marks where None). Its size decides the
+            slicing, never the result.
+        One model, float32: no list of the preceding candidates themselves, no bfloat16 / float16, no ReadersUnion, no
+        ShardedReader, no pooled-bag candidates, no ranks under the 3CosMul score.'''
+        import torch
+        index = self._impl.device()
+        if index == _memb.HOST_DEVICE:
+            raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
+        if rows is None:
+            rows = self._all_rows_device(torch, index)
+        self._norms_arguments(torch, rows)
+        queries, count, ld = self._topk_queries(torch, queries, index)
+        device = rows.device
+        if device.index != index:
+            raise ValueError('queries and rows must be on cuda:{} (the device this reader is staged on), got {} and {}'.format(
+                self.device, queries.device, device))
+        for name, tensor, dtype in (('thresholds', thresholds, torch.float32), ('marks', marks, torch.int64)):
+            if tensor is None and name == 'marks':
+                continue
+            if not isinstance(tensor, torch.Tensor) or tensor.dtype != dtype:
+                raise TypeError('{} must be a {} tensor of shape (Q,)'.format(name, 'float32' if dtype == torch.float32 else 'int64'))
+            if tensor.device.type != 'cuda':
+                raise TypeError('{} must be on the GPU'.format(name))
+            if tensor.dim() != 1 or tensor.shape[0] != count or not tensor.is_contiguous():
+                raise ValueError('{} must be contiguous with shape (Q,) = ({},), got {}'.format(name, count, tuple(tensor.shape)))
+            if tensor.device != device:
+                raise ValueError('{} must be on {} (the device this reader is staged on), got {}'.format(name, device, tensor.device))
+        excluded = (0, 0, 0) if exclude is None else self._topk_exclude(torch, exclude, count, device)
+        rows = rows.reshape(-1)
+        n = rows.numel()
+        context = self._impl.context_handle()
+        fused = _memb_ranks.query_ranks_kernel_name(context)
+        if fused or n == 0:
+            if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1
+                                          or not workspace.is_contiguous() or workspace.device != device):
+                raise TypeError('workspace must be a contiguous uint8 tensor on cuda:{}'.format(index))
+        counts = torch.empty((count,), dtype=torch.int64, device=device)
+        self._last_ranks_kernel = fused if count else ''
+        if count == 0:   # (nothing is launched)
+            return counts
+        if marks is None:
+            marks = torch.full((count,), -1, dtype=torch.int64, device=device)
+        stream = _current_stream(torch, index)
+        if fused or n == 0:
+            if not fused:   # (no candidate: rank_fold alone writes the zeros, whatever the model)
+                self._last_ranks_kernel = 'rank_fold'
+            if workspace is None:
+                workspace = torch.empty((_memb_ranks.query_ranks_workspace_bytes(context, count, n),), dtype=torch.uint8, device=device)
+            done = _memb_ranks.query_ranks_to_device(
+                context, queries.data_ptr(), count, ld, rows.data_ptr(), n, thresholds.data_ptr(), marks.data_ptr(), *excluded,
+                counts.data_ptr(), workspace.data_ptr() if workspace.numel() else 0, workspace.numel(), stream)
+            assert done   # (n == 0 is answered for every model)
+            return counts
+        width = min(n, QUERY_DEVICE_SLICE)
+        temporary = torch.empty((count, width), dtype=torch.float32, device=device)
+        partials = torch.empty((_memb_ranks.dense_ranks_workspace_bytes(count, width),), dtype=torch.uint8, device=device)
+        for start in range(0, n, QUERY_DEVICE_SLICE):
+            size = min(n, start + QUERY_DEVICE_SLICE) - start
+            self.similarity_matrix_device(queries, rows[start:start + size], out=temporary[:, :size])
+            _memb_ranks.dense_ranks_to_device(
+                index, temporary.data_ptr(), count, size, width, start, thresholds.data_ptr(), marks.data_ptr(), *excluded,
+                start > 0, counts.data_ptr(), partials.data_ptr(), partials.numel(), stream)
+        self._last_ranks_kernel = self._last_query_matrix_kernel + '+' + _memb_ranks.dense_ranks_kernel_name()
+        return counts
+
+    def similarity_ranks(self, queries, rows, thresholds, marks=None, exclude=None):
+        '''similarity_ranks_device for host arrays: a numpy float32 (Q, dim) or (dim,) array of queries, numpy row ids
+        (None: every row of the model), float32 (Q,) thresholds and int64 (Q,) marks (None: all -1) in, a numpy int64 (Q,)
+        array of counts out. A reader on a GPU sends everything up and brings the counts back; a device='cpu' reader takes
+        similarity_matrix chunk by chunk and counts in numpy (ranks_host): the same numbers. exclude: an integer (Q, E)
+        array, E <= 64.'''
+        queries = np.asarray(queries)
+        if queries.dtype != np.float32:
+            raise TypeError('queries must be a float32 array of shape (Q, dim) or (dim,)')
+        if queries.ndim == 1:
+            queries = queries[None, :]
+        if queries.ndim != 2 or queries.shape[1] != self.dim:
+            raise ValueError('queries must have shape (Q, {}) or ({},), got {}'.format(self.dim, self.dim, queries.shape))
+        queries = np.ascontiguousarray(queries)
+        count = queries.shape[0]
+        thresholds, marks = rank_marks(thresholds, marks, count)
+        rows = np.arange(len(self), dtype=np.uint32) if rows is None else np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        if exclude is not None:
+            exclude = np.asarray(exclude)
+            if exclude.dtype.kind not in 'iu':
+                raise TypeError('exclude must be an integer array of shape (Q, E)')
+            if exclude.ndim != 2 or exclude.shape[0] != count:
+                raise ValueError('exclude must have shape (Q, E) = ({}, E), got {}'.format(count, exclude.shape))
+            if exclude.shape[1] > QUERY_TOPK_MAX_EXCLUDED:
+                raise ValueError('exclude names at most {} positions per query, got {}'.format(QUERY_TOPK_MAX_EXCLUDED, exclude.shape[1]))
+            exclude = np.ascontiguousarray(exclude, dtype=np.int64)
+        if self._impl.device() != _memb.HOST_DEVICE:
+            import torch
+            device = 'cuda:{}'.format(self._impl.device())
+            return self.similarity_ranks_device(
+                torch.from_numpy(queries).to(device), torch.from_numpy(rows.view(np.int32)).to(device),
+                torch.from_numpy(thresholds).to(device), torch.from_numpy(marks).to(device),
+                exclude=None if exclude is None else torch.from_numpy(exclude).to(device)).cpu().numpy()
+        counts = np.zeros(count, dtype=np.int64)
+        for start in range(0, rows.size, NORMS_HOST_CHUNK):
+            counts += ranks_host(self.similarity_matrix(queries, rows[start:start + NORMS_HOST_CHUNK]), thresholds, marks, start, exclude)
+        return counts
+
+    def rank_device(self, words_a, words_b):
+        '''gensim's rank(a, b) for pairs of words, left on the GPU: an int64 (P,) tensor, for pair i one plus the number of
+        words of the WHOLE model that precede words_b[i] around the unit row of words_a[i] -- 1 where words_b[i] is the
+        nearest word of words_a[i], which is itself no candidate. The threshold is query_similarity_device of the unit row
+        against the one row of words_b[i], bit for bit the entry of similarity_matrix_device there, the mark is that row,
+        the rest is similarity_ranks_device over every row with words_a[i] as the one non-candidate: the 1-based slot
+        words_b[i] takes in most_similar_device(words_a[i]) however far down that is. 0 where either word is not in the
+        model.'''
+        import torch
+        index = self._impl.device()
+        if index == _memb.HOST_DEVICE:
+            raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
+        words_a, words_b = list(words_a), list(words_b)
+        if len(words_a) != len(words_b):
+            raise ValueError('words_a and words_b must hold one word per pair, got {} and {}'.format(len(words_a), len(words_b)))
+        device = 'cuda:{}'.format(index)
+        count = len(words_a)
+        if count == 0:
+            return torch.empty((0,), dtype=torch.int64, device=device)
+        own = self.resolve_rows_device(words_a + words_b)
+        first, second = own[:count].contiguous(), own[count:].contiguous()
+        queries = self.unit_rows_embedding_device(first)
+        return self._ranks_of_marks(torch, queries, second, first.to(torch.int64).unsqueeze(1), (first < 0) | (second < 0))
+
+    def _ranks_of_marks(self, torch, queries, expected, exclude, unanswered):
+        """the 1-based rank of the row expected[q] (int32, -1: not in the model) around queries[q] over the whole model
+        without the positions exclude[q]; 0 where unanswered[q]"""
+        count = queries.shape[0]
+        groups = torch.arange(count + 1, dtype=torch.int32, device=queries.device)
+        thresholds = self.query_similarity_device(queries, expected, groups)   # (one candidate per group: the matrix's bits)
+        counts = self.similarity_ranks_device(queries, None, thresholds, expected.to(torch.int64), exclude=exclude)
+        return torch.where(unanswered, torch.zeros_like(counts), counts + 1)
+
+    def rank(self, words_a, words_b):
+        '''rank_device on the host: a numpy int64 (P,) array of 1-based ranks, 0 where a word is not in the model. A
+        device='cpu' reader goes through unit_rows_embedding, query_similarity and similarity_ranks: the same numbers.'''
+        words_a, words_b = list(words_a), list(words_b)
+        if len(words_a) != len(words_b):
+            raise ValueError('words_a and words_b must hold one word per pair, got {} and {}'.format(len(words_a), len(words_b)))
+        count = len(words_a)
+        if count == 0:
+            return np.zeros(0, dtype=np.int64)
+        if self._impl.device() != _memb.HOST_DEVICE:
+            return self.rank_device(words_a, words_b).cpu().numpy()
+        own = self.resolve_rows(words_a + words_b)
+        first, second = own[:count], own[count:]
+        missing = (first == 0xFFFFFFFF) | (second == 0xFFFFFFFF)
+        exclude = np.where(first == 0xFFFFFFFF, -1, first.astype(np.int64))[:, None]
+        return self._ranks_of_marks_host(self.unit_rows_embedding(first), second, exclude, missing)
+
+    def _ranks_of_marks_host(self, queries, expected, exclude, unanswered):
+        """_ranks_of_marks of a device='cpu' reader: expected uint32 rows (0xFFFFFFFF: not in the model)"""
+        count = queries.shape[0]
+        thresholds = self.query_similarity(queries, expected, np.arange(count + 1))
+        marks = np.where(expected == 0xFFFFFFFF, -1, expected.astype(np.int64))
+        counts = self.similarity_ranks(queries, None, thresholds, marks, exclude=exclude)
+        return np.where(unanswered, 0, counts + 1)
+
+    def count_closer_than(self, words_a, words_b):
+        '''len(gensim's closer_than(a, b)) for pairs of words: a numpy int64 (P,) array, the number of words of the whole
+        model closer to words_a[i] than words_b[i] is (words_a[i] itself left out; equal cosines: the lower row first) --
+        rank(words_a, words_b) - 1, so -1 where a word is not in the model.'''
+        return self.rank(words_a, words_b) - 1
+
+    def analogy_ranks_device(self, positive, negative, expected):
+        '''The rank of the EXPECTED answer of every analogy question, left on the GPU: an int64 (Q,) tensor, 1 where
+        analogies_device(positive, negative, k=1) answers expected[q], 2 where it is the second best word, and so on down
+        the whole vocabulary -- what mean reciprocal rank and hits@k for any k are made of. The queries are
+        analogies_device's composed queries, a question's own words are no candidates, the mark is the row of expected[q]
+        with its cosine against the query as the threshold (query_similarity_device: the matrix's bits). 0 where a word
+        of the question or the expected word is not in the model, or the question has no word.
+        positive, negative : as in analogies_device (negative may be None)
+        expected : one word per question'''
+        import torch
+        index = self._impl.device()
+        if index == _memb.HOST_DEVICE:
+            raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
+        device = 'cuda:{}'.format(index)
+        words, weights, offsets, members = self._analogy_entries(positive, negative)
+        expected = list(expected)
+        count = offsets.size - 1
+        if len(expected) != count:
+            raise ValueError('expected must hold one word per question, got {} for {}'.format(len(expected), count))
+        if count == 0:
+            return torch.empty((0,), dtype=torch.int64, device=device)
+        own = self.resolve_rows_device(words + expected)
+        answers = own[len(words):].contiguous()
+        own = own[:len(words)].contiguous()
+        queries = self.compose_queries_device(
+            own, torch.from_numpy(offsets.astype(np.int32)).to(device), torch.from_numpy(weights).to(device))
+        members = torch.from_numpy(members).to(device)
+        padded = torch.cat([own.to(torch.int64), torch.full((1,), -1, dtype=torch.int64, device=device)])   # (a missing word is -1)
+        exclude = padded[members]   # (members == -1 reads the -1 at the end)
+        unanswered = ((members >= 0) & (exclude < 0)).any(dim=1) | torch.from_numpy(offsets[1:] == offsets[:-1]).to(device) | (answers < 0)
+        return self._ranks_of_marks(torch, queries, answers, exclude, unanswered)
+
+    def analogy_ranks(self, positive, negative, expected):
+        '''analogy_ranks_device on the host: a numpy int64 (Q,) array of 1-based ranks, 0 where a question is not
+        answered. A device='cpu' reader goes through compose_queries, query_similarity and similarity_ranks: the same
+        numbers.'''
+        if self._impl.device() != _memb.HOST_DEVICE:
+            return self.analogy_ranks_device(positive, negative, expected).cpu().numpy()
+        words, weights, offsets, members = self._analogy_entries(positive, negative)
+        expected = list(expected)
+        count = offsets.size - 1
+        if len(expected) != count:
+            raise ValueError('expected must hold one word per question, got {} for {}'.format(len(expected), count))
+        if count == 0:
+            return np.zeros(0, dtype=np.int64)
+        own = self.resolve_rows(words + expected)
+        answers, own = own[len(words):], own[:len(words)]
+        rows = np.concatenate([np.where(own == 0xFFFFFFFF, -1, own.astype(np.int64)), [-1]])
+        exclude = rows[members]
+        unanswered = ((members >= 0) & (exclude < 0)).any(axis=1) | (offsets[1:] == offsets[:-1]) | (answers == 0xFFFFFFFF)
+        return self._ranks_of_marks_host(self.compose_queries(own, offsets, weights), answers, exclude, unanswered)
+
+    def evaluate_analogies(self, questions):
+        '''An analogy test set in one pass: questions is an iterable of (a, b, c, expected) -- a is to b as c is to
+        expected, as the lines of the Google analogy set. Returns a dict: 'questions' (how many were given), 'answered'
+        (those whose four words the model knows; the others count nowhere else, as in gensim's evaluation), 'accuracy'
+        (the share of the answered ones whose expected word is the best candidate, a, b and c left out: rank 1) and
+        'mean_reciprocal_rank' (the mean of 1 / rank over the answered ones), both 0.0 where none is answered. The ranks
+        are analogy_ranks([[b, c]], [[a]], [expected]) for all questions at once; the figures are worked out on the host.'''
+        questions = [tuple(question) for question in questions]
+        for question in questions:
+            if len(question) != 4:
+                raise ValueError('a question is (a, b, c, expected), got {!r}'.format(question))
+        ranks = self.analogy_ranks([[b, c] for _, b, c, _ in questions], [[a] for a, _, _, _ in questions],
+                                   [expected for _, _, _, expected in questions])
+        answered = ranks[ranks > 0]
+        return {
+            'questions': len(questions),
+            'answered': int(answered.size),
+            'accuracy': float((answered == 1).sum() / answered.size) if answered.size else 0.0,
+            'mean_reciprocal_rank': float((1.0 / answered).mean()) if answered.size else 0.0,
+        }
 
     # ---- every query against every pooled bag of rows, matrix and top-k (include/memb_hip_query_bags.h) ----
 
