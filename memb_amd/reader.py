@@ -574,6 +574,7 @@ class Reader(BaseReader):
         self._last_query_bags_kernel = ''
         self._last_query_bags_topk_kernel = ''
         self._all_rows = None              # every row id in order on the device, of similarity_topk_device(rows=None)
+        self._all_rows_lock = threading.Lock()
         self._whole_group_offsets = None   # ((n, device), the device tensor [0, n]) of query_similarity_device(offsets=None)
 
     @property
@@ -1578,10 +1579,19 @@ class Reader(BaseReader):
 
     def _all_rows_device(self, torch, index):
         """every row id of the model in order, on the device. Kept for the reader's lifetime once rows=None was asked for:
-        4 bytes per word (8.8 MB for 2.2 M words), a torch tensor, so not part of info()['device_bytes']"""
-        if self._all_rows is None or self._all_rows.device.index != index:
-            self._all_rows = torch.arange(len(self), dtype=torch.int32, device='cuda:{}'.format(index))
-        return self._all_rows
+        4 bytes per word (8.8 MB for 2.2 M words), a torch tensor, so not part of info()['device_bytes']. Callers on other
+        streams read it without an event of their own: it is built by one of them and finished before any other sees it."""
+        rows = self._all_rows
+        if rows is None or rows.device.index != index:
+            with self._all_rows_lock:
+                rows = self._all_rows
+                if rows is None or rows.device.index != index:
+                    rows = torch.arange(len(self), dtype=torch.int32, device='cuda:{}'.format(index))
+                    if torch.cuda.is_current_stream_capturing():   # (a node of that graph: nothing to keep for others)
+                        return rows
+                    torch.cuda.current_stream(index).synchronize()
+                    self._all_rows = rows
+        return rows
 
     def _topk_exclude(self, torch, exclude, count, device):
         """the checks of similarity_topk_device on its exclusion list: (pointer, E, row stride in entries)"""
@@ -1925,7 +1935,7 @@ class Reader(BaseReader):
         and after a call without questions, which launches nothing. Informational: the bits are the same.'''
         return self._last_cosmul_kernel
 
-    def cosmul_topk_device(self, terms, offsets, negatives_from, rows, k, *, exclude=None, workspace=None):
+    def cosmul_topk_device(self, terms, offsets, negatives_from, rows, k, *, exclude=None, workspace=None, questions=None):
         '''The k best candidates of EVERY question by the 3CosMul score (Levy & Goldberg; gensim's most_similar_cosmul),
         left on the GPU, without the (T, n) matrix of cosines or the (Q, n) matrix of scores in device memory: (values,
         positions), a float32 (Q, k) and an int64 (Q, k) tensor in similarity_topk_device's order and with its empty slots.
@@ -1947,6 +1957,11 @@ class Reader(BaseReader):
         workspace : optional contiguous uint8 tensor on the same device, aligned to 8 bytes, of at least
             _memb_cosmul.query_cosmul_workspace_bytes(self._impl.context_handle(), T, Q, n, k, minimal=True) bytes, for the
             fused path. Its size decides the slicing, never the result.
+        questions : optional contiguous int32 tensor of 2 Q + 1 entries on the same device: offsets, then negatives_from, as
+            the call uploads them where it is None. That upload is a copy from the host, which no graph capture admits: a
+            caller who captures the call uploads the tensor beforehand, keeps it alive for the replays and passes it here.
+            offsets and negatives_from are given and checked all the same, and the tensor must hold their numbers (the
+            kernels trust it).
         One model, float32: no weights, no k > 64, no more than 64 terms, no bfloat16 / float16, no ReadersUnion, no
         ShardedReader, no pooled-bag candidates.'''
         import torch
@@ -1977,7 +1992,11 @@ class Reader(BaseReader):
         self._last_cosmul_kernel = fused if count else ''
         if count == 0:   # (nothing is launched)
             return values, positions
-        questions = torch.from_numpy(np.concatenate([offsets, negatives_from]).astype(np.int32)).to(device)
+        if questions is None:
+            questions = torch.from_numpy(np.concatenate([offsets, negatives_from]).astype(np.int32)).to(device)
+        elif (not isinstance(questions, torch.Tensor) or questions.dtype != torch.int32 or questions.dim() != 1
+                or not questions.is_contiguous() or questions.device != device or questions.numel() != 2 * count + 1):
+            raise TypeError('questions must be a contiguous int32 tensor of 2 Q + 1 = {} entries on cuda:{}'.format(2 * count + 1, index))
         offsets_ptr, negatives_ptr = questions.data_ptr(), questions[count + 1:].data_ptr() if count else 0
         if fused or n == 0:
             if not fused:   # (no candidate: topk_merge alone fills the empty slots, whatever the model)

@@ -403,3 +403,31 @@ def test_refusals(native, make_model):
     torch.cuda.synchronize()
     assert (values.cpu().numpy() == np.float32(SENTINEL)).all() and (positions.cpu().numpy() == SENTINEL_POSITION).all()
     assert (workspace.cpu().numpy() == 0x7FC00001).all() and (fused_workspace.cpu().numpy() == 0x7FC00001).all()
+
+
+# ---- 7. a captured graph ----
+
+def test_captured_into_a_graph(native, make_model):
+    """similarity_topk_device with exclusion lists and a caller's workspace, captured, then replayed once over other queries
+    AND other lists, both written in place; the answer is the host reader's for those"""
+    import torch
+    from test_gpu_query_topk import capture, graph_case, slices_of_256
+    reader, host, rows, on_device, others = graph_case(native, make_model, 73)
+    count, k = 5, 10
+    queries = torch.from_numpy(np.random.default_rng(74).standard_normal((count, 300)).astype(np.float32)).cuda()
+    lists = torch.from_numpy(np.random.default_rng(75).integers(0, rows.size, size=(count, 6)).astype(np.int64)).cuda()
+    workspace = slices_of_256(reader._impl.query_topk_workspace_bytes(count, rows.size, k, True), count)
+    graph, (values, positions) = capture(lambda: reader.similarity_topk_device(queries, on_device, k, exclude=lists, workspace=workspace))
+    assert reader.last_query_topk_kernel == FUSED
+    # the other lists: three of each other query's tied best, a column of the first and of the last slice, padding
+    best = host.similarity_topk(others, rows, 64)[1]
+    other_lists = np.concatenate([best[:, [0, 2, 5]], np.broadcast_to(np.array([3, rows.size - 1, -1]), (count, 3))], axis=1).astype(np.int64)
+    queries.copy_(torch.from_numpy(others))
+    lists.copy_(torch.from_numpy(other_lists))
+    values.fill_(SENTINEL)
+    positions.fill_(SENTINEL_POSITION)
+    graph.replay()
+    torch.cuda.synchronize()
+    want = host.similarity_topk(others, rows, k, exclude=other_lists)
+    assert not same_topk(want, host.similarity_topk(others, rows, k))   # (the lists name entries that would have been kept)
+    assert same_topk((values.cpu().numpy(), positions.cpu().numpy()), want)

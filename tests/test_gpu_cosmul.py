@@ -89,6 +89,20 @@ def test_the_kernel_alone(native, cosines_and_scores, n):
         assert same_bits(one, want[q:q + 1, :n]), (n, q)
 
 
+@pytest.mark.parametrize('n', COLUMNS)
+def test_one_positive_term_alone(native, cosines_and_scores, n):
+    # (64 terms in one launch of their own are above: questions 6 and 7; the question of a single positive term is not)
+    cosines, offsets, negatives_from, want = cosines_and_scores
+    assert PAIRS[1] == (1, 0) and offsets[2] - offsets[1] == 1 and negatives_from[1] == offsets[2]
+    one = cosmul_scores(cosines[:, :n], offsets[1:3], negatives_from[1:2])
+    assert same_bits(one, want[1:2, :n]), n
+    # score = ((1 + c) * 0.5) / (1 + 1e-6): one rounded operation each
+    c = cosines[offsets[1], :n]
+    with np.errstate(invalid='ignore'):
+        by_hand = ((np.float32(1) + c) * np.float32(0.5)) / (np.float32(1) + EPSILON)
+    assert same_bits(one[0], by_hand.astype(np.float32)), n
+
+
 def test_nothing_to_score_is_a_no_op(native):
     import torch
     scores = torch.full((3, 9), SENTINEL, dtype=torch.float32, device='cuda')
@@ -383,3 +397,41 @@ def test_refusals(native, make_model):
     assert cosmul().query_cosmul_nearest_to_device(uniform._impl.context_handle(), **fine) is False
     torch.cuda.synchronize()
     assert (values.cpu().numpy() == np.float32(SENTINEL)).all() and (workspace.cpu().numpy() == 0x7FC00001).all()
+
+
+# ---- 6. a captured graph ----
+
+def test_captured_into_a_graph(native, make_model):
+    """cosmul_topk_device with a caller's workspace and its questions uploaded beforehand (questions=: the upload is the one
+    step of the call no capture admits), captured, then replayed once over other terms and other lists, both written in
+    place; the answer is the host reader's for those"""
+    import torch
+    from test_gpu_query_topk import capture, graph_case, slices_of_256
+    reader, host, rows, on_device, _ = graph_case(native, make_model, 76)
+    offsets, negatives_from, n_terms = questions_of(QUESTIONS)
+    count, k = len(QUESTIONS), 10
+    rng = np.random.default_rng(77)
+    terms = torch.from_numpy(rng.standard_normal((n_terms, 300)).astype(np.float32)).cuda()
+    lists = torch.from_numpy(rng.integers(0, rows.size, size=(count, 6)).astype(np.int64)).cuda()
+    questions = torch.from_numpy(np.concatenate([offsets, negatives_from]).astype(np.int32)).cuda()
+    context = reader._impl.context_handle()
+    workspace = slices_of_256(cosmul().query_cosmul_workspace_bytes(context, n_terms, count, rows.size, k, True), n_terms + count)
+    graph, (values, positions) = capture(lambda: reader.cosmul_topk_device(
+        terms, offsets, negatives_from, on_device, k, exclude=lists, workspace=workspace, questions=questions))
+    assert reader.last_cosmul_kernel == FUSED
+    # the other terms: unit rows of the model that are candidates themselves, so scores repeat bit for bit
+    valid = np.unique(rows[rows < N_ROWS])
+    other_terms = host.unit_rows_embedding(valid[np.arange(n_terms) % 5])
+    best = host.cosmul_topk(other_terms, offsets, negatives_from, rows, 64)[1]
+    other_lists = np.concatenate([best[:, [0, 2, 5]], np.broadcast_to(np.array([3, rows.size - 1, -1]), (count, 3))], axis=1).astype(np.int64)
+    terms.copy_(torch.from_numpy(other_terms))
+    lists.copy_(torch.from_numpy(other_lists))
+    values.fill_(SENTINEL)
+    positions.fill_(SENTINEL_POSITION)
+    graph.replay()
+    torch.cuda.synchronize()
+    want = host.cosmul_topk(other_terms, offsets, negatives_from, rows, k, exclude=other_lists)
+    assert not same_topk(want, host.cosmul_topk(other_terms, offsets, negatives_from, rows, k))
+    assert same_topk((values.cpu().numpy(), positions.cpu().numpy()), want)
+    with pytest.raises(TypeError, match='questions'):
+        reader.cosmul_topk_device(terms, offsets, negatives_from, on_device, k, questions=questions[:-1])

@@ -446,3 +446,40 @@ def test_python_refusals_on_the_device(native, make_model):
         reader.bag_similarity_topk_device(queries, rows, offsets, 3, workspace=torch.zeros((64,), dtype=torch.float32, device='cuda'))
     with pytest.raises(RuntimeError, match='workspace too small'):
         reader.bag_similarity_topk_device(queries, rows, offsets, 3, workspace=torch.zeros((8,), dtype=torch.uint8, device='cuda'))
+
+
+# ---- 8. a captured graph ----
+
+def test_topk_captured_into_a_graph(native, make_model, topk_reader):
+    """bag_similarity_topk_device with a caller's workspace allocates nothing but its results: captured on one stream (a
+    single chain of launches, five slices of 256 bags), then replayed once over other queries written in place -- rows of
+    the model that are bags of one entry themselves, each repeated by the bag behind it; the answer is a host reader's"""
+    import torch
+    reader = topk_reader
+    path, _ = make_model(N_ROWS, 300, 'trained', 4)
+    host = native.Reader(path, device='cpu')
+    bags, count, k = 1100, 5, 10
+    rows, offsets = corpus_with_ties(reader, bags, 91)
+    singles = [b for b in range(1, bags, 3) if offsets[b + 1] - offsets[b] == 1][:count]   # (bag b + 1 repeats bag b)
+    assert len(singles) == count
+    others = host.rows_embedding(rows[offsets[singles]])
+    on_device, cut = to_device(rows), to_device(offsets)
+    queries = torch.from_numpy(queries_batch(count, 300, 92)).cuda()
+    least = reader._impl.query_bags_topk_workspace_bytes(count, bags, k, minimal=True)
+    workspace = torch.empty((least + 4 * count * 192,), dtype=torch.uint8, device='cuda')
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        reader.bag_similarity_topk_device(queries, on_device, cut, k, workspace=workspace)   # (warm-up)
+    stream.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=stream):
+        values, positions = reader.bag_similarity_topk_device(queries, on_device, cut, k, workspace=workspace)
+    queries.copy_(torch.from_numpy(others))
+    values.fill_(float(SENTINEL))
+    positions.fill_(-77)
+    graph.replay()
+    torch.cuda.synchronize()
+    want = host.bag_similarity_topk(others, rows, offsets, k)
+    for q, b in enumerate(singles):
+        assert want[1][q, :2].tolist() == [b, b + 1] and want[0][q, 0].view(np.uint32) == want[0][q, 1].view(np.uint32)
+    assert same_topk((values.cpu().numpy(), positions.cpu().numpy()), want)

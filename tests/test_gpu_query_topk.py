@@ -349,3 +349,53 @@ def test_refusals(native, make_model):
     # the reader still answers
     itself = reader.rows_embedding_device(rows[:1])
     assert int(reader.similarity_topk_device(itself, rows, 1)[1][0, 0]) == 0
+
+
+# ---- 6. a captured graph ----
+
+def graph_case(native, make_model, seed):
+    """(reader, host reader, candidates, their ids on the device, five other queries): 1100 tied candidates -- five slices
+    of 256 under the workspace of slices_of_256 --, the other queries rows of the model that are candidates themselves"""
+    path, _ = make_model(N_ROWS, 300, 'trained', 4)
+    rows = tied_candidates(1100, N_ROWS, seed)
+    host = native.Reader(path, device='cpu')
+    return native.Reader(path), host, rows, to_device(rows), host.rows_embedding(np.unique(rows[rows < N_ROWS])[:5])
+
+
+def slices_of_256(minimal_bytes, matrix_rows):
+    """a workspace for slices of 256 candidates where the minimal one holds slices of 64"""
+    import torch
+    return torch.empty((minimal_bytes + 4 * matrix_rows * 192,), dtype=torch.uint8, device='cuda')
+
+
+def capture(call):
+    """call() once on a side stream, then captured on that one stream (a single chain of launches): (graph, what it returned)"""
+    import torch
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        call()   # (warm-up)
+    stream.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=stream):
+        returned = call()
+    return graph, returned
+
+
+def test_captured_into_a_graph(native, make_model):
+    """similarity_topk_device with a caller's workspace allocates nothing but its results: captured, then replayed once over
+    other queries written in place; the answer is the host reader's for those"""
+    import torch
+    reader, host, rows, on_device, others = graph_case(native, make_model, 71)
+    count, k = 5, 10
+    queries = torch.from_numpy(np.random.default_rng(72).standard_normal((count, 300)).astype(np.float32)).cuda()
+    workspace = slices_of_256(reader._impl.query_topk_workspace_bytes(count, rows.size, k, True), count)
+    graph, (values, positions) = capture(lambda: reader.similarity_topk_device(queries, on_device, k, workspace=workspace))
+    assert reader.last_query_topk_kernel == FUSED
+    queries.copy_(torch.from_numpy(others))
+    values.fill_(SENTINEL)
+    positions.fill_(SENTINEL_POSITION)
+    graph.replay()
+    torch.cuda.synchronize()
+    want = host.similarity_topk(others, rows, k)
+    assert len(np.unique(want[0][0])) == 1 and (np.diff(want[1][0]) > 0).all()   # (bit-equal best, lower position first)
+    assert same_topk((values.cpu().numpy(), positions.cpu().numpy()), want)
