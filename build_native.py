@@ -4,6 +4,7 @@
     _memb.*.so       pybind11 module: C++ Reader / Builder on top of the C ABI
     _memb_cosmul.*   pybind11 module: the 3CosMul entry points of the C ABI, by context handle
     _memb_ranks.*    pybind11 module: the rank-count entry points of the C ABI, likewise
+    _memb_within.*   pybind11 module: the entry points that list the candidates before a mark, likewise
     oracle/...       the CPU checker used by tests (see oracle/README.md)
 
 Everything is built next to its sources so the binaries travel with the tree.
@@ -27,6 +28,7 @@ HIP_LIBRARY = os.path.join(PACKAGE_DIR, 'libmemb_hip.so')
 EXTENSION = os.path.join(PACKAGE_DIR, '_memb' + sysconfig.get_config_var('EXT_SUFFIX'))
 COSMUL_EXTENSION = os.path.join(PACKAGE_DIR, '_memb_cosmul' + sysconfig.get_config_var('EXT_SUFFIX'))
 RANKS_EXTENSION = os.path.join(PACKAGE_DIR, '_memb_ranks' + sysconfig.get_config_var('EXT_SUFFIX'))
+WITHIN_EXTENSION = os.path.join(PACKAGE_DIR, '_memb_within' + sysconfig.get_config_var('EXT_SUFFIX'))
 ORACLE_LIBRARY = os.path.join(ORACLE_DIR, 'libmemb_oracle.so')
 UNIFORM_EXPR_LIBRARY = os.path.join(ORACLE_DIR, 'libmemb_uniform_expr.so')
 REFERENCE_LIBRARY = os.path.join(ORACLE_DIR, '_ref', 'libmemb_ref.so')
@@ -75,7 +77,7 @@ def build_hip_library(force=False, extra_flags=()):
             os.path.join(CSRC, 'memb_hip_queries.hip'), os.path.join(CSRC, 'memb_hip_query_matrix.hip'),
             os.path.join(CSRC, 'memb_hip_query_topk.hip'), os.path.join(CSRC, 'memb_hip_query_bags.hip'),
             os.path.join(CSRC, 'memb_hip_analogies.hip'), os.path.join(CSRC, 'memb_hip_cosmul.hip'),
-            os.path.join(CSRC, 'memb_hip_ranks.hip'),
+            os.path.join(CSRC, 'memb_hip_ranks.hip'), os.path.join(CSRC, 'memb_hip_within.hip'),
         ])
     return HIP_LIBRARY
 
@@ -97,8 +99,10 @@ def build_extension(force=False):
             '-L' + PACKAGE_DIR, '-lmemb_hip', '-Wl,-rpath,$ORIGIN',
             '-o', EXTENSION,
         ])
-    # the 3CosMul and the rank-count entries: a module of its own each (the surface of _memb is pinned), on the C ABI alone
-    for name, target in (('bindings_cosmul.cpp', COSMUL_EXTENSION), ('bindings_ranks.cpp', RANKS_EXTENSION)):
+    # the 3CosMul, the rank-count and the listing entries: a module of its own each (the surface of _memb is pinned), on the
+    # C ABI alone
+    for name, target in (('bindings_cosmul.cpp', COSMUL_EXTENSION), ('bindings_ranks.cpp', RANKS_EXTENSION),
+                         ('bindings_within.cpp', WITHIN_EXTENSION)):
         source = os.path.join(CSRC, name)
         if force or _newer(target, [source] + headers + [HIP_LIBRARY]):
             _run([

@@ -48,9 +48,10 @@ try:
     from . import _memb
     from . import _memb_cosmul   # noqa: F401  (the 3CosMul entries, a module of its own beside _memb)
     from . import _memb_ranks    # noqa: F401  (the rank counts, likewise)
+    from . import _memb_within   # noqa: F401  (the lists of the candidates before a mark, likewise)
 except ImportError as error:  # fail loudly: nothing here works without the native code
     raise ImportError(
-        'memb_amd: the native extension (_memb / _memb_cosmul / _memb_ranks / libmemb_hip.so) is missing or does not load ({}). '
+        'memb_amd: the native extension (_memb / _memb_cosmul / _memb_ranks / _memb_within / libmemb_hip.so) is missing or does not load ({}). '
         'Build it with `python build_native.py` (needs hipcc).'.format(error)) from error
 
 from .builder import Builder

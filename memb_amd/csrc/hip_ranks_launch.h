@@ -100,28 +100,35 @@ inline uint64_t queryRanksWorkspaceBytes(uint64_t nQueries, uint64_t n, bool min
 }
 
 // The candidates of one slice under a workspace of workspaceBytes, by planTopkSlice's rule: all n where they fit,
-// otherwise the largest multiple of MIN_SLICE that does, at most MAX_SLICE; 0: the workspace is too small. The partial
-// counts grow with the slice in steps (one per BLOCK_RUN columns and query), so the largest multiple is found by
-// bisection over rankSliceBytes, which never falls as the slice grows.
-inline uint64_t planRanksSlice(uint64_t nQueries, uint64_t n, uint64_t workspaceBytes)
+// otherwise the largest multiple of MIN_SLICE that does, at most MAX_SLICE; 0: the workspace is too small. What a slice
+// needs beside its cosines grows with the slice in steps (per BLOCK_RUN columns and query), so the largest multiple is
+// found by bisection over sliceBytes(nQueries, slice), which never falls as the slice grows.
+template <typename SliceBytes>
+inline uint64_t planSliceByBisection(uint64_t nQueries, uint64_t n, uint64_t workspaceBytes, SliceBytes sliceBytes)
 {
     if (!nQueries || !n) {
         return 0;
     }
-    if (n <= memb_query_topk::MAX_SLICE && rankSliceBytes(nQueries, n) <= workspaceBytes) {
+    if (n <= memb_query_topk::MAX_SLICE && sliceBytes(nQueries, n) <= workspaceBytes) {
         return n;
     }
     uint64_t fits = 0;                                                                      // (in units of MIN_SLICE: fits)
     uint64_t beyond = std::min(n, memb_query_topk::MAX_SLICE) / memb_query_topk::MIN_SLICE + 1;   // (does not, or is not asked for)
     while (beyond - fits > 1) {
         const uint64_t middle = fits + (beyond - fits) / 2;
-        if (rankSliceBytes(nQueries, middle * memb_query_topk::MIN_SLICE) <= workspaceBytes) {
+        if (sliceBytes(nQueries, middle * memb_query_topk::MIN_SLICE) <= workspaceBytes) {
             fits = middle;
         } else {
             beyond = middle;
         }
     }
     return fits * memb_query_topk::MIN_SLICE;
+}
+
+// planSliceByBisection for the partial counts and cosines of memb_hip_query_ranks_device
+inline uint64_t planRanksSlice(uint64_t nQueries, uint64_t n, uint64_t workspaceBytes)
+{
+    return planSliceByBisection(nQueries, n, workspaceBytes, rankSliceBytes);
 }
 
 // What memb_hip_query_ranks_device refuses before it looks at the model, or null. dim: the model's. The matrix call's own

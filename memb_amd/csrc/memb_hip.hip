@@ -59,7 +59,8 @@
 // score of every (question, candidate) from the cosines of the question's terms (hip_cosmul.h), launched by
 // hip_cosmul_launch.h alone or between the query matrix and that selection, slice after slice; memb_hip_ranks.hip -- per
 // row the number of candidates that precede a mark in the selection's order (hip_ranks.h), launched by hip_ranks_launch.h
-// alone or behind the query matrix, slice after slice.
+// alone or behind the query matrix, slice after slice; memb_hip_within.hip -- per row the list of those candidates
+// themselves in CSR form, an ordered compaction (hip_within.h), launched by hip_within_launch.h the same two ways.
 #include <hip/hip_runtime.h>
 
 #include "../../include/memb_hip.h"
@@ -78,6 +79,7 @@
 #include "../../include/memb_hip_analogies.h"
 #include "../../include/memb_hip_cosmul.h"
 #include "../../include/memb_hip_ranks.h"
+#include "../../include/memb_hip_within.h"
 #include "codec.h"
 #include "hip_narrow.h"
 #include "hip_pooled.h"
@@ -93,6 +95,7 @@
 #include "hip_analogies.h"
 #include "hip_cosmul.h"
 #include "hip_ranks.h"
+#include "hip_within.h"
 #include "wire.h"
 #include "worker_pool.h"
 
@@ -175,6 +178,7 @@ namespace {
 #include "hip_analogies_launch.h"
 #include "hip_cosmul_launch.h"
 #include "hip_ranks_launch.h"
+#include "hip_within_launch.h"
 
 // No C++ exception leaves the library: allocation failures and the like become error codes.
 template <typename Call>
@@ -693,6 +697,43 @@ size_t memb_hip_query_ranks_workspace_bytes(const memb_hip_ctx* ctx, size_t n_qu
 const char* memb_hip_query_ranks_kernel_name(const memb_hip_ctx* ctx)
 {
     return query_ranks_kernel_name(ctx);
+}
+
+int memb_hip_dense_within_device(
+    int device, const float* matrix, size_t n_rows, size_t n, size_t ld, int64_t base, const float* thresholds, const int64_t* marks,
+    const int64_t* excluded, size_t width, size_t ld_excluded, int accumulate, const int64_t* offsets, int64_t* cursors,
+    int64_t* positions, float* values, size_t capacity, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return guarded([&] {
+        const WithinLists lists{thresholds, marks, excluded, width, ld_excluded, offsets, cursors, positions, values, capacity};
+        return dense_within_device_checked(device, matrix, n_rows, n, ld, base, lists, accumulate != 0, workspace, workspace_bytes, stream);
+    });
+}
+
+size_t memb_hip_dense_within_workspace_bytes(size_t n_rows, size_t n)
+{
+    return static_cast<size_t>(denseWithinWorkspaceBytes(n_rows, n));
+}
+
+int memb_hip_query_within_device(
+    memb_hip_ctx* ctx, const float* queries, size_t n_queries, size_t ld_queries, const uint32_t* rows, size_t n,
+    const float* thresholds, const int64_t* marks, const int64_t* excluded, size_t width, size_t ld_excluded, const int64_t* offsets,
+    int64_t* cursors, int64_t* positions, float* values, size_t capacity, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return guarded([&] {
+        const WithinLists lists{thresholds, marks, excluded, width, ld_excluded, offsets, cursors, positions, values, capacity};
+        return query_within_device_checked(ctx, queries, n_queries, ld_queries, rows, n, lists, workspace, workspace_bytes, stream);
+    });
+}
+
+size_t memb_hip_query_within_workspace_bytes(const memb_hip_ctx* ctx, size_t n_queries, size_t n, int minimal)
+{
+    return query_within_workspace_bytes(ctx, n_queries, n, minimal != 0);
+}
+
+const char* memb_hip_query_within_kernel_name(const memb_hip_ctx* ctx)
+{
+    return query_within_kernel_name(ctx);
 }
 
 int memb_hip_decode_batches_device(memb_hip_ctx* ctx, const memb_hip_batch* batches, size_t count, void* stream)

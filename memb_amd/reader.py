@@ -12,6 +12,7 @@ import numpy as np
 from . import _memb
 from . import _memb_cosmul
 from . import _memb_ranks
+from . import _memb_within
 
 
 class BaseReader(ABC):
@@ -430,6 +431,12 @@ def ranks_host(matrix, thresholds, marks, base=0, exclude=None):
     the list of non-candidates, an integer (Q, E) array of positions that are not counted; an entry outside
     [base, base + n) is ignored, repeats count once. Counts of slices of a matrix, each with its base, add up to the count
     of the whole."""
+    return _precedes_host(matrix, thresholds, marks, base, exclude)[1].sum(axis=1, dtype=np.int64)
+
+
+def _precedes_host(matrix, thresholds, marks, base, exclude):
+    """(the matrix as contiguous float32, the bool (Q, n) array "column c of row q precedes the row's mark and is not named
+    by the row's list"): the one predicate of ranks_host and within_host"""
     matrix = np.ascontiguousarray(matrix, dtype=np.float32)
     count, n = matrix.shape
     thresholds, marks = rank_marks(thresholds, marks, count)
@@ -441,7 +448,20 @@ def ranks_host(matrix, thresholds, marks, base=0, exclude=None):
         exclude = np.asarray(exclude, dtype=np.int64).reshape(count, -1)
         named = (exclude >= base) & (exclude < base + n)
         precedes[np.nonzero(named)[0], (exclude - np.where(named, base, exclude))[named]] = False
-    return precedes.sum(axis=1, dtype=np.int64)
+    return matrix, precedes
+
+
+def within_host(matrix, thresholds, marks, base=0, exclude=None):
+    """The contract of include/memb_hip_within.h in numpy: (offsets int64 (Q + 1,), positions int64 (total,), values
+    float32 (total,)) of the float32 (Q, n) matrix -- the columns ranks_host counts, listed: row q's entries are
+    positions[offsets[q]:offsets[q + 1]], base + column ascending, and values holds the matrix's bits there. The lists of
+    slices of a matrix, each with its base, in ascending order of the bases, concatenate row by row to the lists of the
+    whole."""
+    matrix, precedes = _precedes_host(matrix, thresholds, marks, base, exclude)
+    offsets = np.zeros(matrix.shape[0] + 1, dtype=np.int64)
+    np.cumsum(precedes.sum(axis=1, dtype=np.int64), out=offsets[1:])
+    found_rows, columns = np.nonzero(precedes)   # (row by row, the columns of a row ascending)
+    return offsets, base + columns.astype(np.int64), matrix[found_rows, columns]
 
 
 QUERY_BAGS_DEVICE_SLICE = 1 << 16   # bags bag_similarity_matrix_device pools into a temporary at a time where no fused kernel exists
@@ -571,6 +591,7 @@ class Reader(BaseReader):
         self._last_query_topk_kernel = ''
         self._last_cosmul_kernel = ''
         self._last_ranks_kernel = ''
+        self._last_within_kernel = ''
         self._last_query_bags_kernel = ''
         self._last_query_bags_topk_kernel = ''
         self._all_rows = None              # every row id in order on the device, of similarity_topk_device(rows=None)
@@ -2170,30 +2191,9 @@ class Reader(BaseReader):
         Informational: the counts are the same.'''
         return self._last_ranks_kernel
 
-    def similarity_ranks_device(self, queries, rows, thresholds, marks=None, *, exclude=None, workspace=None):
-        '''Where a mark stands among ALL candidates of every query, left on the GPU, without the (Q, n) matrix of
-        similarity_matrix_device in device memory: an int64 (Q,) tensor, counts[q] the number of candidates of row q of
-        that matrix that PRECEDE the mark (thresholds[q], marks[q]) in similarity_topk_device's order -- a candidate at
-        position c (an index into `rows`) with cosine v precedes it where v is greater than thresholds[q] (NaN above every
-        number, -0.0 equal to +0.0), or equal and c < marks[q] (include/memb_hip_ranks.h). marks[q] = -1 counts the
-        strictly greater cosines, the largest int64 the greater-or-equal ones; with marks[q] the position of a candidate
-        and thresholds[q] the matrix's bits there, counts[q] is that candidate's 0-based rank: the slot it takes in
-        similarity_topk_device's output. No k, no limit of 64. For trained models whose dim is a multiple of 4 and at most
-        512 the matrix kernel fills a slice of the candidates in a workspace (about 32 MiB, independent of n) and two
-        kernels (rank_count, rank_fold) count it; otherwise slices of at most 2^19 candidates go through
-        similarity_matrix_device into one reused temporary and the same kernels (last_ranks_kernel says which).
-        queries : as in similarity_matrix_device
-        rows : as in similarity_topk_device; None: every row of the model in order, so positions are row ids
-        thresholds : contiguous float32 (Q,) tensor on the same device
-        marks : contiguous int64 (Q,) tensor on the same device; None: all -1
-        exclude : as in similarity_topk_device: positions that are no candidates of their query and are not counted
-        workspace : optional contiguous uint8 tensor on the same device, aligned to 8 bytes, of at least
-            _memb_ranks.query_ranks_workspace_bytes(self._impl.context_handle(), Q, n, minimal=True) bytes, for the fused
-            path: a call with it allocates nothing but its result (and the marks where None). Its size decides the
-            slicing, never the result.
-        One model, float32: no list of the preceding candidates themselves, no bfloat16 / float16, no ReadersUnion, no
-        ShardedReader, no pooled-bag candidates, no ranks under the 3CosMul score.'''
-        import torch
+    def _marks_arguments(self, torch, queries, rows, thresholds, marks, exclude):
+        """the checks similarity_ranks_device and similarity_within_device share, before anything is launched: (index,
+        queries as (Q, dim), Q, ld, rows flattened, n, device, the list of non-candidates as (pointer, E, row stride))"""
         index = self._impl.device()
         if index == _memb.HOST_DEVICE:
             raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
@@ -2219,6 +2219,33 @@ class Reader(BaseReader):
         excluded = (0, 0, 0) if exclude is None else self._topk_exclude(torch, exclude, count, device)
         rows = rows.reshape(-1)
         n = rows.numel()
+        return index, queries, count, ld, rows, n, device, excluded
+
+    def similarity_ranks_device(self, queries, rows, thresholds, marks=None, *, exclude=None, workspace=None):
+        '''Where a mark stands among ALL candidates of every query, left on the GPU, without the (Q, n) matrix of
+        similarity_matrix_device in device memory: an int64 (Q,) tensor, counts[q] the number of candidates of row q of
+        that matrix that PRECEDE the mark (thresholds[q], marks[q]) in similarity_topk_device's order -- a candidate at
+        position c (an index into `rows`) with cosine v precedes it where v is greater than thresholds[q] (NaN above every
+        number, -0.0 equal to +0.0), or equal and c < marks[q] (include/memb_hip_ranks.h). marks[q] = -1 counts the
+        strictly greater cosines, the largest int64 the greater-or-equal ones; with marks[q] the position of a candidate
+        and thresholds[q] the matrix's bits there, counts[q] is that candidate's 0-based rank: the slot it takes in
+        similarity_topk_device's output. No k, no limit of 64. For trained models whose dim is a multiple of 4 and at most
+        512 the matrix kernel fills a slice of the candidates in a workspace (about 32 MiB, independent of n) and two
+        kernels (rank_count, rank_fold) count it; otherwise slices of at most 2^19 candidates go through
+        similarity_matrix_device into one reused temporary and the same kernels (last_ranks_kernel says which).
+        queries : as in similarity_matrix_device
+        rows : as in similarity_topk_device; None: every row of the model in order, so positions are row ids
+        thresholds : contiguous float32 (Q,) tensor on the same device
+        marks : contiguous int64 (Q,) tensor on the same device; None: all -1
+        exclude : as in similarity_topk_device: positions that are no candidates of their query and are not counted
+        workspace : optional contiguous uint8 tensor on the same device, aligned to 8 bytes, of at least
+            _memb_ranks.query_ranks_workspace_bytes(self._impl.context_handle(), Q, n, minimal=True) bytes, for the fused
+            path: a call with it allocates nothing but its result (and the marks where None). Its size decides the
+            slicing, never the result.
+        One model, float32: the preceding candidates themselves are similarity_within_device's; no bfloat16 / float16, no
+        ReadersUnion, no ShardedReader, no pooled-bag candidates, no ranks under the 3CosMul score.'''
+        import torch
+        index, queries, count, ld, rows, n, device, excluded = self._marks_arguments(torch, queries, rows, thresholds, marks, exclude)
         context = self._impl.context_handle()
         fused = _memb_ranks.query_ranks_kernel_name(context)
         if fused or n == 0:
@@ -2254,12 +2281,9 @@ class Reader(BaseReader):
         self._last_ranks_kernel = self._last_query_matrix_kernel + '+' + _memb_ranks.dense_ranks_kernel_name()
         return counts
 
-    def similarity_ranks(self, queries, rows, thresholds, marks=None, exclude=None):
-        '''similarity_ranks_device for host arrays: a numpy float32 (Q, dim) or (dim,) array of queries, numpy row ids
-        (None: every row of the model), float32 (Q,) thresholds and int64 (Q,) marks (None: all -1) in, a numpy int64 (Q,)
-        array of counts out. A reader on a GPU sends everything up and brings the counts back; a device='cpu' reader takes
-        similarity_matrix chunk by chunk and counts in numpy (ranks_host): the same numbers. exclude: an integer (Q, E)
-        array, E <= 64.'''
+    def _host_marks_arguments(self, queries, rows, thresholds, marks, exclude):
+        """the checks similarity_ranks and similarity_within share: (queries (Q, dim), Q, rows uint32, thresholds, marks,
+        exclude int64 (Q, E) or None), contiguous"""
         queries = np.asarray(queries)
         if queries.dtype != np.float32:
             raise TypeError('queries must be a float32 array of shape (Q, dim) or (dim,)')
@@ -2280,6 +2304,15 @@ class Reader(BaseReader):
             if exclude.shape[1] > QUERY_TOPK_MAX_EXCLUDED:
                 raise ValueError('exclude names at most {} positions per query, got {}'.format(QUERY_TOPK_MAX_EXCLUDED, exclude.shape[1]))
             exclude = np.ascontiguousarray(exclude, dtype=np.int64)
+        return queries, count, rows, thresholds, marks, exclude
+
+    def similarity_ranks(self, queries, rows, thresholds, marks=None, exclude=None):
+        '''similarity_ranks_device for host arrays: a numpy float32 (Q, dim) or (dim,) array of queries, numpy row ids
+        (None: every row of the model), float32 (Q,) thresholds and int64 (Q,) marks (None: all -1) in, a numpy int64 (Q,)
+        array of counts out. A reader on a GPU sends everything up and brings the counts back; a device='cpu' reader takes
+        similarity_matrix chunk by chunk and counts in numpy (ranks_host): the same numbers. exclude: an integer (Q, E)
+        array, E <= 64.'''
+        queries, count, rows, thresholds, marks, exclude = self._host_marks_arguments(queries, rows, thresholds, marks, exclude)
         if self._impl.device() != _memb.HOST_DEVICE:
             import torch
             device = 'cuda:{}'.format(self._impl.device())
@@ -2428,6 +2461,241 @@ class Reader(BaseReader):
             'accuracy': float((answered == 1).sum() / answered.size) if answered.size else 0.0,
             'mean_reciprocal_rank': float((1.0 / answered).mean()) if answered.size else 0.0,
         }
+
+    # ---- the candidates that precede a mark, listed: closer_than as words, a radius search (include/memb_hip_within.h) ----
+
+    @property
+    def last_within_kernel(self):
+        '''The kernel families of the last fill of similarity_within_device, joined by '+':
+        'query_matrix_trained+within_count+within_starts+within_write' (slices of the fused matrix kernel in a workspace,
+        compacted there), or 'pairs_dense+within_count+within_starts+within_write' where the cosines of a slice come from
+        similarity_matrix_device's fallback -- uniform and full storage, dims that are no multiple of 4 or beyond 512;
+        'within_starts' where such a model is asked with no candidate at all. '' before any call and after a call without
+        queries, which launches nothing. Informational: the lists are the same.'''
+        return self._last_within_kernel
+
+    def similarity_within_device(self, queries, rows, thresholds, marks=None, *, exclude=None, return_values=True, offsets=None,
+                                 capacity=None, workspace=None):
+        '''The candidates similarity_ranks_device COUNTS, themselves, left on the GPU, without the (Q, n) matrix of
+        similarity_matrix_device in device memory: (offsets, positions, values) in CSR form -- offsets an int64 (Q + 1,)
+        tensor, positions an int64 (total,) tensor and values a float32 (total,) tensor (None with return_values=False).
+        positions[offsets[q]:offsets[q + 1]] are the candidates of query q (indices into `rows`) that precede the mark
+        (thresholds[q], marks[q]) and are not named by exclude[q], ASCENDING, and values holds the matrix's bits there
+        (include/memb_hip_within.h). marks[q] = -1 lists the cosines strictly greater than thresholds[q], the largest int64
+        the greater-or-equal ones: every candidate within a radius, however many. The result depends on the arguments
+        alone, never on the slicing. For trained models whose dim is a multiple of 4 and at most 512 the matrix kernel fills
+        a slice of the candidates in a workspace and three kernels (within_count, within_starts, within_write) compact it
+        in order; otherwise slices of at most 2^19 candidates go through similarity_matrix_device into one reused temporary
+        and the same kernels (last_within_kernel says which).
+        queries, rows, thresholds, marks, exclude : as in similarity_ranks_device
+        offsets : None: the sizes come from similarity_ranks_device -- a second pass over the candidates --, their running
+            sum is the offsets and its last entry is read on the host to size the result: ONE synchronisation. Or a
+            contiguous int64 (Q + 1,) tensor on the same device, non-decreasing from offsets[0] >= 0: the segments the
+            caller chose, filled by the one call, and the result is (offsets, positions, values, found), found an int64
+            (Q,) tensor of what each query found whatever its segment holds. A segment that is too short keeps the first
+            entries of its list and found[q] > offsets[q + 1] - offsets[q] says so; nothing is written outside it.
+        capacity : with offsets given, the entries positions and values are allocated with (what lies outside every
+            segment is left as allocated); the call then synchronises nothing and can be captured into a graph. None:
+            offsets[Q] is read on the host, one synchronisation. Nothing checks that capacity covers offsets[Q]: entries
+            whose place lies at or beyond capacity are dropped like those beyond a segment's end, and only
+            found[q] > min(offsets[q + 1], capacity) - offsets[q] tells.
+        workspace : optional contiguous uint8 tensor on the same device, aligned to 8 bytes, of at least
+            _memb_within.query_within_workspace_bytes(self._impl.context_handle(), Q, n, minimal=True) bytes, for the fused
+            path (it serves the count pass too). Its size decides the slicing, never the result.
+        One model, float32: no bfloat16 / float16, no ReadersUnion, no ShardedReader, no pooled-bag candidates, no lists
+        under the 3CosMul score, no output sorted by cosine (torch.sort of a segment of values does that).'''
+        import torch
+        index, queries, count, ld, rows, n, device, excluded = self._marks_arguments(torch, queries, rows, thresholds, marks, exclude)
+        context = self._impl.context_handle()
+        fused = _memb_within.query_within_kernel_name(context)
+        if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1
+                                      or not workspace.is_contiguous() or workspace.device != device):
+            raise TypeError('workspace must be a contiguous uint8 tensor on cuda:{}'.format(index))
+        given = offsets is not None
+        if given:
+            if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64:
+                raise TypeError('offsets must be an int64 tensor of shape (Q + 1,)')
+            if offsets.device != device:
+                raise ValueError('offsets must be on {} (the device this reader is staged on), got {}'.format(device, offsets.device))
+            if offsets.dim() != 1 or offsets.shape[0] != count + 1 or not offsets.is_contiguous():
+                raise ValueError('offsets must be contiguous with shape (Q + 1,) = ({},), got {}'.format(count + 1, tuple(offsets.shape)))
+            if capacity is not None and (isinstance(capacity, bool) or int(capacity) != capacity or capacity < 0):
+                raise ValueError('capacity must be a non-negative integer, got {!r}'.format(capacity))
+        elif capacity is not None:
+            raise ValueError('capacity goes with offsets: without them the call sizes its result itself')
+        self._last_within_kernel = ''
+        if not given:
+            counts = self.similarity_ranks_device(queries, rows, thresholds, marks, exclude=exclude, workspace=workspace)
+            offsets = torch.zeros((count + 1,), dtype=torch.int64, device=device)
+            torch.cumsum(counts, 0, out=offsets[1:])
+        if capacity is None:
+            capacity = offsets[-1].item()   # (the one synchronisation)
+        capacity = int(capacity)
+        # (at least one entry is allocated, so that the outputs have an address where nothing is to be listed)
+        held_positions = torch.empty((max(capacity, 1),), dtype=torch.int64, device=device)
+        held_values = torch.empty((max(capacity, 1),), dtype=torch.float32, device=device) if return_values else None
+        positions, values = held_positions[:capacity], held_values[:capacity] if return_values else None
+        found = torch.empty((count,), dtype=torch.int64, device=device)
+        result = (offsets, positions, values, found) if given else (offsets, positions, values)
+        if count == 0:   # (nothing is launched)
+            return result
+        if marks is None:
+            marks = torch.full((count,), -1, dtype=torch.int64, device=device)
+        stream = _current_stream(torch, index)
+        output = (offsets.data_ptr(), found.data_ptr(), held_positions.data_ptr(), held_values.data_ptr() if return_values else 0, capacity)
+        if fused or n == 0:
+            self._last_within_kernel = fused or 'within_starts'   # (no candidate: within_starts alone writes zeros, whatever the model)
+            if workspace is None:
+                workspace = torch.empty((_memb_within.query_within_workspace_bytes(context, count, n),), dtype=torch.uint8, device=device)
+            done = _memb_within.query_within_to_device(
+                context, queries.data_ptr(), count, ld, rows.data_ptr(), n, thresholds.data_ptr(), marks.data_ptr(), *excluded,
+                *output, workspace.data_ptr() if workspace.numel() else 0, workspace.numel(), stream)
+            assert done   # (n == 0 is answered for every model)
+            return result
+        width = min(n, QUERY_DEVICE_SLICE)
+        temporary = torch.empty((count, width), dtype=torch.float32, device=device)
+        blocks = torch.empty((_memb_within.dense_within_workspace_bytes(count, width),), dtype=torch.uint8, device=device)
+        for start in range(0, n, QUERY_DEVICE_SLICE):   # (ascending, as the lists are)
+            size = min(n, start + QUERY_DEVICE_SLICE) - start
+            self.similarity_matrix_device(queries, rows[start:start + size], out=temporary[:, :size])
+            _memb_within.dense_within_to_device(
+                index, temporary.data_ptr(), count, size, width, start, thresholds.data_ptr(), marks.data_ptr(), *excluded,
+                start > 0, *output, blocks.data_ptr(), blocks.numel(), stream)
+        self._last_within_kernel = self._last_query_matrix_kernel + '+' + _memb_within.dense_within_kernel_name()
+        return result
+
+    def similarity_within(self, queries, rows, thresholds, marks=None, exclude=None):
+        '''similarity_within_device for host arrays: numpy queries, row ids (None: every row of the model), float32 (Q,)
+        thresholds and int64 (Q,) marks (None: all -1) in, numpy (offsets int64 (Q + 1,), positions int64 (total,), values
+        float32 (total,)) out. A reader on a GPU sends everything up and brings the lists back; a device='cpu' reader takes
+        similarity_matrix chunk by chunk and lists in numpy (within_host): the same bits. exclude: an integer (Q, E) array,
+        E <= 64.'''
+        queries, count, rows, thresholds, marks, exclude = self._host_marks_arguments(queries, rows, thresholds, marks, exclude)
+        if self._impl.device() != _memb.HOST_DEVICE:
+            import torch
+            device = 'cuda:{}'.format(self._impl.device())
+            return tuple(part.cpu().numpy() for part in self.similarity_within_device(
+                torch.from_numpy(queries).to(device), torch.from_numpy(rows.view(np.int32)).to(device),
+                torch.from_numpy(thresholds).to(device), torch.from_numpy(marks).to(device),
+                exclude=None if exclude is None else torch.from_numpy(exclude).to(device)))
+        chunks = [within_host(self.similarity_matrix(queries, rows[start:start + NORMS_HOST_CHUNK]), thresholds, marks, start, exclude)
+                  for start in range(0, rows.size, NORMS_HOST_CHUNK)]
+        offsets = np.zeros(count + 1, dtype=np.int64)
+        np.cumsum(sum((np.diff(chunk[0]) for chunk in chunks), np.zeros(count, dtype=np.int64)), out=offsets[1:])
+        positions = np.empty(offsets[-1], dtype=np.int64)
+        values = np.empty(offsets[-1], dtype=np.float32)
+        filled = offsets[:-1].copy()   # (where row q goes on: the chunks come in ascending order)
+        for chunk_offsets, chunk_positions, chunk_values in chunks:
+            sizes = np.diff(chunk_offsets)
+            of_row = np.repeat(np.arange(count), sizes)
+            target = filled[of_row] + np.arange(chunk_positions.size) - chunk_offsets[of_row]
+            positions[target], values[target] = chunk_positions, chunk_values
+            filled += sizes
+        return offsets, positions, values
+
+    @staticmethod
+    def _no_list_where(torch, unanswered, thresholds, marks):
+        """the marks of queries that list nothing: a NaN threshold has the greatest key, and no position is below -1"""
+        return (torch.where(unanswered, torch.full_like(thresholds, float('nan')), thresholds),
+                torch.where(unanswered, torch.full_like(marks, -1), marks))
+
+    def closer_than_device(self, words_a, words_b):
+        '''gensim's closer_than(a, b) for pairs of words, left on the GPU: (offsets, rows), an int64 (P + 1,) and an int64
+        (total,) tensor -- rows[offsets[i]:offsets[i + 1]] are the row ids (positions in keys()), ascending, of the words of
+        the WHOLE model that are closer to words_a[i] than words_b[i] is: exactly the words rank_device counts, so
+        offsets[i + 1] - offsets[i] == rank_device(...)[i] - 1. words_a[i] itself is no candidate; equal cosines: the lower
+        row is the closer one. An empty list where either word is not in the model. One synchronisation
+        (similarity_within_device's).'''
+        import torch
+        index = self._impl.device()
+        if index == _memb.HOST_DEVICE:
+            raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
+        words_a, words_b = list(words_a), list(words_b)
+        if len(words_a) != len(words_b):
+            raise ValueError('words_a and words_b must hold one word per pair, got {} and {}'.format(len(words_a), len(words_b)))
+        device = 'cuda:{}'.format(index)
+        count = len(words_a)
+        if count == 0:
+            return torch.zeros((1,), dtype=torch.int64, device=device), torch.empty((0,), dtype=torch.int64, device=device)
+        own = self.resolve_rows_device(words_a + words_b)
+        first, second = own[:count].contiguous(), own[count:].contiguous()
+        queries = self.unit_rows_embedding_device(first)
+        groups = torch.arange(count + 1, dtype=torch.int32, device=queries.device)
+        thresholds = self.query_similarity_device(queries, second, groups)   # (one candidate per group: the matrix's bits)
+        thresholds, marks = self._no_list_where(torch, (first < 0) | (second < 0), thresholds, second.to(torch.int64))
+        offsets, rows, _ = self.similarity_within_device(
+            queries, None, thresholds, marks, exclude=first.to(torch.int64).unsqueeze(1), return_values=False)
+        return offsets, rows
+
+    def closer_than(self, a, b):
+        '''gensim's closer_than(a, b): the list of the words of the whole model that are closer to the word a than the word
+        b is, in row order (the order of keys()); a itself is no candidate, equal cosines: the lower row is the closer one.
+        len() of it is count_closer_than([a], [b])[0]. [] where a or b is not in the model. closer_than_device on a GPU
+        reader; a device='cpu' reader goes through unit_rows_embedding, query_similarity and similarity_within: the same
+        words.'''
+        if self._impl.device() != _memb.HOST_DEVICE:
+            rows = self.closer_than_device([a], [b])[1].cpu().numpy()
+        else:
+            own = self.resolve_rows([a, b])
+            if (own == 0xFFFFFFFF).any():
+                return []
+            queries = self.unit_rows_embedding(own[:1])
+            thresholds = self.query_similarity(queries, own[1:], np.arange(2))
+            rows = self.similarity_within(queries, None, thresholds, own[1:].astype(np.int64), exclude=own[:1].astype(np.int64)[:, None])[1]
+        vocabulary = self.keys()
+        return [vocabulary[row] for row in rows]
+
+    @staticmethod
+    def _min_cosine(min_cosine):
+        """min_cosine as a float32; TypeError / ValueError unless it is a number"""
+        if isinstance(min_cosine, bool) or not isinstance(min_cosine, numbers.Real):
+            raise TypeError('min_cosine must be a number')
+        if np.isnan(min_cosine):
+            raise ValueError('min_cosine must be a number, got NaN')
+        return np.float32(min_cosine)
+
+    def words_within_device(self, words, min_cosine):
+        '''Every word within a radius of each word, left on the GPU: (offsets, rows, values), an int64 (len(words) + 1,), an
+        int64 (total,) and a float32 (total,) tensor -- rows[offsets[i]:offsets[i + 1]] are the row ids, ascending, of the
+        words of the WHOLE model whose cosine to words[i] is at least min_cosine (compared as float32), the word itself
+        left out, and values their cosines: similarity_within_device with the mark at the largest int64. An empty list for
+        a word that is not in the model. One synchronisation.'''
+        import torch
+        index = self._impl.device()
+        if index == _memb.HOST_DEVICE:
+            raise RuntimeError("this reader decodes on the host (device 'cpu'): device buffers need a reader on a HIP device")
+        min_cosine = self._min_cosine(min_cosine)
+        words = list(words)
+        device = 'cuda:{}'.format(index)
+        if not words:
+            return (torch.zeros((1,), dtype=torch.int64, device=device), torch.empty((0,), dtype=torch.int64, device=device),
+                    torch.empty((0,), dtype=torch.float32, device=device))
+        own = self.resolve_rows_device(words)
+        thresholds = torch.full((len(words),), float(min_cosine), dtype=torch.float32, device=device)
+        marks = torch.full((len(words),), np.iinfo(np.int64).max, dtype=torch.int64, device=device)
+        thresholds, marks = self._no_list_where(torch, own < 0, thresholds, marks)
+        return self.similarity_within_device(self.unit_rows_embedding_device(own), None, thresholds, marks, exclude=own.to(torch.int64).unsqueeze(1))
+
+    def words_within(self, words, min_cosine):
+        '''Every word within a radius of each word, on the host: one list of (word, cosine) pairs per word, in row order
+        (the order of keys()), with cosine >= min_cosine, the word itself left out; [] for a word the model lacks.
+        words_within_device on a GPU reader, similarity_within on a device='cpu' reader: the same pairs.'''
+        min_cosine = self._min_cosine(min_cosine)
+        words = list(words)
+        if not words:
+            return []
+        if self._impl.device() != _memb.HOST_DEVICE:
+            offsets, rows, values = (part.cpu().numpy() for part in self.words_within_device(words, min_cosine))
+        else:
+            own = self.resolve_rows(words)
+            missing = own == 0xFFFFFFFF
+            thresholds = np.where(missing, np.float32(np.nan), min_cosine).astype(np.float32)
+            marks = np.where(missing, -1, np.iinfo(np.int64).max).astype(np.int64)
+            exclude = np.where(missing, -1, own.astype(np.int64))[:, None]
+            offsets, rows, values = self.similarity_within(self.unit_rows_embedding(own), None, thresholds, marks, exclude=exclude)
+        vocabulary = self.keys()
+        return [[(vocabulary[row], float(value)) for row, value in zip(rows[offsets[i]:offsets[i + 1]], values[offsets[i]:offsets[i + 1]])]
+                for i in range(len(words))]
 
     # ---- every query against every pooled bag of rows, matrix and top-k (include/memb_hip_query_bags.h) ----
 

@@ -2,7 +2,7 @@
 registers, scratch and LDS, read from the device assembly (no GPU needed).
 
     python tools/perf/isa.py [substring of the demangled kernel name] [-- extra hipcc flags]
-    python tools/perf/isa.py --digests     one line per kernel of every translation unit of libmemb_hip.so (WITH_RANKS),
+    python tools/perf/isa.py --digests     one line per kernel of every translation unit of libmemb_hip.so (WITH_WITHIN),
                                            instruction digest and resources: run it on two commits and diff the listings
                                            to see which kernels a change touched
 
@@ -59,9 +59,13 @@ WITH_ANALOGIES = WITH_QUERY_BAGS + (ANALOGIES_SOURCE,)
 COSMUL_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_cosmul.hip')
 WITH_COSMUL = WITH_ANALOGIES + (COSMUL_SOURCE,)
 # the unit of the rank counts, kept out of WITH_COSMUL likewise (tests/test_cosmul_isa.py pins it); WITH_RANKS is every
-# translation unit of the library today, and what --digests lists
+# translation unit of the library before the unit of the lists
 RANKS_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_ranks.hip')
 WITH_RANKS = WITH_COSMUL + (RANKS_SOURCE,)
+# the unit of the lists of the candidates before a mark, kept out of WITH_RANKS likewise (tests/test_ranks_isa.py pins it);
+# WITH_WITHIN is every translation unit of the library today, and what --digests lists
+WITHIN_SOURCE = os.path.join(REPO, 'memb_amd', 'csrc', 'memb_hip_within.hip')
+WITH_WITHIN = WITH_RANKS + (WITHIN_SOURCE,)
 # the flags of build_native.build_hip_library
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt',
          '-Wno-unused-value', '-Wno-align-mismatch', '-Wno-pass-failed', '-Wno-unused-command-line-argument']
@@ -95,7 +99,7 @@ def _instructions(code, symbol):
 def kernel_table(extra_flags=(), source=SOURCE):
     """{demangled kernel name: facts} for every kernel of one translation unit of libmemb_hip.so (default memb_hip.hip;
     NARROW_SOURCE: the bf16 / fp16 decode kernels; POOLED_SOURCE: every sequential pooled kernel; POOLED_CHUNKED_SOURCE: the
-    chunked order's; POOLED_UNION_SOURCE: the pooled kernels of averaged unions and of dense rows; NORMS_SOURCE: row norms and unit rows; PAIRS_SOURCE: the cosine of row pairs; BAG_PAIRS_SOURCE: the cosine of pairs of pooled bags; QUERIES_SOURCE: the cosine of query vectors against groups of rows; QUERY_MATRIX_SOURCE: the cosine of every query against one shared list of rows; QUERY_TOPK_SOURCE: the k best columns of every row of a matrix; QUERY_BAGS_SOURCE: the cosine of every query against every pooled bag of rows; ANALOGIES_SOURCE: the selection with exclusion lists and sums of weighted rows; COSMUL_SOURCE: the 3CosMul scores; RANKS_SOURCE: the number of candidates that precede a mark; or any other path, such as a unit of another checkout)"""
+    chunked order's; POOLED_UNION_SOURCE: the pooled kernels of averaged unions and of dense rows; NORMS_SOURCE: row norms and unit rows; PAIRS_SOURCE: the cosine of row pairs; BAG_PAIRS_SOURCE: the cosine of pairs of pooled bags; QUERIES_SOURCE: the cosine of query vectors against groups of rows; QUERY_MATRIX_SOURCE: the cosine of every query against one shared list of rows; QUERY_TOPK_SOURCE: the k best columns of every row of a matrix; QUERY_BAGS_SOURCE: the cosine of every query against every pooled bag of rows; ANALOGIES_SOURCE: the selection with exclusion lists and sums of weighted rows; COSMUL_SOURCE: the 3CosMul scores; RANKS_SOURCE: the number of candidates that precede a mark; WITHIN_SOURCE: the list of those candidates; or any other path, such as a unit of another checkout)"""
     text = device_assembly(extra_flags, source)
     names = re.findall(r'^\s*\.amdhsa_kernel (\S+)$', text, flags=re.M)
     demangled = subprocess.run([_tool('c++filt')], input='\n'.join(names), stdout=subprocess.PIPE, text=True,
@@ -170,7 +174,7 @@ if __name__ == '__main__':
         extra = arguments[arguments.index('--') + 1:]
         arguments = arguments[:arguments.index('--')]
     if arguments[:1] == ['--digests']:   # one line per kernel, to diff against another commit's; [units of that commit]
-        for pretty, facts in sorted(kernel_digests(arguments[1:] or WITH_RANKS).items()):
+        for pretty, facts in sorted(kernel_digests(arguments[1:] or WITH_WITHIN).items()):
             print(pretty.replace('(anonymous namespace)::', '').split('(')[0], *facts)
         sys.exit(0)
     needle = arguments[0] if arguments else ''
